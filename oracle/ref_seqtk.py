@@ -9,9 +9,16 @@ import subprocess
 _HERE = pathlib.Path(__file__).resolve().parent
 
 
+def sources_reachable():
+    """Whether the recipe (oracle/Makefile `ref`) can read the reference's sources: make's question mode answers 2 when
+    a prerequisite is missing or cannot be read (no reference tree, or one this user may not enter)."""
+    return subprocess.call(["make", "-s", "-q", "-C", str(_HERE), "ref"],
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) != 2
+
+
 def load(build=True):
     found = glob.glob(str(_HERE / "_ref" / "seqtk*.so"))
-    if not found and build and pathlib.Path("/root/reference/mapdamage/seqtk/seqtk.c").exists():
+    if not found and build and sources_reachable():
         subprocess.check_call(["make", "-s", "-C", str(_HERE), "ref"])
         found = glob.glob(str(_HERE / "_ref" / "seqtk*.so"))
     if not found:

@@ -48,13 +48,13 @@ def test_two_engines_on_one_gpu_shard_and_reduce_match_oracle():
 
 @pytest.mark.gpu
 def test_bench_line_at_two_ranks_verifies_itself():
-    """bench.py --gpus 2 on one GPU (--share-gpu, blocks summed over gloo): the N > 1 line carries `parity` (every
+    """bench.py --gpus 2 --full on one GPU (--share-gpu, blocks summed over gloo): the N > 1 line carries `parity` (every
     rank's own block against the oracle) and `reduction` (all-reduced block == sum of the ranks' blocks)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--reads", "300000", "--steps", "3", "--warmup", "1",
-           "--backend", "gloo", "--share-gpu"]
+           "--backend", "gloo", "--share-gpu", "--full"]
     out = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -65,19 +65,19 @@ def test_bench_line_at_two_ranks_verifies_itself():
 
 @pytest.mark.gpu
 def test_bench_line_with_rccl_initialised(tmp_path):
-    """bench.py at N = 1 with the process group up: the all-reduce of the timed region goes through RCCL."""
+    """bench.py --full at N = 1 with the process group up: the all-reduce of the timed region goes through RCCL."""
     import json
     env = dict(os.environ, MASTER_PORT="29553", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, str(ROOT / "bench.py"), "--reads", "400000", "--steps", "3", "--warmup", "1",
-           "--force-dist", "--secondary-reads", "200000", "--genome-copies", "20"]
+           "--force-dist", "--full", "--secondary-reads", "200000", "--genome-copies", "20"]
     out = subprocess.run(cmd, cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["parity"].startswith("bit-exact")
     assert line["roofline"]["frac"] > 0 and line["cpu_baseline"]["value"] > 0
     sec = line["secondary"]
-    assert set(sec) == {"config2", "config4", "config5", "minqual", "nlib8", "nlib8_q20", "rescale_file", "file_to_tables", "config3_genome3g", "file_to_tables_50m",
-                        "cli_wall"}
+    assert set(sec) == {"config2", "config4", "short_reads", "config5", "minqual", "nlib8", "nlib8_q20", "rescale_file", "file_to_tables",
+                        "config3_genome3g", "file_to_tables_50m", "cli_wall"}
     assert sec["minqual"]["q20_kernel_ms"] > 0 and sec["minqual"]["q0_kernel_ms"] > 0
     # (eight libraries: one launch of the packed kernel per call, the resident batch brings its copy ordered by library)
     assert sec["nlib8"]["packed_launches_per_call"] == 1 and sec["nlib8"]["sorts_inside_the_launches"] == 0
