@@ -339,6 +339,32 @@ int64_t mdx_libsorts(const mdx_ctx *ctx);
 int64_t mdx_rescale_summary_words(const mdx_ctx *ctx);
 int mdx_rescale_summary(mdx_ctx *ctx, uint64_t *words);
 
+/* Input sources (additions of ABI 6; every entry point that takes a path opens one of its own).  A source is the compressed
+ * input opened once: a regular file — and "-" when fd 0 is one (`< x.bam`), from fd 0's current offset — is mapped as
+ * before; anything else — a pipe, FIFO, character device or socket: "-", /dev/stdin, /dev/fd/N, a named pipe — is a stream,
+ * read front to back, once, by a thread of the source's own into a window.  The window holds the bytes from the release
+ * point on: a stream's consumer gives back what it will not read again (mdx_bam_next: the blocks it has inflated;
+ * mdx_gbam_next: everything in front of mdx_gbam_tell's position, where a host decoder can take the stream up with
+ * mdx_bam_seek), and the reader stops when it is 16 MiB ahead of that point, or as far ahead as a consumer has asked for if
+ * that is farther (the device decoder: three slabs) — memory stays bounded however long the stream is.  Reading or seeking
+ * in front of the release point is MDX_ERR_ARG with a message, never a wait.  A pipe's buffer is raised to what this
+ * process may set (F_SETPIPE_SZ on the source's own descriptor).  The one-piece decode (mdx_bam_read_source) reads a stream
+ * to its end: memory in proportion to the stream.  A stream that ends inside a block, a damaged block, an empty stream: the
+ * same codes and texts as the same bytes in a file.
+ *   mdx_source_open    *out is set even on failure (mdx_source_error says why; close it)
+ *   mdx_source_peek    the first n bytes (fewer: the input is shorter), e.g. to tell SAM from BAM; a stream waits for them
+ *   mdx_source_read    the next bytes in order (SAM text), the peeked ones included: how many, 0 at the end, -1 on error
+ *   mdx_*_open_source  the handles take a reference of their own: the source may be closed behind them, and lives until the
+ *                      last of them is closed (mdx_source_close, mdx_bam_close, mdx_gbam_close)
+ * A caller that holds a descriptor opens "/dev/fd/N". */
+typedef struct mdx_source mdx_source;
+int mdx_source_open(const char *path, mdx_source **out);
+const char *mdx_source_error(const mdx_source *source);
+int mdx_source_is_stream(const mdx_source *source);
+int mdx_source_peek(mdx_source *source, uint8_t *buf, int32_t n, int32_t *got);
+int64_t mdx_source_read(mdx_source *source, uint8_t *buf, int64_t cap);
+void mdx_source_close(mdx_source *source);
+
 /* Native BAM decoding (host side, no GPU involved).  Replaces opening and iterating a
  * pysam.AlignmentFile (mapdamage/reader.py:38, 83-96; pysam is not needed): the BGZF blocks are
  * inflated on `threads` host threads and every record is unpacked into the SoA columns of mdx_batch.
@@ -348,6 +374,7 @@ int mdx_rescale_summary(mdx_ctx *ctx, uint64_t *words);
  * the rescale routing; has_mr flags records that already carry an MR tag (rescale.py:277). */
 typedef struct mdx_bam mdx_bam;
 int mdx_bam_read(const char *path, int threads, mdx_bam **out);
+int mdx_bam_read_source(mdx_source *source, int threads, mdx_bam **out);
 void mdx_bam_free(mdx_bam *bam);
 const char *mdx_bam_error(const mdx_bam *bam);
 const char *mdx_bam_header_text(const mdx_bam *bam);
@@ -371,6 +398,7 @@ const char *mdx_bam_qnames(const mdx_bam *bam, const uint32_t **offsets);
  * stream; chunks may be consumed on other threads. */
 typedef struct mdx_bam_stream mdx_bam_stream;
 int mdx_bam_open(const char *path, int threads, mdx_bam_stream **out);
+int mdx_bam_open_source(mdx_source *source, int threads, mdx_bam_stream **out);
 const mdx_bam *mdx_bam_stream_header(const mdx_bam_stream *stream);
 int mdx_bam_next(mdx_bam_stream *stream, int64_t chunk_bytes, mdx_bam **out);
 /* Points the stream at the BGZF block at compressed offset comp_off; the next chunk starts with the record `phase`
@@ -446,6 +474,7 @@ int mdx_table_mode(const mdx_ctx *ctx);
 typedef struct mdx_gbam mdx_gbam;
 int mdx_ctx_stream(mdx_ctx *ctx, void **stream, int *device);
 int mdx_gbam_open(mdx_ctx *ctx, const char *path, mdx_gbam **out);
+int mdx_gbam_open_source(mdx_ctx *ctx, mdx_source *source, mdx_gbam **out);
 const mdx_bam *mdx_gbam_header(const mdx_gbam *g);
 const char *mdx_gbam_error(const mdx_gbam *g);
 int mdx_gbam_configure(mdx_gbam *g, int32_t n_rg, const char *const *rg_ids, const int32_t *lib_of_rg, int32_t lib_default,

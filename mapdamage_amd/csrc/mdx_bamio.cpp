@@ -9,6 +9,7 @@
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
+#include <poll.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -16,6 +17,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <functional>
@@ -136,13 +138,12 @@ struct mdx_bam {
 };
 
 
-namespace { struct MappedFile; }
 
 // Streaming decode: the file is consumed a slab of BGZF blocks at a time, so host memory is bounded by the
 // chunk size and the caller can tabulate chunk k while chunk k+1 is being decoded.
 struct mdx_bam_stream {
     mdx_bam head;                    // header text + reference dictionary (no records); also carries the error text
-    MappedFile *file = nullptr;
+    mdx_source *file = nullptr;      // (one reference held: mdx_bam_close drops it)
     size_t coff = 0;                 // compressed offset of the first block not inflated yet
     int threads = 1;
     bool eof = false;
@@ -158,31 +159,200 @@ namespace {
 
 struct Block { size_t in_off, in_size, out_off, out_size; uint32_t crc; };   // crc: CRC32 of the inflated bytes (gzip trailer)
 
-// The compressed file, mapped read-only: the inflating threads read the page cache directly (an fread of the
-// whole file into a buffer first was a single-threaded copy, a quarter of the decode time on a 64-thread host).
-struct MappedFile {
+}  // namespace
+
+// The compressed input, addressed by absolute offset (p + off, (*this)[off]) whatever it is:
+//  * a regular file — `-` too, when fd 0 is one: mapped read-only (the inflating threads read the page cache directly: an
+//    fread of the whole file into a buffer first was a single-threaded copy, a quarter of the decode time on a 64-thread
+//    host); fd 0 from its current offset on;
+//  * anything else (pipe, FIFO, character device, socket, /dev/stdin, /dev/fd/N): a stream, read once, front to back, by a
+//    thread of its own into a window — one reservation of address space, committed ahead of the reader and handed back
+//    behind the consumer (release).  size() is what has come in so far, reach(x) waits until [0, x) is there or the stream
+//    has ended, and the bytes in front of the release point are gone (kept_from).  The reader stops when it is kReadAhead
+//    bytes ahead of the release point, or as far as a consumer has asked for (reach) if that is farther: memory is bounded
+//    by what the consumer needs at once — the device decoder, three slabs — and never grows with the stream.
+// One source is shared by every handle opened on it (reference-counted: mdx_source_close, mdx_bam_close, mdx_gbam_close).
+struct mdx_source {
+    // (huge pages in the window: the reader's first touch of 4 KiB pages was a page fault per 4 KiB, half of what a pipe of
+    // 2.4 GB cost; released in whole huge pages)
+    static constexpr size_t kReadAhead = (size_t)16 << 20, kCommitStep = (size_t)8 << 20, kReleaseStep = (size_t)2 << 20;
     const uint8_t *p = nullptr;
     size_t n = 0;
-    int fd = -1;                     // kept open: the device decode's host threads read their blocks with pread()
-    bool open(const char *path, std::string &err) {
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) { err = std::string("cannot open ") + path; return false; }
-        struct stat st;
-        if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) { ::close(fd); fd = -1; err = std::string("not a regular file: ") + path; return false; }
-        n = (size_t)st.st_size;
+    int fd = -1;                     // a regular file's, kept open: the device decode's host threads read their blocks with pread()
+    size_t fd_off = 0;               // ... at this offset in it (fd 0, redirected from a file that has been read in part)
+    void *map = nullptr;
+    size_t map_len = 0;
+    std::string path, error;
+    size_t rpos = 0;                 // mdx_source_read's position
+    std::atomic<int> refs{1};
+    struct Window {
+        int fd = -1, wake[2] = {-1, -1};
+        uint8_t *base = nullptr;             // (2 MiB-aligned, inside the reservation [resv, resv + resv_len))
+        void *resv = nullptr;
+        size_t resv_len = 0;
+        size_t reserved = 0, committed = 0, kept = 0, limit = kReadAhead;
+        std::atomic<size_t> seen{0};
+        bool ended = false, stop = false;
+        int err = 0;
+        std::mutex mu;
+        std::condition_variable cv;
+        std::thread reader;
+        void run();
+    };
+    Window *w = nullptr;             // a stream's
+
+    bool open(const char *path_, std::string &err);
+    void close();
+    ~mdx_source() { close(); }
+    bool is_stream() const { return w != nullptr; }
+    size_t size() const { return w ? w->seen.load(std::memory_order_acquire) : n; }
+    const uint8_t &operator[](size_t i) const { return p[i]; }
+    // [0, upto) present, or the stream has ended: what has come in (a file: all of it, at once)
+    size_t reach(size_t upto) const {
+        if (!w) return n;
+        const size_t have = w->seen.load(std::memory_order_acquire);
+        return have >= upto ? have : wait_for(upto);
+    }
+    bool at_end(size_t off) const { return reach(off + 1) <= off; }
+    size_t kept_from() const {
+        if (!w) return 0;
+        std::lock_guard<std::mutex> lk(w->mu);
+        return w->kept;
+    }
+    // nothing in front of `upto` is needed any more (a file: nothing happens)
+    void release(size_t upto) const {
+        if (!w) return;
+        std::lock_guard<std::mutex> lk(w->mu);
+        const size_t to = std::min(upto, w->seen.load()) / kReleaseStep * kReleaseStep;
+        if (to <= w->kept) return;
+        (void)madvise(w->base + w->kept, to - w->kept, MADV_DONTNEED);
+        (void)mprotect(w->base + w->kept, to - w->kept, PROT_NONE);
+        w->kept = to;
+        w->cv.notify_all();
+    }
+    std::string behind(size_t off) const {
+        return "offset " + std::to_string(off) + " of " + path + " lies behind the part of the stream still held (from " +
+               std::to_string(kept_from()) + " on): a stream is read once";
+    }
+
+  private:
+    size_t wait_for(size_t upto) const {
+        std::unique_lock<std::mutex> lk(w->mu);
+        // (a consumer that needs more at once than the reader may hold: the reader may hold that much — it must not wait
+        // for a release that only this consumer's progress would bring)
+        if (upto > w->kept + w->limit) { w->limit = upto - w->kept + kReadAhead; w->cv.notify_all(); }
+        w->cv.wait(lk, [&] { return w->seen.load() >= upto || w->ended; });
+        return w->seen.load();
+    }
+};
+
+void mdx_source::Window::run() {
+    const size_t kRead = (size_t)1 << 20;
+    for (;;) {
+        size_t at = 0, room = 0;
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return stop || seen.load() < kept + limit; });
+            if (stop) return;
+            at = seen.load();
+            room = std::min(kRead, kept + limit - at);
+            if (at + room > reserved) room = reserved - at;
+            if (room == 0) { err = EFBIG; ended = true; cv.notify_all(); return; }
+            if (at + room > committed) {
+                const size_t to = std::min(reserved, (at + room + kCommitStep - 1) / kCommitStep * kCommitStep);
+                if (mprotect(base + committed, to - committed, PROT_READ | PROT_WRITE) != 0) { err = errno; ended = true; cv.notify_all(); return; }
+                (void)madvise(base + committed, to - committed, MADV_HUGEPAGE);
+                committed = to;
+            }
+        }
+        // (poll with the wake-up pipe beside: mdx_source_close must not wait for a writer that never writes)
+        struct pollfd pf[2] = {{fd, POLLIN, 0}, {wake[0], POLLIN, 0}};
+        if (poll(pf, 2, -1) < 0) {
+            if (errno == EINTR) continue;
+            std::lock_guard<std::mutex> lk(mu);
+            err = errno; ended = true; cv.notify_all();
+            return;
+        }
+        if (pf[1].revents) return;
+        const ssize_t r = ::read(fd, base + at, room);
+        const int e = errno;
+        std::lock_guard<std::mutex> lk(mu);
+        if (r > 0) seen.store(at + (size_t)r, std::memory_order_release);
+        else if (r < 0 && (e == EINTR || e == EAGAIN)) continue;
+        else { if (r < 0) err = e; ended = true; }
+        cv.notify_all();
+        if (ended) return;
+    }
+}
+
+bool mdx_source::open(const char *path_, std::string &err) {
+    path = path_;
+    const bool std_in = path == "-";
+    fd = std_in ? fcntl(0, F_DUPFD_CLOEXEC, 0) : ::open(path_, O_RDONLY);
+    if (fd < 0) { err = std::string("cannot open ") + path_; return false; }
+    struct stat st;
+    if (fstat(fd, &st) != 0 || S_ISDIR(st.st_mode)) { ::close(fd); fd = -1; err = std::string("not a regular file: ") + path_; return false; }
+    if (S_ISREG(st.st_mode)) {
+        const off_t at = std_in ? lseek(fd, 0, SEEK_CUR) : 0;
+        const size_t whole = (size_t)st.st_size;
+        fd_off = at > 0 ? std::min((size_t)at, whole) : 0;
+        n = whole - fd_off;
         if (n) {
-            void *m = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); fd = -1; n = 0; err = std::string("cannot map ") + path; return false; }
-            (void)madvise(m, n, MADV_SEQUENTIAL);
-            p = (const uint8_t *)m;
+            void *m = mmap(nullptr, whole, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) { ::close(fd); fd = -1; n = 0; err = std::string("cannot map ") + path_; return false; }
+            (void)madvise(m, whole, MADV_SEQUENTIAL);
+            map = m; map_len = whole;
+            p = (const uint8_t *)m + fd_off;
         }
         return true;
     }
-    void close() { if (p) munmap((void *)p, n); p = nullptr; n = 0; if (fd >= 0) ::close(fd); fd = -1; }
-    ~MappedFile() { close(); }
-    size_t size() const { return n; }
-    const uint8_t &operator[](size_t i) const { return p[i]; }
-};
+    // a stream: the reservation as large as the address space allows (absolute offsets: it bounds the stream's length, not
+    // the memory used), the pipe's buffer as large as this process may make it
+    w = new Window();
+    w->fd = fd; fd = -1;
+    for (const int shift : {44, 42, 40, 38, 36}) {
+        const size_t len = ((size_t)1 << shift) + kReleaseStep;
+        void *m = mmap(nullptr, len, PROT_NONE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+        if (m == MAP_FAILED) continue;
+        w->resv = m; w->resv_len = len;
+        w->base = (uint8_t *)(((uintptr_t)m + kReleaseStep - 1) / kReleaseStep * kReleaseStep);
+        w->reserved = (size_t)1 << shift;
+        break;
+    }
+    if (!w->base || pipe(w->wake) != 0) { err = std::string("cannot set up a window for the stream ") + path_; close(); return false; }
+    if (S_ISFIFO(st.st_mode)) {
+        int most = 1 << 20;
+        if (FILE *f = std::fopen("/proc/sys/fs/pipe-max-size", "r")) { if (std::fscanf(f, "%d", &most) != 1) most = 1 << 20; std::fclose(f); }
+        if (fcntl(w->fd, F_GETPIPE_SZ) < most) (void)fcntl(w->fd, F_SETPIPE_SZ, most);
+    }
+    p = w->base;
+    w->reader = std::thread([win = w] { win->run(); });
+    return true;
+}
+
+void mdx_source::close() {
+    if (w) {
+        {
+            std::lock_guard<std::mutex> lk(w->mu);
+            w->stop = true;
+            w->cv.notify_all();
+        }
+        if (w->wake[1] >= 0) { const char c = 1; (void)!::write(w->wake[1], &c, 1); }
+        if (w->reader.joinable()) w->reader.join();
+        if (w->resv) munmap(w->resv, w->resv_len);
+        for (int f : {w->fd, w->wake[0], w->wake[1]}) if (f >= 0) ::close(f);
+        delete w;
+        w = nullptr;
+    }
+    if (map) munmap(map, map_len);
+    map = nullptr; map_len = 0; p = nullptr; n = 0;
+    if (fd >= 0) ::close(fd);
+    fd = -1;
+}
+
+static mdx_source *source_ref(mdx_source *s) { if (s) s->refs.fetch_add(1); return s; }
+
+namespace {
 
 inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 inline uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
@@ -191,30 +361,36 @@ inline int32_t rdi32(const uint8_t *p) { return (int32_t)rd32(p); }
 // `partial`: the buffer may end inside a block (streaming); the scan stops there and `consumed` says how far
 // it got.  Otherwise a truncated block is an error.
 // `from`/`want`: scan from that offset and stop after about `want` compressed bytes (streaming).
-bool scan_blocks(const MappedFile &file, std::vector<Block> &blocks, size_t &total, std::string &err,
+bool scan_blocks(const mdx_source &file, std::vector<Block> &blocks, size_t &total, std::string &err,
                  size_t from = 0, size_t want = ~(size_t)0, size_t *consumed = nullptr) {
     size_t off = from;
     const bool partial = false;      // a mapped file is all there: a block running past its end is corrupt
     total = 0;
     if (consumed) *consumed = from;
-    while (off < file.size() && off - from < want) {
-        if (partial && off + 18 > file.size()) break;
-        if (off + 18 > file.size() || file[off] != 0x1f || file[off + 1] != 0x8b || !(file[off + 3] & 4)) {
+    // (`have`: the bytes there are — a stream's wait for the ones this step reads, until it has ended: the same verdicts as
+    // for the same bytes in a file)
+    while (off - from < want) {
+        size_t have = file.reach(off + 18);
+        if (off >= have) break;
+        if (partial && off + 18 > have) break;
+        if (off + 18 > have || file[off] != 0x1f || file[off + 1] != 0x8b || !(file[off + 3] & 4)) {
             err = "not a BGZF-compressed file";
             return false;
         }
         const size_t xlen = rd16(&file[off + 10]);
         size_t x = off + 12, xend = x + xlen;
-        if (partial && xend > file.size()) break;
+        have = file.reach(xend);
+        if (partial && xend > have) break;
         size_t bsize = 0;
-        while (x + 4 <= xend && xend <= file.size()) {
+        while (x + 4 <= xend && xend <= have) {
             const size_t slen = rd16(&file[x + 2]);
             if (x + 4 + slen > xend) break;                     // (a subfield may not run past the extra field)
             if (file[x] == 'B' && file[x + 1] == 'C' && slen == 2) bsize = (size_t)rd16(&file[x + 4]) + 1;
             x += 4 + slen;
         }
-        if (partial && bsize && bsize >= xlen + 20 && off + bsize > file.size()) break;
-        if (!bsize || off + bsize > file.size() || bsize < xlen + 20) { err = "corrupt BGZF block"; return false; }
+        if (bsize) have = file.reach(off + bsize);
+        if (partial && bsize && bsize >= xlen + 20 && off + bsize > have) break;
+        if (!bsize || off + bsize > have || bsize < xlen + 20) { err = "corrupt BGZF block"; return false; }
         Block b;
         b.in_off = off + 12 + xlen;
         b.in_size = bsize - xlen - 20;
@@ -633,13 +809,14 @@ int unpack_records(mdx_bam *b, const uint8_t *data, size_t off, size_t total, in
 // s->pending.  Returns false on an I/O or format error (text in s->head.error).
 bool stream_fill(mdx_bam_stream *s, size_t want) {
     if (s->eof) return true;
+    if (s->coff < s->file->kept_from()) { s->head.error = s->file->behind(s->coff); return false; }
     std::vector<Block> blocks;
     size_t total = 0, consumed = s->coff;
     if (!scan_blocks(*s->file, blocks, total, s->head.error, s->coff, want, &consumed)) return false;
     const size_t base = s->pending.size();
     s->pending.resize(base + total);
     std::atomic<bool> ok{true};
-    const MappedFile &file = *s->file;
+    const mdx_source &file = *s->file;
     parallel_for(blocks.size(), s->threads, [&](size_t i) {
         const Block &k = blocks[i];
         if (!inflate_block(&file[k.in_off], k.in_size, &s->pending[base + k.out_off], k.out_size, k.crc)) ok = false;
@@ -647,7 +824,7 @@ bool stream_fill(mdx_bam_stream *s, size_t want) {
     if (!ok) { s->head.error = "inflate failed (corrupt BGZF block: DEFLATE stream, ISIZE or CRC32)"; return false; }
     for (const Block &k : blocks) s->hints.push_back(base + k.out_off);
     s->coff = consumed;
-    if (s->coff >= file.size()) s->eof = true;
+    if (file.at_end(s->coff)) s->eof = true;
     return true;
 }
 
@@ -655,47 +832,128 @@ bool stream_fill(mdx_bam_stream *s, size_t want) {
 
 extern "C" {
 
+}  // extern "C"
+
+// The one-piece decode of mdx_bam_read / mdx_bam_read_source: `owned` — the source is this call's, and is let go as soon as
+// its blocks are inflated (a stream's bytes, which are all held until then: it is read to its end).
+static int bam_read(mdx_source *file, bool owned, int threads, mdx_bam *b) {
+    // MDX_BAM_TIMING=1: stage times on stderr
+    const bool timing = std::getenv("MDX_BAM_TIMING") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what) {
+        if (!timing) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "mdx_bam_read %-12s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+        t_last = now;
+    };
+    struct Let { mdx_source *&f; bool owned; ~Let() { if (owned && f) mdx_source_close(f); } } let{file, owned};
+    lap("file map");
+    if (file->kept_from() > 0) { b->error = file->behind(0); return MDX_ERR_ARG; }
+    std::vector<Block> blocks;
+    size_t total = 0;
+    if (!scan_blocks(*file, blocks, total, b->error)) return MDX_ERR_ARG;
+    lap("block scan");
+    raw_bytes data(total + 8);
+    std::atomic<bool> ok{true};
+    const mdx_source &src = *file;
+    parallel_for(blocks.size(), threads, [&](size_t i) {
+        const Block &k = blocks[i];
+        if (!inflate_block(&src[k.in_off], k.in_size, &data[k.out_off], k.out_size, k.crc)) ok = false;
+    });
+    if (!ok) { b->error = "inflate failed (corrupt BGZF block: DEFLATE stream, ISIZE or CRC32)"; return MDX_ERR_ARG; }
+    lap("inflate");
+    if (owned) { mdx_source_close(file); file = nullptr; }
+    else file->release(file->size());
+
+    size_t off = 0, used = 0;
+    if (parse_header(b, data.data(), total, false, &off) != 0) return MDX_ERR_ARG;
+    std::vector<size_t> hints(blocks.size());
+    for (size_t i = 0; i < blocks.size(); i++) hints[i] = blocks[i].out_off;
+    const int rc = unpack_records(b, data.data(), off, total, threads, false, &used, lap, &hints);
+    b->reaper = std::thread([](raw_bytes d) { raw_bytes().swap(d); }, std::move(data));
+    lap("release");
+    return rc;
+}
+
+extern "C" {
+
+int mdx_source_open(const char *path, mdx_source **out) {
+    try {
+        if (!path || !out) return MDX_ERR_ARG;
+        mdx_source *s = new (std::nothrow) mdx_source();
+        *out = s;
+        if (!s) return MDX_ERR_ARG;
+        return s->open(path, s->error) ? MDX_OK : MDX_ERR_ARG;
+    } catch (const std::exception &e) {
+        if (out && *out) (*out)->error = std::string("mdx_source_open: ") + e.what();
+        return MDX_ERR_ARG;
+    } catch (...) {
+        return MDX_ERR_ARG;
+    }
+}
+
+const char *mdx_source_error(const mdx_source *s) {
+    if (!s) return "null handle";
+    if (s->w && s->error.empty()) {
+        std::lock_guard<std::mutex> lk(s->w->mu);
+        if (s->w->err) return std::strerror(s->w->err);
+    }
+    return s->error.c_str();
+}
+
+int mdx_source_is_stream(const mdx_source *s) { return (s && s->is_stream()) ? 1 : 0; }
+
+int mdx_source_peek(mdx_source *s, uint8_t *buf, int32_t n, int32_t *got) {
+    if (!s || n < 0 || (n > 0 && !buf) || !got) return MDX_ERR_ARG;
+    *got = 0;
+    if (s->kept_from() > 0) { s->error = s->behind(0); return MDX_ERR_ARG; }
+    const size_t have = std::min((size_t)n, s->reach((size_t)n));
+    if (have) std::memcpy(buf, s->p, have);
+    *got = (int32_t)have;
+    return MDX_OK;
+}
+
+int64_t mdx_source_read(mdx_source *s, uint8_t *buf, int64_t cap) {
+    if (!s || cap < 0 || (cap > 0 && !buf)) return -1;
+    if (s->rpos < s->kept_from()) { s->error = s->behind(s->rpos); return -1; }
+    const size_t have = s->reach(s->rpos + 1);
+    if (have <= s->rpos) return 0;
+    const size_t k = std::min((size_t)cap, have - s->rpos);
+    std::memcpy(buf, s->p + s->rpos, k);
+    s->rpos += k;
+    s->release(s->rpos);
+    return (int64_t)k;
+}
+
+void mdx_source_close(mdx_source *s) {
+    if (s && s->refs.fetch_sub(1) == 1) delete s;
+}
+
+int mdx_bam_read_source(mdx_source *source, int threads, mdx_bam **out) {
+    try {
+        if (!source || !out) return MDX_ERR_ARG;
+        mdx_bam *b = new (std::nothrow) mdx_bam();
+        if (!b) return MDX_ERR_ARG;
+        *out = b;
+        return bam_read(source, false, threads, b);
+    } catch (const std::exception &e) {
+        if (out && *out) (*out)->error = std::string("mdx_bam_read: ") + e.what();
+        return MDX_ERR_ARG;
+    } catch (...) {
+        if (out && *out) (*out)->error = "mdx_bam_read: unknown failure";
+        return MDX_ERR_ARG;
+    }
+}
+
 int mdx_bam_read(const char *path, int threads, mdx_bam **out) {
     try {
         if (!path || !out) return MDX_ERR_ARG;
         mdx_bam *b = new (std::nothrow) mdx_bam();
         if (!b) return MDX_ERR_ARG;
         *out = b;
-        // MDX_BAM_TIMING=1: stage times on stderr
-        const bool timing = std::getenv("MDX_BAM_TIMING") != nullptr;
-        auto t_last = std::chrono::steady_clock::now();
-        auto lap = [&](const char *what) {
-            if (!timing) return;
-            const auto now = std::chrono::steady_clock::now();
-            std::fprintf(stderr, "mdx_bam_read %-12s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-            t_last = now;
-        };
-        MappedFile file;
-        if (!file.open(path, b->error)) return MDX_ERR_ARG;
-        lap("file map");
-        std::vector<Block> blocks;
-        size_t total = 0;
-        if (!scan_blocks(file, blocks, total, b->error)) return MDX_ERR_ARG;
-        lap("block scan");
-        raw_bytes data(total + 8);
-        std::atomic<bool> ok{true};
-        parallel_for(blocks.size(), threads, [&](size_t i) {
-            const Block &k = blocks[i];
-            if (!inflate_block(&file[k.in_off], k.in_size, &data[k.out_off], k.out_size, k.crc)) ok = false;
-        });
-        if (!ok) { b->error = "inflate failed (corrupt BGZF block: DEFLATE stream, ISIZE or CRC32)"; return MDX_ERR_ARG; }
-        lap("inflate");
-        file.close();
-    
-        size_t off = 0, used = 0;
-        if (parse_header(b, data.data(), total, false, &off) != 0) return MDX_ERR_ARG;
-        std::vector<size_t> hints(blocks.size());
-        for (size_t i = 0; i < blocks.size(); i++) hints[i] = blocks[i].out_off;
-        const int rc = unpack_records(b, data.data(), off, total, threads, false, &used, lap, &hints);
-        b->reaper = std::thread([](raw_bytes d) { raw_bytes().swap(d); }, std::move(data));
-        lap("release");
-        return rc;
-    
+        mdx_source *file = new mdx_source();
+        if (!file->open(path, b->error)) { mdx_source_close(file); return MDX_ERR_ARG; }
+        return bam_read(file, true, threads, b);
     } catch (const std::exception &e) {
         if (out && *out) (*out)->error = std::string("mdx_bam_read: ") + e.what();
         return MDX_ERR_ARG;
@@ -758,16 +1016,15 @@ const char *mdx_bam_qnames(const mdx_bam *b, const uint32_t **offsets) {
     return b->qnames.data();
 }
 
-int mdx_bam_open(const char *path, int threads, mdx_bam_stream **out) {
+int mdx_bam_open_source(mdx_source *source, int threads, mdx_bam_stream **out) {
     try {
-        if (!path || !out) return MDX_ERR_ARG;
+        if (!source || !out) return MDX_ERR_ARG;
         mdx_bam_stream *s = new (std::nothrow) mdx_bam_stream();
         if (!s) return MDX_ERR_ARG;
         *out = s;
         s->threads = threads < 1 ? 1 : threads;
-        s->file = new (std::nothrow) MappedFile();
-        if (!s->file || !s->file->open(path, s->head.error)) return MDX_ERR_ARG;
-        if (s->file->size() == 0) s->eof = true;
+        s->file = source_ref(source);
+        if (s->file->at_end(0)) s->eof = true;
         // the header may span several blocks: inflate until it parses (one block's worth first — the header of most files
         // — then a megabyte at a time: the device decode path opens the file for its header alone, and a megabyte of blocks
         // inflated for nothing was 2 of its 2.5 ms)
@@ -794,6 +1051,31 @@ int mdx_bam_open(const char *path, int threads, mdx_bam_stream **out) {
     }
 }
 
+int mdx_bam_open(const char *path, int threads, mdx_bam_stream **out) {
+    try {
+        if (!path || !out) return MDX_ERR_ARG;
+        *out = nullptr;
+        mdx_source *file = new mdx_source();
+        std::string err;
+        if (!file->open(path, err)) {
+            mdx_source_close(file);
+            mdx_bam_stream *s = new (std::nothrow) mdx_bam_stream();
+            if (!s) return MDX_ERR_ARG;
+            *out = s;
+            s->head.error = err;
+            return MDX_ERR_ARG;
+        }
+        const int rc = mdx_bam_open_source(file, threads, out);
+        mdx_source_close(file);              // (the stream holds it)
+        return rc;
+    } catch (const std::exception &e) {
+        if (out && *out) (*out)->head.error = std::string("mdx_bam_open: ") + e.what();
+        return MDX_ERR_ARG;
+    } catch (...) {
+        return MDX_ERR_ARG;
+    }
+}
+
 const mdx_bam *mdx_bam_stream_header(const mdx_bam_stream *s) { return s ? &s->head : nullptr; }
 
 int mdx_bam_next(mdx_bam_stream *s, int64_t chunk_bytes, mdx_bam **out) {
@@ -810,6 +1092,8 @@ int mdx_bam_next(mdx_bam_stream *s, int64_t chunk_bytes, mdx_bam **out) {
             t_last = now;
         };
         for (;;) {
+            // (what is in front of the blocks inflated so far is this stream's no longer: a stream's window moves on)
+            s->file->release(s->coff);
             // BGZF members hold at most 64 KiB each; BAM compresses about 3-4x
             while (!s->eof && s->pending.size() < limit + s->skip)
                 if (!stream_fill(s, std::max<size_t>(limit / 4, (size_t)1 << 16))) return MDX_ERR_ARG;
@@ -864,11 +1148,13 @@ int mdx_bam_next(mdx_bam_stream *s, int64_t chunk_bytes, mdx_bam **out) {
 
 int mdx_bam_seek(mdx_bam_stream *s, int64_t comp_off, int64_t phase) {
     try {
-        if (!s || !s->file || comp_off < 0 || phase < 0 || (size_t)comp_off > s->file->size()) return MDX_ERR_ARG;
+        if (!s || !s->file || comp_off < 0 || phase < 0) return MDX_ERR_ARG;
+        if ((size_t)comp_off < s->file->kept_from()) { s->head.error = "mdx_bam_seek: " + s->file->behind((size_t)comp_off); return MDX_ERR_ARG; }
+        if ((size_t)comp_off > s->file->reach((size_t)comp_off)) return MDX_ERR_ARG;
         s->pending.clear();
         s->hints.clear();
         s->coff = (size_t)comp_off;
-        s->eof = s->coff >= s->file->size();
+        s->eof = s->file->at_end(s->coff);
         s->skip = (size_t)phase;
         return MDX_OK;
     } catch (...) {
@@ -944,7 +1230,7 @@ int mdx_mr_round(const double *mr_raw, int64_t n, float *out, int32_t threads) {
 
 void mdx_bam_close(mdx_bam_stream *s) {
     if (!s) return;
-    delete s->file;
+    mdx_source_close(s->file);
     delete s;
 }
 
@@ -1096,8 +1382,8 @@ struct mdx_gbam {
     size_t scanned = 0, scanned_out = 0; // compressed offset behind the last block found, inflated bytes in front of it
     // blocks up to compressed offset `upto` (or the end of the file); false: a corrupt block header
     bool scan_to(size_t upto) {
-        const MappedFile &f = *hs->file;
-        while (scanned < f.size() && scanned < upto) {
+        const mdx_source &f = *hs->file;
+        while (scanned < upto && !f.at_end(scanned)) {
             std::vector<Block> more;
             size_t total = 0, consumed = scanned;
             if (!scan_blocks(f, more, total, error, scanned, std::max<size_t>(upto - scanned, (size_t)1 << 20), &consumed)) return false;
@@ -1107,7 +1393,7 @@ struct mdx_gbam {
         }
         return true;
     }
-    bool whole_file_scanned() const { return scanned >= hs->file->size(); }
+    bool whole_file_scanned() const { return hs->file->at_end(scanned); }
     size_t next_block = 0;               // first block not decoded yet
     // Records may straddle BGZF blocks and slabs: a slab's batch holds the records that START in it (the blocks behind it
     // are inflated as far as its last record reaches), and `phase` is where the first record of the next slab starts,
@@ -1206,9 +1492,9 @@ struct mdx_gbam {
     }
 };
 
-int mdx_gbam_open(mdx_ctx *ctx, const char *path, mdx_gbam **out) {
+int mdx_gbam_open_source(mdx_ctx *ctx, mdx_source *source, mdx_gbam **out) {
     try {
-        if (!ctx || !path || !out) return MDX_ERR_ARG;
+        if (!ctx || !source || !out) return MDX_ERR_ARG;
         mdx_gbam *g = new (std::nothrow) mdx_gbam();
         if (!g) return MDX_ERR_ARG;
         *out = g;
@@ -1216,7 +1502,7 @@ int mdx_gbam_open(mdx_ctx *ctx, const char *path, mdx_gbam **out) {
         void *st = nullptr;
         if (mdx_ctx_stream(ctx, &st, &g->device) != MDX_OK) { g->error = "no context"; return MDX_ERR_ARG; }
         g->stream = (hipStream_t)st;
-        int rc = mdx_bam_open(path, 4, &g->hs);
+        int rc = mdx_bam_open_source(source, 4, &g->hs);
         if (rc != MDX_OK) { g->error = g->hs ? g->hs->head.error : "cannot open"; return rc; }
         // the first slab starts with the block that holds the first record (htslib flushes the header into blocks of its
         // own; other writers let it share a block with records): `phase` bytes into it
@@ -1254,6 +1540,35 @@ int mdx_gbam_open(mdx_ctx *ctx, const char *path, mdx_gbam **out) {
                 if (hipEventCreate(&s.ev_infl0) != hipSuccess || hipEventCreate(&s.ev_infl) != hipSuccess) { g->error = "HIP set-up failed"; return MDX_ERR_HIP; }
         }
         return MDX_OK;
+    } catch (const std::exception &e) {
+        if (out && *out) (*out)->error = std::string("mdx_gbam_open: ") + e.what();
+        return MDX_ERR_ARG;
+    } catch (...) {
+        return MDX_ERR_ARG;
+    }
+}
+
+int mdx_gbam_open(mdx_ctx *ctx, const char *path, mdx_gbam **out) {
+    try {
+        if (!ctx || !path || !out) return MDX_ERR_ARG;
+        *out = nullptr;
+        mdx_source *file = new mdx_source();
+        std::string err;
+        if (!file->open(path, err)) {
+            mdx_source_close(file);
+            mdx_gbam *g = new (std::nothrow) mdx_gbam();
+            if (!g) return MDX_ERR_ARG;
+            *out = g;
+            g->ctx = ctx;
+            void *st = nullptr;
+            (void)mdx_ctx_stream(ctx, &st, &g->device);
+            g->stream = (hipStream_t)st;
+            g->error = err;
+            return MDX_ERR_ARG;
+        }
+        const int rc = mdx_gbam_open_source(ctx, file, out);
+        mdx_source_close(file);              // (the handle holds it)
+        return rc;
     } catch (const std::exception &e) {
         if (out && *out) (*out)->error = std::string("mdx_gbam_open: ") + e.what();
         return MDX_ERR_ARG;
@@ -1307,6 +1622,7 @@ int mdx_gbam_configure(mdx_gbam *g, int32_t n_rg, const char *const *rg_ids, con
 // step over each other's slabs (mdx_gbam_skip), agree on the borders.
 static size_t slab_want(const mdx_gbam *g, size_t b0, int64_t chunk_bytes) {
     size_t want = chunk_bytes < 65536 ? 65536 : (size_t)chunk_bytes;
+    if (g->hs->file->is_stream()) return want;          // (a stream's size is not known: chunk_bytes as asked)
     const size_t fsz = g->hs->file->size();
     const size_t in0 = b0 < g->blocks.size() ? (size_t)g->blocks[b0].in_off : g->scanned;
     if (fsz > in0) {
@@ -1543,7 +1859,7 @@ static int gbam_half_a(mdx_gbam *g, mdx_gbam::Slab &s, size_t b0, int64_t chunk_
         for (size_t j = 0; j < np; j++) done[j] = 0;
         std::atomic<int> bad_block{-1};
         std::vector<int32_t> host_status(nt);
-        const MappedFile &file = *g->hs->file;
+        const mdx_source &file = *g->hs->file;
         // (a copy: the walk over the next slab's headers, below, appends to g->blocks while the pool reads these)
         const std::vector<Block> host_blocks(g->blocks.begin() + (long)(b0 + nh), g->blocks.begin() + (long)(b0 + nba));
         const Block *const bl = host_blocks.data();
@@ -1556,14 +1872,15 @@ static int gbam_half_a(mdx_gbam *g, mdx_gbam::Slab &s, size_t b0, int64_t chunk_
             const size_t off = (size_t)(k.out_off - out0) - tail0;
             // (the block's compressed bytes through pread() into a buffer of the thread's own: a hundred threads faulting
             // pages of the file's mapping in — under the address space's lock, next to whatever else maps and unmaps —
-            // stalled for tens of milliseconds now and then)
+            // stalled for tens of milliseconds now and then; a stream's window is anonymous memory its reader has written
+            // already: read in place)
             thread_local std::vector<uint8_t> mine;
             const uint8_t *src = &file[k.in_off];
             if (file.fd >= 0 && k.in_size) {
                 if (mine.size() < k.in_size) mine.resize(std::max<size_t>(k.in_size, 80 << 10));
                 size_t got = 0;
                 while (got < k.in_size) {
-                    const ssize_t r = pread(file.fd, mine.data() + got, k.in_size - got, (off_t)(k.in_off + got));
+                    const ssize_t r = pread(file.fd, mine.data() + got, k.in_size - got, (off_t)(file.fd_off + k.in_off + got));
                     if (r <= 0) break;
                     got += (size_t)r;
                 }
@@ -1866,6 +2183,15 @@ int mdx_gbam_next(mdx_gbam *g, int64_t chunk_bytes, mdx_batch *view, const int32
         }
         g->view_slab = g->cur;
         g->cur ^= 1;
+        // a stream: nothing in front of the next slab's first block is needed any more — by this handle, or by a host decoder
+        // that takes the stream up where it gave up (mdx_gbam_tell) — once the device has read the slab's bytes (its inflate
+        // has run: the uploads in front of it on the same stream have)
+        mdx_source *src = g->hs->file;
+        int64_t keep = 0, ph = 0;
+        if (src->is_stream() && mdx_gbam_tell(g, &keep, &ph) == MDX_OK) {
+            if (hipEventSynchronize(g->slab[g->view_slab].ev_infl) != hipSuccess) return MDX_ERR_HIP;
+            src->release((size_t)keep);
+        }
         tr.mark("end");
         return MDX_OK;
     } catch (const std::exception &e) {

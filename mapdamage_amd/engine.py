@@ -40,6 +40,8 @@ EXPORTS = (
     "mdx_rescale_patches_device", "mdx_tabulate_rescale_patches_device", "mdx_rescale_expand_device", "mdx_mr_round", "mdx_batch_fold", "mdx_bgzf_deflate",
     "mdx_gbam_rescale_slab", "mdx_gbam_write_rescaled", "mdx_gbam_record_name",
     "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
+    "mdx_source_open", "mdx_source_error", "mdx_source_is_stream", "mdx_source_peek", "mdx_source_read", "mdx_source_close",
+    "mdx_bam_read_source", "mdx_bam_open_source", "mdx_gbam_open_source",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -158,6 +160,18 @@ def load_library(path=None):
                                             ctypes.c_void_p]
     lib.mdx_reference_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     lib.mdx_warm.argtypes = [ctypes.c_int32, ctypes.c_int64]
+    lib.mdx_source_open.argtypes = [ctypes.c_char_p, ctypes.c_void_p]
+    lib.mdx_source_error.restype = ctypes.c_char_p
+    lib.mdx_source_error.argtypes = [ctypes.c_void_p]
+    lib.mdx_source_is_stream.argtypes = [ctypes.c_void_p]
+    lib.mdx_source_peek.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    lib.mdx_source_read.restype = ctypes.c_int64
+    lib.mdx_source_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+    lib.mdx_source_close.restype = None
+    lib.mdx_source_close.argtypes = [ctypes.c_void_p]
+    lib.mdx_bam_read_source.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.mdx_bam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    lib.mdx_gbam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib

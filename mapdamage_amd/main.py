@@ -18,7 +18,7 @@ from .batch import mark_unmaskable
 from .engine import BadReadError, DamageEngine, MdxError
 from .fasta import compare_sequence_dicts, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
-from .reader import BAMReader, draw_uniform
+from .reader import BAMReader, draw_uniform, is_stream
 from .sam import BAMError
 from .statistics import check_table_and_warn_if_dmg_freq_is_low
 
@@ -148,6 +148,14 @@ def parse_args(argv):
         parser.error("--folder required when using --rescale-only")
     if not o.filename:
         parser.error("--input SAM/BAM file not specified")
+    if is_stream(o.filename):
+        # (a stream is read once, by one process, front to back)
+        if o.gpus > 1:
+            parser.error("--gpus %d cannot read its input from stdin or a pipe: every rank opens the input itself; "
+                         "write it to a file, or use --gpus 1" % o.gpus)
+        if o.rescale_only:
+            parser.error("--rescale-only cannot read its input from stdin or a pipe (it reads the file more than once); "
+                         "write it to a file")
     if not o.ref:
         parser.error("--reference FASTA file not specified")
     if o.downsample is not None:
@@ -297,22 +305,23 @@ def launch_command(argv, gpus):
 
 def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None):
     """The records decoded on the host (native BGZF/BAM decoder or SAM text), uploaded batch by batch.
-    ``carry``: (engine, resume position, records counted so far) of a device decode that gave up part of the way: the
-    same engine — its tables hold the slabs already counted — goes on with the rest of the file."""
+    ``carry``: (engine, resume position, records counted so far, --downsample generator or None) of a device decode that
+    gave up part of the way: the same engine — its tables hold the slabs already counted — goes on with the rest of the
+    file (a stream's draws with the run's one generator, where the device path left it)."""
     import contextlib
     with contextlib.ExitStack() as stack:
         if carry is None:
             engine = stack.enter_context(DamageEngine(libraries, options.length, options.around, options.minqual,
                                                       device=ranks.device))
             engine.set_reference(ref)
-            n_reads, resume = 0, None
+            n_reads, resume, rand = 0, None, None
         else:
-            engine, resume, n_reads = carry
+            engine, resume, n_reads, rand = carry
             stack.enter_context(engine)
         warned_about_quals = False
         error = None
         # a BAM file arrives in chunks (bounded host memory; chunk k+1 is decoded while chunk k is tabulated)
-        for batch in reader.iter_batches(resume=resume):
+        for batch in reader.iter_batches(resume=resume, rand=rand):
             if options.minqual and not warned_about_quals and batch.n:
                 # main.py:185-192: the first iterated read without qualities (`not read.qual`: absent or
                 # empty) triggers the warning, once
@@ -355,7 +364,11 @@ def _device_path_applies(options, world=1):
     flags, and the stream of draws is the whole file's); a fixed number of reads is reservoir sampling over the whole file
     (reader.py:148-164): the host's."""
     from .sam import is_bam
-    return str(options.filename) != "-" and is_bam(options.filename) and (
+    # (stdin and pipes as files: through the run's one Source, options.source — a stream is never opened twice)
+    source = getattr(options, "source", None)
+    if source is None and is_stream(options.filename):
+        return False
+    return is_bam(source if source is not None else options.filename) and (
         options.downsample is None or (options.downsample < 1 and world == 1))
 
 
@@ -377,6 +390,9 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     reference does: the whole file (carry None), or, when the device path failed on a slab it had not begun to count,
     the rest of it with the same engine (``_tabulate_on_host``'s ``carry``)."""
     from .sam import GpuBamStream, GpuDecodeUnsupported
+    # a stream (stdin, a pipe) is read once: a host decoder that takes over goes on where the device path stopped, never
+    # from the start
+    streaming = reader.source is not None and reader.source.is_stream
     if not _device_path_applies(options, ranks.world):
         logger.debug("the GPU decode path does not apply to this run; decoding on the host")
         return None, None
@@ -400,8 +416,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         if warm is not None:
             warm.join()         # (the pinned buffer it leaves behind is the one the first slab takes)
         stages.mark("warm-up joined")
-        with GpuBamStream(engine, options.filename, readgroups=readgroups, lib_default=lib_default,
-                          chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual) as stream:
+        with GpuBamStream(engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
+                          lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual) as stream:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
             slab, n_reads = 0, 0
             try:
@@ -423,8 +439,11 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                             # (resuming needs the chunked host decoder, reader.iter_batches(resume=...): with --chunk-mb 0
                             # the host path reads the file in one piece, so the whole file is counted again)
                             # (... and --downsample: the host decoder starts its stream of draws at the file's first record)
-                            if where is not None and slab > 1 and reader._chunks is not None and options.downsample is None:
-                                carry = (engine, where, n_reads)
+                            # (a stream cannot be read again: the host decoder takes it up at that slab, the first one too,
+                            # and the draws go on with the run's one generator)
+                            if where is not None and reader._chunks is not None and (
+                                    streaming or (slab > 1 and options.downsample is None)):
+                                carry = (engine, where, n_reads, downsample_rand if options.downsample is not None else None)
                         raise
                     if view is None:
                         break
@@ -461,7 +480,11 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     except GpuDecodeUnsupported as error:
         reason = "file layout the device path does not take (MDX_ERR_UNSUPPORTED): %s" % error
     except BadReadError as error:
-        # a record the reference cannot process, or one without a usable read group: the host path names it
+        # a record the reference cannot process, or one without a usable read group: the host path names it — but a stream,
+        # which the host decoder cannot read again up to that record: the device path's error stands
+        if streaming:
+            engine.close()
+            raise
         reason = "a record the device path cannot count (MDX_ERR_BAD_READ, record %d)" % error.read_index
         carry = None
     except (ValueError, MdxError) as error:
@@ -515,12 +538,20 @@ def main(argv):
         return subprocess.call(cmd, env=env)
     ranks = _Ranks(options)
     first = ranks.rank == 0
+    # stdin, a named pipe, /dev/fd/N: opened once, here — the format sniff, the header, the device decode and a host decoder
+    # that takes over all read the one Source
+    options.source = None
+    if is_stream(options.filename):
+        from .sam import Source
+        options.source = Source(options.filename)
     if options.gpu_decode and not options.rescale_only and _device_path_applies(options, ranks.world) and not os.environ.get("MDX_NO_WARM"):
         # the device's context, the decode kernels and the pinned buffer of the host's share (about a fifth of a slab's
         # inflated bytes, which are four to five times its compressed ones), beside the header, index and FASTA reads
         import threading
         try:
-            pinned = min(_slab_bytes(options, ranks.world), os.path.getsize(options.filename))
+            pinned = _slab_bytes(options, ranks.world)
+            if options.source is None or not options.source.is_stream:       # (a pipe has no size)
+                pinned = min(pinned, os.path.getsize(options.filename))
         except OSError:
             pinned = 0
         options.warm_thread = threading.Thread(target=_warm_up, args=(ranks.device, pinned), daemon=True)
@@ -531,6 +562,7 @@ def main(argv):
     handler.setFormatter(logging.Formatter(_LOG_FORMAT))
     handler.setLevel(options.log_level)
     logging.getLogger().addHandler(handler)
+    reader = None
     try:
         logger.info("Started with the command: " + " ".join(sys.argv))
         if options.rescale_only:
@@ -546,7 +578,7 @@ def main(argv):
                      load_library().mdx_host_threads(), usable_cpus(), os.environ.get("LOCAL_WORLD_SIZE", "1"))
         reader = BAMReader(options.filename, merge_libraries=options.merge_libraries,
                            downsample_to=options.downsample, downsample_seed=options.downsample_seed,
-                           chunk_bytes=int(options.chunk_mb * (1 << 20)))
+                           chunk_bytes=int(options.chunk_mb * (1 << 20)), source=options.source)
         reflengths = reader.get_references()
         fai_lengths = read_fasta_index(str(options.ref) + ".fai")
         if not fai_lengths:
@@ -558,6 +590,13 @@ def main(argv):
         stages.mark("headers and index")
 
         logger.info("Reading from '%s'", options.filename)
+        if options.source is None:
+            logger.debug("Input: a regular file (mapped)")
+        elif options.source.is_stream:
+            logger.info("Input: %s from a stream (stdin, a pipe or a character device), read once as it comes in",
+                        "BAM" if reader.is_bam else "SAM text")
+        else:
+            logger.info("Input: stdin redirected from a regular file (mapped)")
         if options.minqual != 0:
             logger.info("Filtering out bases with a Phred score < %d", options.minqual)
         logger.info("Writing results to '%s/'", options.folder)
@@ -592,6 +631,10 @@ def main(argv):
         logger.error("%s", error)
         raise
     finally:
+        if reader is not None:
+            reader.close()
+        elif options.source is not None:
+            options.source.close()
         logging.getLogger().removeHandler(handler)
         handler.close()
         ranks.close()

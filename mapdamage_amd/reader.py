@@ -9,7 +9,12 @@ import numpy as np
 
 from . import layout as L
 from .batch import ReadBatch
-from .sam import Alignments, BamStream, BAMError, is_bam, read_alignments
+from .sam import Alignments, BamStream, BAMError, Source, input_is_stream, is_bam, read_alignments
+
+
+def is_stream(path):
+    """``-``, a FIFO or a character device: the input is read once, as a stream (mapdamage/reader.py:32-38)."""
+    return input_is_stream(path)
 
 
 def draw_uniform(rand, n):
@@ -50,26 +55,35 @@ def downsample_indices(flag, tid, pos, downsample_to, rand):
 
 class BAMReader:
     def __init__(self, filepath, merge_libraries=False, downsample_to=None, downsample_seed=None,
-                 chunk_bytes=None):
+                 chunk_bytes=None, source=None):
         """``chunk_bytes``: decode a BAM file in chunks of that many uncompressed bytes (``iter_batches``
         then yields one batch per chunk and ``handle`` holds the header only) instead of all at once.
         Downsampling to a fixed number of reads needs the whole file (reservoir + coordinate sort,
-        reader.py:148-164) and SAM text is small-file territory: both keep the one-piece decode."""
+        reader.py:148-164) and SAM text is small-file territory: both keep the one-piece decode.
+        A stream (``is_stream``: stdin, a pipe) is opened once, as ``source`` (a ``sam.Source``: the caller's, or one of
+        the reader's own), which the device decode and a host decoder that takes up after it share; its BAM is decoded in
+        chunks whatever ``chunk_bytes`` says (256 MiB when it says nothing), so that the header read does not read the
+        whole stream — but for -n N, which needs all of it."""
         log = logging.getLogger(__name__)
         self.filepath = filepath
         self.downsample_to = downsample_to
         self.downsample_seed = downsample_seed
-        self.is_stream = str(filepath) == "-"
+        self.is_stream = is_stream(filepath)
+        self.source = source if source is not None else (Source(filepath) if self.is_stream else None)
+        src = self.source if self.source is not None else filepath
         self._chunks = None
-        if chunk_bytes and is_bam(filepath) and (downsample_to is None or downsample_to < 1):
-            self._chunks = BamStream(filepath, chunk_bytes=chunk_bytes)
+        if self.is_stream and not chunk_bytes:
+            chunk_bytes = 256 << 20
+        self.is_bam = is_bam(src)
+        if chunk_bytes and self.is_bam and (downsample_to is None or downsample_to < 1):
+            self._chunks = BamStream(src, chunk_bytes=chunk_bytes)
             empty = ReadBatch(np.zeros(0, np.uint16), np.zeros(0, np.uint16), np.zeros(0, np.int32),
                               np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(1, np.uint32),
                               np.zeros(0, np.uint32), np.zeros(1, np.uint32), np.zeros(0, np.uint8),
                               np.zeros(0, np.uint8))
             self.handle = Alignments(self._chunks.header, empty, [], [])
         else:
-            self.handle: Alignments = read_alignments(filepath)
+            self.handle: Alignments = read_alignments(src)
         self._merge_libraries = merge_libraries
         # read group id -> (sample, library); with --merge-libraries every record, tagged or not, is ("*", "*")
         self._readgroups = {None: ("*", "*")} if merge_libraries else self._collect_readgroups(log, self.handle)
@@ -98,12 +112,20 @@ class BAMReader:
             readgroups[line["ID"]] = (line["SM"], line["LB"])
         return readgroups
 
-    def iter_batches(self, resume=None):
+    def close(self):
+        """Lets go of the input: a stream's writer sees the pipe closed (the run has read what it will)."""
+        if self._chunks is not None:
+            self._chunks.close()
+        if self.source is not None:
+            self.source.close()
+
+    def iter_batches(self, resume=None, rand=None):
         """The records the reference would iterate over (reader.py:83-96, 121-164), in its order, as
         ``ReadBatch``es with the library column filled in: one per decoded chunk, or the whole file
         at once.  The decode of chunk k+1 runs on a helper thread while the caller works on chunk k.
         ``resume``: (compressed offset of a BGZF block, inflated bytes in front of the first record wanted) — the records
-        from there on only (chunked BAM decode: ``BamStream.seek``)."""
+        from there on only (chunked BAM decode: ``BamStream.seek``); ``rand``: the generator whose stream of --downsample
+        draws they carry on (a run that took a stream up from the device decode: its draws go on unbroken)."""
         if resume is not None:
             if self._chunks is None:
                 raise ValueError("resuming needs the chunked BAM decoder")
@@ -117,7 +139,8 @@ class BAMReader:
             yield batch
             return
         from concurrent.futures import ThreadPoolExecutor
-        rand = random.Random(self.downsample_seed)
+        if rand is None:
+            rand = random.Random(self.downsample_seed)
         with ThreadPoolExecutor(1) as pool:
             pending = pool.submit(self._chunks.next_chunk)
             while True:

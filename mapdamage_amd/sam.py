@@ -424,8 +424,12 @@ def read_bam_native(path, threads=None):
     from .engine import MdxBatch, load_library
     lib = load_library()
     handle = ctypes.c_void_p()
-    rc = lib.mdx_bam_read(str(path).encode(), ctypes.c_int(threads or min(64, usable_cpus())),
-                          ctypes.byref(handle))
+    if isinstance(path, Source):
+        # (a stream is read to its end: memory in proportion to it — what reservoir sampling, -n N, needs anyway)
+        rc = lib.mdx_bam_read_source(path.handle, ctypes.c_int(threads or min(64, usable_cpus())), ctypes.byref(handle))
+    else:
+        rc = lib.mdx_bam_read(str(path).encode(), ctypes.c_int(threads or min(64, usable_cpus())),
+                              ctypes.byref(handle))
     owner = _NativeBam(lib, handle)
     if rc != 0:
         raise ValueError("%r: %s" % (str(path), lib.mdx_bam_error(handle).decode() if handle else "BAM decode failed"))
@@ -440,7 +444,7 @@ class GpuBamStream:
     (None: such a record is an error when it is counted).  Any BGZF layout: records may straddle blocks and slabs, the
     header may share a block with records.  Raises ``GpuDecodeUnsupported`` for what is left (a record longer than a
     gigabyte; in a sharded run a slab whose first record cannot be told without the slab in front) — the caller then
-    decodes on the host (``BamStream``), from ``tell()`` on if it likes."""
+    decodes on the host (``BamStream``), from ``tell()`` on if it likes.  ``path``: a file's, or a ``Source``."""
 
     def __init__(self, engine, path, readgroups=(), lib_default=None, chunk_bytes=256 << 20, want_qual=False,
                  want_mate=False, min_basequal=0, packed=None):
@@ -451,7 +455,10 @@ class GpuBamStream:
         self.path, self.chunk_bytes = path, int(chunk_bytes)
         if not engine._ctx:
             raise ValueError("the engine is closed")
-        rc = self._lib.mdx_gbam_open(engine._ctx, str(path).encode(), ctypes.byref(self._g))
+        if isinstance(path, Source):
+            rc = self._lib.mdx_gbam_open_source(engine._ctx, path.handle, ctypes.byref(self._g))
+        else:
+            rc = self._lib.mdx_gbam_open(engine._ctx, str(path).encode(), ctypes.byref(self._g))
         # (the engine closes the streams still open on it before it destroys its context: DamageEngine.close)
         if not hasattr(engine, "_streams"):
             import weakref
@@ -617,7 +624,8 @@ class GpuDecodeUnsupported(ValueError):
 class BamStream:
     """Chunked form of ``read_bam_native`` (include/mdx.h ``mdx_bam_open`` / ``mdx_bam_next``): iterating yields
     ``Alignments`` of consecutive records, at most ``chunk_bytes`` of uncompressed BAM data each, so host memory stays
-    bounded and the caller can tabulate one chunk while the next is decoded (the ctypes call drops the GIL)."""
+    bounded and the caller can tabulate one chunk while the next is decoded (the ctypes call drops the GIL).  ``path``: a
+    file's, or a ``Source`` (a stream is taken up where a ``GpuBamStream`` on the same source gave up: ``seek``)."""
 
     def __init__(self, path, threads=None, chunk_bytes=256 << 20, keep_raw=False):
         import ctypes
@@ -627,8 +635,12 @@ class BamStream:
         self._lib = load_library()
         self._stream = ctypes.c_void_p()
         self.path, self.chunk_bytes, self.keep_raw = path, int(chunk_bytes), bool(keep_raw)
-        rc = self._lib.mdx_bam_open(str(path).encode(), ctypes.c_int(threads or min(64, usable_cpus())),
-                                    ctypes.byref(self._stream))
+        if isinstance(path, Source):
+            rc = self._lib.mdx_bam_open_source(path.handle, ctypes.c_int(threads or min(64, usable_cpus())),
+                                               ctypes.byref(self._stream))
+        else:
+            rc = self._lib.mdx_bam_open(str(path).encode(), ctypes.c_int(threads or min(64, usable_cpus())),
+                                        ctypes.byref(self._stream))
         if rc != 0:
             message = self._error()
             self.close()
@@ -718,16 +730,126 @@ class BamStream:
         self.close()
 
 
-def is_bam(path):
+def input_is_stream(path):
+    """The reference's rule for an input read as a stream (mapdamage/reader.py:32-38): ``-``, a FIFO (a named pipe,
+    ``/dev/fd/N`` of a process substitution) or a character device.  Such a path is opened once per run (``Source``)."""
+    import os
+    import stat
     if str(path) == "-":
+        return True
+    try:
+        mode = os.stat(path).st_mode
+    except OSError:
         return False
+    return stat.S_ISFIFO(mode) or stat.S_ISCHR(mode)
+
+
+class Source:
+    """The input opened once (include/mdx.h ``mdx_source_*``): a regular file is mapped, anything else — stdin (``-``), a
+    pipe, a FIFO, a character device — is read front to back by a thread of the library into a bounded window.  The header
+    read, the device decode and the host decoder all attach to it (``BamStream``, ``GpuBamStream``, ``read_bam_native``
+    take one in place of a path); ``peek`` tells SAM from BAM without losing a byte, ``text`` reads SAM through it.
+    ``str()`` is the path, so messages name the input as for a file."""
+
+    def __init__(self, path):
+        import ctypes
+
+        from .engine import load_library
+        self._lib = load_library()
+        self.path = path
+        self.handle = ctypes.c_void_p()
+        self._peeked = (0, b"")
+        rc = self._lib.mdx_source_open(str(path).encode(), ctypes.byref(self.handle))
+        if rc != 0:
+            message = self._lib.mdx_source_error(self.handle).decode() if self.handle else "cannot open"
+            self.close()
+            raise ValueError("%r: %s" % (str(path), message))
+        self.is_stream = bool(self._lib.mdx_source_is_stream(self.handle))
+
+    def __str__(self):
+        return str(self.path)
+
+    def error(self):
+        return self._lib.mdx_source_error(self.handle).decode() if self.handle else "closed"
+
+    def peek(self, n):
+        """The first ``n`` bytes (fewer: the input is shorter); a stream waits for them.  (They are kept here too: a stream
+        lets go of its first bytes once a decoder has read past them, and the format is asked about after that.)"""
+        import ctypes
+        if n <= self._peeked[0]:
+            return self._peeked[1][:n]
+        buf = ctypes.create_string_buffer(max(1, int(n)))
+        got = ctypes.c_int32(0)
+        if self._lib.mdx_source_peek(self.handle, buf, int(n), ctypes.byref(got)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self.error()))
+        self._peeked = (int(n), buf.raw[:got.value])
+        return self._peeked[1]
+
+    def readinto(self, view):
+        """The next bytes in order into ``view`` (a writable buffer): how many, 0 at the end."""
+        import ctypes
+        n = len(view)
+        if n == 0:
+            return 0
+        buf = (ctypes.c_char * n).from_buffer(view)
+        got = self._lib.mdx_source_read(self.handle, buf, n)
+        if got < 0:
+            raise ValueError("%r: %s" % (str(self.path), self.error()))
+        return int(got)
+
+    def text(self):
+        """The input as text, from its first byte — the peeked ones included — decoded as ``sys.stdin`` decodes."""
+        import sys
+        source = self
+
+        class _Raw(io.RawIOBase):
+            def readable(self):
+                return True
+
+            def readinto(self, view):
+                return source.readinto(memoryview(view).cast("B"))
+
+        stdin = sys.__stdin__
+        return io.TextIOWrapper(io.BufferedReader(_Raw(), 1 << 20), encoding=getattr(stdin, "encoding", None) or "utf-8",
+                                errors=getattr(stdin, "errors", None) or "strict")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._lib.mdx_source_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def is_bam(path):
+    """BGZF (BAM) or not (SAM text), by the first two bytes.  A ``Source`` is peeked; a path that is a stream
+    (``input_is_stream``) is never opened here — its bytes would be lost to the run — and must come as a ``Source``."""
+    if isinstance(path, Source):
+        return path.peek(2) == b"\x1f\x8b"
+    if input_is_stream(path):
+        raise ValueError("%r is a stream: it is read once, through a Source" % str(path))
     with open(path, "rb") as handle:
         return handle.read(2) == b"\x1f\x8b"
 
 
 def read_alignments(path):
     """SAM or BAM by content (mapdamage/reader.py:38 lets htslib sniff the format).  BAM goes through
-    the native decoder of libmdx.so; the pure-Python ``read_bam`` remains as its cross-check."""
+    the native decoder of libmdx.so; the pure-Python ``read_bam`` remains as its cross-check.  ``path``: a file's, or a
+    ``Source`` (stdin and pipes: SAM text is read through it, the sniffed bytes included)."""
+    if isinstance(path, Source):
+        if is_bam(path):
+            return read_bam_native(path)
+        return read_sam(path.text())
     if str(path) == "-":
         import sys
         return read_sam(sys.stdin)
@@ -738,7 +860,6 @@ def read_alignments(path):
     return read_bam_native(path)
 
 
-# ---------------------------------------------------------------------------- writers (tests, synthetic inputs)
 def header_text(ref_names, ref_lengths, read_groups):
     lines = ["@HD\tVN:1.6\tSO:unsorted"]
     lines += ["@SQ\tSN:%s\tLN:%d" % (n, ln) for n, ln in zip(ref_names, ref_lengths)]
