@@ -36,7 +36,7 @@ extern "C" {
                                      contig end (pysam ValueError from align.py:33 / main.py:180),
                                      tid/library out of range, CIGAR/SEQ length mismatch */
 
-#define MDX_ERR_UNSUPPORTED (-8)  /* mdx_gbam_*: something the GPU decode path does not take (use mdx_bam_*, from mdx_gbam_tell on) */
+#define MDX_ERR_UNSUPPORTED (-8)  /* mdx_gbam_* / mdx_gsam_*: something the GPU decode path does not take (use the host decoder, from mdx_gbam_tell / mdx_gsam_tell on) */
 #define MDX_ERR_COMM (-7)         /* RCCL failure, or another rank of the communicator reported an error */
 
 /* Optional hint in the `flag` column (a bit SAM does not define): every base quality of the record is at least
@@ -363,6 +363,9 @@ const char *mdx_source_error(const mdx_source *source);
 int mdx_source_is_stream(const mdx_source *source);
 int mdx_source_peek(mdx_source *source, uint8_t *buf, int32_t n, int32_t *got);
 int64_t mdx_source_read(mdx_source *source, uint8_t *buf, int64_t cap);
+/* mdx_source_seek: the next mdx_source_read starts at byte `offset` of the input (MDX_ERR_ARG in front of a stream's release
+ * point) — where a host SAM parser takes a stream up behind the device decoder (mdx_gsam_tell). */
+int mdx_source_seek(mdx_source *source, int64_t offset);
 void mdx_source_close(mdx_source *source);
 
 /* Native BAM decoding (host side, no GPU involved).  Replaces opening and iterating a
@@ -531,6 +534,52 @@ int mdx_warm(int32_t device, int64_t pinned_bytes);
  * streams, against zlib. */
 int mdx_gbam_inflate_blocks(mdx_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const uint32_t *blk, int32_t n_blocks,
                             uint8_t *out, int64_t out_bytes, int32_t *status, const uint32_t *want_crc, uint8_t *crc_ok);
+
+/* ---- GPU-side SAM text decode (additions of ABI 6).  The counterpart of mdx_gbam_* for SAM text, and with it of sam.read_sam
+ * (the parser behind mapdamage/reader.py:34-38 when the input is not BGZF): the text goes to HBM a slab of whole lines at a
+ * time and is parsed there — a bitmap of the slab's newlines and tabs, the line ends compacted out of it, eight lanes per
+ * line for the fields — into the columns of an mdx_batch that never exist on the host.  The view of mdx_gsam_next follows
+ * the rules of mdx_gbam_next: device pointers valid until the next mdx_gsam_next / mdx_gsam_close, MDX_SEQ_4BIT nibbles
+ * recoded as the BAM unpack recodes them (MDX_SEQ_4BITQ under mdx_gsam_set_min_basequal), flag bits 14 and 15 cleared and
+ * then MDX_FLAG_HAS_QUAL / MDX_FLAG_QUAL_ABOVE_MIN set, library 0xFFFF for a missing or unlisted read group (MDX_ERR_BAD_READ
+ * only if the kernel counts the record), a slab without a maskable record handed over without its quality column.
+ *   mdx_gsam_open        the header — the leading run of lines that start with '@' — is parsed on the host (mdx_gsam_header:
+ *                        a record-less mdx_bam for the mdx_bam_* accessors).  Two @SQ lines with one SN: MDX_ERR_UNSUPPORTED
+ *                        (read_sam keeps the last index of a name)
+ *   mdx_gsam_next        the complete lines within the next chunk_bytes of text (a slab ends at its last '\n'; a last line
+ *                        without one is a record too).  Two slabs in a pipeline: the next one is copied to HBM under the
+ *                        kernels of this one.  At the end: MDX_OK, n_reads 0, mdx_gsam_at_end 1.
+ *   mdx_gsam_tell        byte offset of the first line of the slab mdx_gsam_next would decode.  A stream is never released
+ *                        past it: a host parser can take the stream up there (mdx_source_seek) when a call fails — and the
+ *                        slab handed out last stays readable until the next call.
+ * Lines are parsed as read_sam parses them: fewer than 11 fields (an empty line too) is no record; FLAG & 0x3FFF; RNAME the
+ * header's index or -1; POS - 1; TLEN; CIGAR '*' no operations; SEQ '*' empty, upper-cased, every other symbol N; QUAL '*'
+ * 0xFF per base; the last RG:Z: tag wins.  Where Python's int(), str.upper(), text decoding or ReadBatch.validate() could
+ * differ from that, the slab is given up with MDX_ERR_UNSUPPORTED and none of it is counted: a byte >= 0x80 or a '\r', a
+ * line starting with '@' behind the first record, FLAG not 1-5 digits or above 65535, POS / TLEN not -?[0-9]+ or outside
+ * int32, a CIGAR byte outside [0-9MIDNSHP=X], an operation of 2^28 bases or more, digits without an operation, QUAL not '*'
+ * and not as long as SEQ or with a byte below 33, SEQ '*' with QUAL not '*'.  mdx_gsam_error says which line and why. */
+typedef struct mdx_gsam mdx_gsam;
+int mdx_gsam_open(mdx_ctx *ctx, const char *path, mdx_gsam **out);
+int mdx_gsam_open_source(mdx_ctx *ctx, mdx_source *source, mdx_gsam **out);
+const mdx_bam *mdx_gsam_header(const mdx_gsam *g);
+const char *mdx_gsam_error(const mdx_gsam *g);
+/* the read groups with the library of each, the library of a record without RG tag (-1: none), the quality column wanted —
+ * as mdx_gbam_configure (no mate columns: SAM's RNEXT / PNEXT are not parsed) */
+int mdx_gsam_configure(mdx_gsam *g, int32_t n_rg, const char *const *rg_ids, const int32_t *lib_of_rg, int32_t lib_default, int want_qual);
+/* MDX_SEQ_ASCII (default) or MDX_SEQ_4BIT, as mdx_gbam_set_seq_format */
+int mdx_gsam_set_seq_format(mdx_gsam *g, int32_t seq_format);
+/* --min-basequal on the device path, as mdx_gbam_set_min_basequal (the context's threshold; needs want_qual) */
+int mdx_gsam_set_min_basequal(mdx_gsam *g, int32_t minqual);
+int mdx_gsam_next(mdx_gsam *g, int64_t chunk_bytes, mdx_batch *dev_view);
+int mdx_gsam_at_end(const mdx_gsam *g);
+int mdx_gsam_tell(const mdx_gsam *g, int64_t *offset);
+/* the flag column of the view handed out last, to the host and back (--downsample), as mdx_gbam_view_flags / _set_flags */
+int mdx_gsam_view_flags(mdx_gsam *g, uint16_t *flags, int64_t n);
+int mdx_gsam_view_set_flags(mdx_gsam *g, const uint16_t *flags, int64_t n);
+/* a record the kernel counts has come by without qualities so far (under mdx_gsam_set_min_basequal; main.py:185-192) */
+int mdx_gsam_missing_qualities(const mdx_gsam *g);
+void mdx_gsam_close(mdx_gsam *g);
 
 #ifdef __cplusplus
 }

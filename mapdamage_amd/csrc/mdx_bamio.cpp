@@ -352,6 +352,17 @@ void mdx_source::close() {
 
 static mdx_source *source_ref(mdx_source *s) { if (s) s->refs.fetch_add(1); return s; }
 
+#ifndef MDX_HOST_ONLY
+// (mdx_internal.h: what the SAM decoder of mdx_samio.cpp needs of a source)
+mdx_source *mdx_source_retain(mdx_source *s) { return source_ref(s); }
+const uint8_t *mdx_source_bytes(mdx_source *s, size_t upto, size_t *have) {
+    *have = s->reach(upto);
+    return s->p;
+}
+size_t mdx_source_kept(const mdx_source *s) { return s->kept_from(); }
+void mdx_source_release_to(mdx_source *s, size_t upto) { s->release(upto); }
+#endif
+
 namespace {
 
 inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
@@ -903,6 +914,13 @@ const char *mdx_source_error(const mdx_source *s) {
 
 int mdx_source_is_stream(const mdx_source *s) { return (s && s->is_stream()) ? 1 : 0; }
 
+int mdx_source_seek(mdx_source *s, int64_t offset) {
+    if (!s || offset < 0) return MDX_ERR_ARG;
+    if ((size_t)offset < s->kept_from()) { s->error = s->behind((size_t)offset); return MDX_ERR_ARG; }
+    s->rpos = (size_t)offset;
+    return MDX_OK;
+}
+
 int mdx_source_peek(mdx_source *s, uint8_t *buf, int32_t n, int32_t *got) {
     if (!s || n < 0 || (n > 0 && !buf) || !got) return MDX_ERR_ARG;
     *got = 0;
@@ -962,6 +980,23 @@ int mdx_bam_read(const char *path, int threads, mdx_bam **out) {
         return MDX_ERR_ARG;
     }
 }
+
+}  // extern "C"
+
+#ifndef MDX_HOST_ONLY
+mdx_bam *mdx_bam_header_only(const std::string &text, const std::vector<std::string> &names, const std::vector<int64_t> &lengths) {
+    mdx_bam *b = new mdx_bam();
+    b->header_text = text;
+    b->ref_names = names;
+    b->ref_lengths = lengths;
+    b->cigar_off.assign(1, 0);
+    b->seq_off.assign(1, 0);
+    b->qname_off.assign(1, 0);
+    return b;
+}
+#endif
+
+extern "C" {
 
 void mdx_bam_free(mdx_bam *b) {
     if (!b) return;

@@ -475,3 +475,62 @@ void mdx_k_gbam_patch_qual(uint8_t *unc, const uint32_t *rec_off, const uint32_t
 void mdx_k_gbam_out_sizes(const uint8_t *unc, const uint32_t *rec_off, const uint8_t *rescaled, uint32_t n_rec, uint32_t *sizes, hipStream_t s);
 void mdx_k_gbam_write_back(const uint8_t *unc, const uint32_t *rec_off, const unsigned long long *out_off, const uint8_t *rescaled, const float *mr,
                            uint32_t n_rec, uint8_t *out, int *clash, hipStream_t s);
+
+// ---- GPU-side SAM text decode (mdx_gsam.hip; host side: mdx_gsam_* in mdx_samio.cpp)
+// why a slab is given up (status[0] of the kernels; status[1] = the lowest line of the slab that gave a reason)
+enum {
+    MDX_GSAM_BAD_BYTE = 1,          // a byte >= 0x80 or a '\r' (text decoding and universal newlines are Python's)
+    MDX_GSAM_HEADER_LINE = 2,       // a line starting with '@' behind the first record
+    MDX_GSAM_BAD_FLAG = 4,          // FLAG not 1-5 digits, or above 65535
+    MDX_GSAM_BAD_INT = 8,           // POS or TLEN not -?[0-9]+ or outside int32
+    MDX_GSAM_BAD_CIGAR = 16,        // a byte outside [0-9MIDNSHP=X], a length of 2^28 or more, digits without an operation
+    MDX_GSAM_BAD_QUAL = 32,         // QUAL not '*' and not as long as SEQ (SEQ '*' too), or a byte below 33
+};
+// an open-addressing hash of names (FNV-1a, linear probing): names concatenated, off[n + 1], table[mask + 1] (-1: empty),
+// value[n] (the library of a read group; unused for references)
+struct MdxGsamNames {
+    const uint8_t *names;
+    const uint32_t *off;
+    const int32_t *table;
+    const int32_t *value;
+    uint32_t mask;
+    int n;
+};
+// what the field pass leaves for the fill pass, per line (32 bytes)
+struct MdxGsamLine {
+    uint32_t flag_lib;              // FLAG & 0x3FFF | library << 16
+    int32_t tid, pos, tlen;
+    uint32_t cigar_a, cigar_b;      // the CIGAR field's bytes (empty for '*')
+    uint32_t seq_a, qual_a;         // where SEQ and QUAL start (qual_a 0xFFFFFFFF: '*')
+};
+struct MdxGsamCols {
+    uint16_t *flag, *lib;
+    int32_t *tid, *pos, *tlen;
+    uint32_t *cigar_off, *cigar, *seq_off;
+    uint8_t *seq, *qual;            // qual may be null (not wanted)
+    int seq_packed, minqual, fold;  // as in MdxGbamCols
+    uint32_t *counters;
+};
+uint32_t mdx_k_gsam_words(uint32_t n);         // 32-bit words of a bitmap of n bytes
+uint32_t mdx_k_gsam_blocks(uint32_t n);        // blocks of the byte passes (8 KiB each)
+size_t mdx_k_gsam_scan_parts(uint32_t n);      // uint4 of scratch a scan of n triples needs
+// the bitmaps of '\n' and '\t' and the newlines per block of 8 KiB, scanned: blk_nl[n_blocks].x = the slab's lines
+// (txt readable up to 32 x words; blk_nl: n_blocks + 1 entries)
+void mdx_k_gsam_classify(const uint8_t *txt, uint32_t n, uint32_t *nl_bits, uint32_t *tab_bits, uint4 *blk_nl, uint4 *part, uint32_t *status,
+                         hipStream_t s);
+// ... and the newline bitmap compacted: line_end[k] = the offset of line k's '\n'
+void mdx_k_gsam_line_ends(const uint32_t *nl_bits, uint32_t n, const uint4 *blk_nl, uint32_t *line_end, hipStream_t s);
+// the field pass and the scan of its counts: cnt[line] = (records, operations, bases in front of it), cnt[n_lines] = totals
+void mdx_k_gsam_fields(const uint8_t *txt, const uint32_t *tab_bits, const uint32_t *line_end, uint32_t n_lines, const MdxGsamNames &refs,
+                       const MdxGsamNames &rgs, int lib_default, uint4 *cnt, MdxGsamLine *ldata, uint4 *part, uint32_t *status, hipStream_t s);
+void mdx_k_gsam_fill(const uint8_t *txt, const uint4 *cnt, uint32_t n_lines, const MdxGsamLine *ldata, const MdxGsamCols &c, hipStream_t s);
+
+// (mdx_bamio.cpp) what the SAM decoder needs of a source and of a header-only mdx_bam
+struct mdx_source;
+struct mdx_bam;
+mdx_source *mdx_source_retain(mdx_source *s);                 // one more reference (mdx_source_close drops it)
+const uint8_t *mdx_source_bytes(mdx_source *s, size_t upto, size_t *have);   // offset 0's address; *have: bytes come in
+                                                              // (a stream waits for [0, upto) or its end)
+size_t mdx_source_kept(const mdx_source *s);                  // the release point (0: a file)
+void mdx_source_release_to(mdx_source *s, size_t upto);
+mdx_bam *mdx_bam_header_only(const std::string &text, const std::vector<std::string> &names, const std::vector<int64_t> &lengths);

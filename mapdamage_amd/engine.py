@@ -42,6 +42,9 @@ EXPORTS = (
     "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
     "mdx_source_open", "mdx_source_error", "mdx_source_is_stream", "mdx_source_peek", "mdx_source_read", "mdx_source_close",
     "mdx_bam_read_source", "mdx_bam_open_source", "mdx_gbam_open_source",
+    "mdx_source_seek", "mdx_gsam_open", "mdx_gsam_open_source", "mdx_gsam_header", "mdx_gsam_error", "mdx_gsam_configure",
+    "mdx_gsam_set_seq_format", "mdx_gsam_set_min_basequal", "mdx_gsam_next", "mdx_gsam_at_end", "mdx_gsam_tell",
+    "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*

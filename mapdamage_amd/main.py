@@ -209,7 +209,7 @@ def rescale_qual(options):
                                name, "missing" if not have else "%i bp" % have, length)
         with DamageEngine([("*", "*")], options.length, options.around, 0, device=options.device) as engine:
             summary = None
-            if options.gpu_decode and not options.host_deflate and _device_path_applies(options):
+            if options.gpu_decode and not options.host_deflate and _device_path_applies(options, sam_text=False):
                 # the records never on the host: inflated, rescaled, written back and deflated in HBM
                 from .rescale import rescale_bam_on_device
                 from .sam import GpuDecodeUnsupported
@@ -358,18 +358,18 @@ def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None
     return tables
 
 
-def _device_path_applies(options, world=1):
+def _device_path_applies(options, world=1, sam_text=True):
     """BAM files on disk; --downsample to a fraction too (the draws are made on the host from the flag column of every slab,
     reader.py:134-146) unless several ranks share the file (a rank steps over the slabs of the others without seeing their
     flags, and the stream of draws is the whole file's); a fixed number of reads is reservoir sampling over the whole file
-    (reader.py:148-164): the host's."""
+    (reader.py:148-164): the host's.  SAM text (``sam_text``: the tabulation pass, not --rescale-only) for one rank."""
     from .sam import is_bam
     # (stdin and pipes as files: through the run's one Source, options.source — a stream is never opened twice)
     source = getattr(options, "source", None)
     if source is None and is_stream(options.filename):
         return False
-    return is_bam(source if source is not None else options.filename) and (
-        options.downsample is None or (options.downsample < 1 and world == 1))
+    bam = is_bam(source if source is not None else options.filename)
+    return (bam or (sam_text and world == 1)) and (options.downsample is None or (options.downsample < 1 and world == 1))
 
 
 def _slab_bytes(options, world):
@@ -389,10 +389,15 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     the path does not apply or has given up — the caller decodes on the host, which also words the errors the way the
     reference does: the whole file (carry None), or, when the device path failed on a slab it had not begun to count,
     the rest of it with the same engine (``_tabulate_on_host``'s ``carry``)."""
-    from .sam import GpuBamStream, GpuDecodeUnsupported
+    from .sam import GpuBamStream, GpuDecodeUnsupported, GpuSamStream
     # a stream (stdin, a pipe) is read once: a host decoder that takes over goes on where the device path stopped, never
     # from the start
     streaming = reader.source is not None and reader.source.is_stream
+    # SAM text: parsed on the device as well (sam.GpuSamStream); a stream of it is taken up by the host parser from the first
+    # line of the slab that failed — also for a bad record or read group, so that the host words the error (the slab handed
+    # out last stays in the stream until the next one is asked for: each slab is synchronised before the next)
+    sam_text = not reader.is_bam
+    sam_stream = sam_text and streaming
     if not _device_path_applies(options, ranks.world):
         logger.debug("the GPU decode path does not apply to this run; decoding on the host")
         return None, None
@@ -416,10 +421,11 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         if warm is not None:
             warm.join()         # (the pinned buffer it leaves behind is the one the first slab takes)
         stages.mark("warm-up joined")
-        with GpuBamStream(engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
-                          lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual) as stream:
+        with (GpuSamStream if sam_text else GpuBamStream)(
+                engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
+                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual) as stream:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
-            slab, n_reads = 0, 0
+            slab, n_reads, n_kept = 0, 0, 0
             try:
                 while True:
                     mine = slab % ranks.world == ranks.rank
@@ -428,6 +434,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                         if not stream.skip():
                             break
                         continue
+                    if sam_stream:
+                        slab_start, kept_before, rand_state = stream.tell(), n_kept, downsample_rand.getstate()
                     try:
                         view = stream.next_view()
                     except ValueError:
@@ -444,6 +452,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                             if where is not None and reader._chunks is not None and (
                                     streaming or (slab > 1 and options.downsample is None)):
                                 carry = (engine, where, n_reads, downsample_rand if options.downsample is not None else None)
+                            elif where is not None and sam_stream:
+                                carry = (engine, where, n_kept, downsample_rand if options.downsample is not None else None)
                         raise
                     if view is None:
                         break
@@ -464,6 +474,16 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                         logger.warning("Reads without PHRED scores found; cannot filter by --min-basequal")
                         warned_about_quals = True
                     engine.tabulate_view(view, record_base=n_reads)
+                    if sam_stream:
+                        try:
+                            engine.sync()
+                        except BadReadError:
+                            downsample_rand.setstate(rand_state)
+                            carry = (engine, slab_start, kept_before, downsample_rand if options.downsample is not None else None)
+                            raise
+                        # (the records the host decoder would have counted: its record numbers go on from there)
+                        kept = stream.view_flags(view) if options.downsample is None else flags
+                        n_kept += int(((kept & FLAG_FILTER) == 0).sum())
                     n_reads += int(view.n_reads)
                 engine.sync()
                 stages.mark("decode and tabulate")
@@ -482,11 +502,12 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     except BadReadError as error:
         # a record the reference cannot process, or one without a usable read group: the host path names it — but a stream,
         # which the host decoder cannot read again up to that record: the device path's error stands
-        if streaming:
+        if streaming and not sam_stream:
             engine.close()
             raise
         reason = "a record the device path cannot count (MDX_ERR_BAD_READ, record %d)" % error.read_index
-        carry = None
+        if not sam_stream:
+            carry = None
     except (ValueError, MdxError) as error:
         # a damaged file (the host decoder finds the same damage and words the error), or the device path out of
         # memory: either way the host path has the last word
@@ -500,8 +521,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         engine.close()
         logger.warning("GPU decode path gave up: %s; decoding on the host (the whole file again)", reason)
     else:
-        logger.warning("GPU decode path gave up: %s; decoding on the host (from compressed offset %d on: %d records are counted)",
-                       reason, carry[1][0], carry[2])
+        logger.warning("GPU decode path gave up: %s; decoding on the host (from %s offset %d on: %d records are counted)",
+                       reason, "byte" if sam_text else "compressed", carry[1] if sam_text else carry[1][0], carry[2])
     return None, carry
 
 
@@ -578,7 +599,8 @@ def main(argv):
                      load_library().mdx_host_threads(), usable_cpus(), os.environ.get("LOCAL_WORLD_SIZE", "1"))
         reader = BAMReader(options.filename, merge_libraries=options.merge_libraries,
                            downsample_to=options.downsample, downsample_seed=options.downsample_seed,
-                           chunk_bytes=int(options.chunk_mb * (1 << 20)), source=options.source)
+                           chunk_bytes=int(options.chunk_mb * (1 << 20)), source=options.source,
+                           sam_header_only=options.gpu_decode and _device_path_applies(options, ranks.world))
         reflengths = reader.get_references()
         fai_lengths = read_fasta_index(str(options.ref) + ".fai")
         if not fai_lengths:

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import layout as L
 from .batch import ReadBatch
-from .sam import Alignments, BamStream, BAMError, Source, input_is_stream, is_bam, read_alignments
+from .sam import Alignments, BamStream, BAMError, Source, input_is_stream, is_bam, read_alignments, read_sam, sam_header
 
 
 def is_stream(path):
@@ -55,7 +55,7 @@ def downsample_indices(flag, tid, pos, downsample_to, rand):
 
 class BAMReader:
     def __init__(self, filepath, merge_libraries=False, downsample_to=None, downsample_seed=None,
-                 chunk_bytes=None, source=None):
+                 chunk_bytes=None, source=None, sam_header_only=False):
         """``chunk_bytes``: decode a BAM file in chunks of that many uncompressed bytes (``iter_batches``
         then yields one batch per chunk and ``handle`` holds the header only) instead of all at once.
         Downsampling to a fixed number of reads needs the whole file (reservoir + coordinate sort,
@@ -63,7 +63,10 @@ class BAMReader:
         A stream (``is_stream``: stdin, a pipe) is opened once, as ``source`` (a ``sam.Source``: the caller's, or one of
         the reader's own), which the device decode and a host decoder that takes up after it share; its BAM is decoded in
         chunks whatever ``chunk_bytes`` says (256 MiB when it says nothing), so that the header read does not read the
-        whole stream — but for -n N, which needs all of it."""
+        whole stream — but for -n N, which needs all of it.
+        ``sam_header_only`` (the device path, ``sam.GpuSamStream``): SAM text is not parsed here — ``handle`` holds its header
+        only, read without consuming a stream — and ``iter_batches`` parses the records (all of them, or a stream from
+        ``resume``, a byte offset, on) when the host has to count them after all."""
         log = logging.getLogger(__name__)
         self.filepath = filepath
         self.downsample_to = downsample_to
@@ -75,13 +78,13 @@ class BAMReader:
         if self.is_stream and not chunk_bytes:
             chunk_bytes = 256 << 20
         self.is_bam = is_bam(src)
-        if chunk_bytes and self.is_bam and (downsample_to is None or downsample_to < 1):
+        self._sam_body = None
+        if sam_header_only and not self.is_bam and (downsample_to is None or downsample_to < 1):
+            header, self._sam_body = sam_header(src)
+            self.handle = Alignments(header, self._empty_batch(), [], [])
+        elif chunk_bytes and self.is_bam and (downsample_to is None or downsample_to < 1):
             self._chunks = BamStream(src, chunk_bytes=chunk_bytes)
-            empty = ReadBatch(np.zeros(0, np.uint16), np.zeros(0, np.uint16), np.zeros(0, np.int32),
-                              np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(1, np.uint32),
-                              np.zeros(0, np.uint32), np.zeros(1, np.uint32), np.zeros(0, np.uint8),
-                              np.zeros(0, np.uint8))
-            self.handle = Alignments(self._chunks.header, empty, [], [])
+            self.handle = Alignments(self._chunks.header, self._empty_batch(), [], [])
         else:
             self.handle: Alignments = read_alignments(src)
         self._merge_libraries = merge_libraries
@@ -92,6 +95,12 @@ class BAMReader:
         for readgroup, library in self._readgroups.items():
             self._libraries.setdefault(library, set()).add(readgroup)
         log.info("Found %i libraries in BAM file", len(self._libraries))
+
+    @staticmethod
+    def _empty_batch():
+        return ReadBatch(np.zeros(0, np.uint16), np.zeros(0, np.uint16), np.zeros(0, np.int32), np.zeros(0, np.int32),
+                         np.zeros(0, np.int32), np.zeros(1, np.uint32), np.zeros(0, np.uint32), np.zeros(1, np.uint32),
+                         np.zeros(0, np.uint8), np.zeros(0, np.uint8))
 
     def get_references(self):
         return dict(zip(self.handle.header.references, self.handle.header.lengths))
@@ -126,6 +135,21 @@ class BAMReader:
         ``resume``: (compressed offset of a BGZF block, inflated bytes in front of the first record wanted) — the records
         from there on only (chunked BAM decode: ``BamStream.seek``); ``rand``: the generator whose stream of --downsample
         draws they carry on (a run that took a stream up from the device decode: its draws go on unbroken)."""
+        if self._sam_body is not None:
+            # SAM text the device path has not counted: the whole file, or a stream from `resume` (or its first record) on,
+            # with the header read already and the run's --downsample generator
+            if self.source is not None and self.source.is_stream:
+                self.source.seek(self._sam_body if resume is None else resume)
+                handle = read_sam(self.source.text(), header=self.handle.header)
+            else:
+                handle = read_alignments(self.source if self.source is not None else self.filepath)
+            indices = self.kept_indices(handle, rand)
+            batch = handle.batch
+            if len(indices) != batch.n:
+                batch = batch.take(indices)
+            batch.lib = self.library_column(indices, handle)
+            yield batch
+            return
         if resume is not None:
             if self._chunks is None:
                 raise ValueError("resuming needs the chunked BAM decoder")

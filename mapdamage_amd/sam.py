@@ -121,12 +121,15 @@ def _finish(header, flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs
     return Alignments(header, batch, rgs, qnames)
 
 
-def read_sam(path_or_handle):
+def read_sam(path_or_handle, header=None):
+    """SAM text -> ``Alignments``.  ``header``: a ``Header`` read already (a host parser that takes a stream up behind the
+    device decoder, ``GpuSamStream.tell``): every line is then a record line, and a line that starts with '@' is skipped."""
     handle = open(path_or_handle, "rt") if isinstance(path_or_handle, (str, bytes)) or hasattr(path_or_handle, "__fspath__") else path_or_handle
     head, lines = [], []
     for line in handle:
         (head if line.startswith("@") else lines).append(line)
-    header = Header("".join(head))
+    if header is None:
+        header = Header("".join(head))
     tid_of = {name: i for i, name in enumerate(header.references)}
     flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs, qnames = [], [], [], [], [], [], [], [], [], []
     for line in lines:
@@ -617,6 +620,169 @@ class GpuBamStream:
             pass
 
 
+class GpuSamStream:
+    """GPU-side parse of SAM text (include/mdx.h ``mdx_gsam_*``): a slab of whole lines at a time goes to HBM and is parsed
+    there into the columns ``read_sam`` makes; ``GpuBamStream``'s interface (``next_view`` returns an ``MdxBatch`` of DEVICE
+    pointers, None at the end).  Raises ``GpuDecodeUnsupported`` for a slab where Python's parser could read a line otherwise
+    (see the header) — the caller then parses on the host, a stream from ``tell()`` on (``Source.seek``).  ``path``: a
+    file's, or a ``Source``."""
+
+    def __init__(self, engine, path, readgroups=(), lib_default=None, chunk_bytes=256 << 20, want_qual=False,
+                 min_basequal=0, packed=None):
+        import ctypes
+        self._lib = engine._lib
+        self._engine = engine
+        self._g = ctypes.c_void_p()
+        self.path, self.chunk_bytes = path, int(chunk_bytes)
+        if not engine._ctx:
+            raise ValueError("the engine is closed")
+        lib = self._lib
+        lib.mdx_gsam_error.restype = ctypes.c_char_p
+        lib.mdx_gsam_header.restype = ctypes.c_void_p
+        for name in ("mdx_gsam_error", "mdx_gsam_header", "mdx_gsam_at_end", "mdx_gsam_missing_qualities", "mdx_gsam_close"):
+            getattr(lib, name).argtypes = [ctypes.c_void_p]
+        if isinstance(path, Source):
+            rc = lib.mdx_gsam_open_source(engine._ctx, path.handle, ctypes.byref(self._g))
+        else:
+            rc = lib.mdx_gsam_open(engine._ctx, str(path).encode(), ctypes.byref(self._g))
+        if not hasattr(engine, "_streams"):
+            import weakref
+            engine._streams = weakref.WeakSet()
+        engine._streams.add(self)
+        if rc != 0:
+            message = self._error()
+            self.close()
+            if rc == -8:
+                raise GpuDecodeUnsupported("%r: %s" % (str(path), message))
+            raise ValueError("%r: %s" % (str(path), message))
+        self.header = _native_header(lib, lib.mdx_gsam_header(self._g))
+        ids = [str(rg).encode() for rg, _ in readgroups]
+        arr = (ctypes.c_char_p * max(1, len(ids)))(*ids)
+        libs = (ctypes.c_int32 * max(1, len(ids)))(*[int(x) for _, x in readgroups])
+        rc = lib.mdx_gsam_configure(self._g, len(ids), arr, libs, -1 if lib_default is None else int(lib_default), int(bool(want_qual)))
+        if rc != 0:
+            raise ValueError("%r: %s" % (str(path), self._error()))
+        if min_basequal and lib.mdx_gsam_set_min_basequal(self._g, int(min_basequal)) != 0:
+            raise ValueError("%r: %s" % (str(path), self._error()))
+        if packed is None:
+            packed = bool(min_basequal) or not want_qual
+        self.packed = bool(packed)
+        if self.packed:
+            lib.mdx_gsam_set_seq_format(self._g, 1)
+
+    def _error(self):
+        return self._lib.mdx_gsam_error(self._g).decode(errors="replace") if self._g else "GPU SAM decode failed"
+
+    def missing_qualities(self):
+        """A record the kernel counts has come by without qualities (main.py:185-192 warns once)."""
+        return bool(self._lib.mdx_gsam_missing_qualities(self._g))
+
+    def next_view(self):
+        import ctypes
+        from .engine import MdxBatch
+        view = MdxBatch()
+        rc = self._lib.mdx_gsam_next(self._g, ctypes.c_int64(self.chunk_bytes), ctypes.byref(view))
+        if rc == -8:
+            raise GpuDecodeUnsupported("%r: %s" % (str(self.path), self._error()))
+        if rc != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        if view.n_reads == 0 and self._lib.mdx_gsam_at_end(self._g):
+            return None
+        view.mtid, view.mpos = None, None
+        return view
+
+    def tell(self):
+        """Byte offset of the first line of the slab ``next_view`` would parse (a failed call: of the slab that failed)."""
+        import ctypes
+        off = ctypes.c_int64()
+        if self._lib.mdx_gsam_tell(self._g, ctypes.byref(off)) != 0:
+            return None
+        return off.value
+
+    def view_flags(self, view):
+        import ctypes
+        n = int(view.n_reads)
+        out = np.empty(n, np.uint16)
+        rc = self._lib.mdx_gsam_view_flags(self._g, ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(n))
+        if rc != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        return out
+
+    def set_view_flags(self, view, flags):
+        import ctypes
+        flags = np.ascontiguousarray(flags, dtype=np.uint16)
+        assert flags.shape[0] == int(view.n_reads)
+        rc = self._lib.mdx_gsam_view_set_flags(self._g, ctypes.c_void_p(flags.ctypes.data), ctypes.c_int64(flags.shape[0]))
+        if rc != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+
+    def fixups(self):
+        return 0
+
+    def skip(self):
+        raise GpuDecodeUnsupported("%r: SAM text is parsed by one rank" % str(self.path))
+
+    def close(self):
+        if self._g:
+            self._lib.mdx_gsam_close(self._g)
+            self._g = None
+            streams = getattr(self._engine, "_streams", None)
+            if streams is not None:
+                streams.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sam_header(src):
+    """The header of SAM text — its leading run of lines that start with '@', as ``read_sam`` reads it — and the byte
+    offset of the first line behind it, without reading further: a ``Source`` is peeked (a stream keeps every byte for
+    whoever parses the body), a path is read line by line."""
+    if isinstance(src, Source):
+        n = 1 << 16
+        while True:
+            data = src.peek(n)
+            complete = len(data) < n            # (the whole input)
+            off, done = 0, False
+            while True:
+                if off >= len(data):
+                    done = complete
+                    break
+                if data[off:off + 1] != b"@":
+                    done = True
+                    break
+                e = data.find(b"\n", off)
+                if e < 0:
+                    if complete:
+                        off, done = len(data), True
+                    break
+                off = e + 1
+            if done:
+                break
+            n *= 2
+        raw = data[:off]
+    else:
+        raw = b""
+        with open(src, "rb") as handle:
+            for line in handle:
+                if not line.startswith(b"@"):
+                    break
+                raw += line
+    import sys
+    encoding = getattr(sys.__stdin__, "encoding", None) or "utf-8" if isinstance(src, Source) else None
+    text = raw.decode(encoding) if encoding else io.TextIOWrapper(io.BytesIO(raw)).read()
+    return Header(text), len(raw)
+
+
 class GpuDecodeUnsupported(ValueError):
     """The file's layout is not one the GPU decode path takes (MDX_ERR_UNSUPPORTED)."""
 
@@ -812,6 +978,15 @@ class Source:
         stdin = sys.__stdin__
         return io.TextIOWrapper(io.BufferedReader(_Raw(), 1 << 20), encoding=getattr(stdin, "encoding", None) or "utf-8",
                                 errors=getattr(stdin, "errors", None) or "strict")
+
+    def seek(self, offset):
+        """The next ``readinto`` (and ``text``) starts at byte ``offset`` of the input (a stream: not in front of what it has
+        let go of)."""
+        import ctypes
+        fn = self._lib.mdx_source_seek
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        if fn(self.handle, int(offset)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self.error()))
 
     def close(self):
         if getattr(self, "handle", None):
