@@ -164,11 +164,22 @@ int mdx_set_reference(mdx_ctx *ctx, const uint8_t *bases, const int64_t *contig_
  * kernel takes the line ends out by the index's arithmetic — no pass over the bases on the host; pieces of the file that
  * hold none of the wanted sequences are not read.  lengths (may be NULL) receives the length of each; a name the index
  * lacks is MDX_ERR_ARG, or with missing_ok an empty contig (a record mapped to it is MDX_ERR_BAD_READ when it is met: the
- * reference fails in fetch at that read, not before).  Uncompressed FASTA only (a bgzip-ed one goes through
- * mdx_set_reference).  Synchronous. */
+ * reference fails in fetch at that read, not before).  Synchronous.
+ * The file may be uncompressed or bgzip-compressed (BGZF; told by its first bytes, not by its name).  A BGZF file's index
+ * holds offsets into the inflated text, as htslib writes them, and it has a second one, `<fasta_path>.gzi` (bgzip's block
+ * index).  mdx_fasta_index makes sure both exist: a missing .fai is built from the text inflated on the host's threads — once —
+ * and written together with the .gzi; a .gzi that exists is left alone.  mdx_set_reference_fasta sends the BGZF blocks that
+ * hold bytes of the wanted sequences — no others — to HBM compressed and inflates, CRC-checks and strips them there; the block
+ * table comes from the .gzi, or from a walk over the block headers when there is none or it does not fit the file.  A block
+ * that does not inflate, whose ISIZE disagrees or whose CRC32 is wrong is MDX_ERR_ARG, the message naming the block's offset
+ * in the file.  A plain (single-member) gzip file is neither: its text begins with 0x1f, not with '>'.
+ * mdx_fasta_load_stats (introspection for tests and tools): what the calling thread's last mdx_set_reference_fasta read —
+ * out[0] BGZF blocks of the file, out[1] blocks inflated on the device, out[2] slabs (BGZF) or pieces (uncompressed) uploaded,
+ * out[3] bytes of the file uploaded. */
 int mdx_fasta_index(const char *fasta_path, char *err, int32_t err_cap);
 int mdx_set_reference_fasta(mdx_ctx *ctx, const char *fasta_path, int32_t n_contig, const char *const *names, int32_t missing_ok,
                             int64_t *lengths);
+int mdx_fasta_load_stats(int64_t *out);
 /* Introspection for tests: bases [start, end) of contig tid of the resident reference as the kernels see them — the letter
  * where ref.fetch(chrom, start, end).upper() (main.py:180) holds one of "ACGT", '-' for '-', 'N' for anything else.  Host
  * buffer of end - start bytes; synchronous. */

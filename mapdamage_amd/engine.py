@@ -39,7 +39,7 @@ EXPORTS = (
     "mdx_gbam_view_flags", "mdx_gbam_view_set_flags",
     "mdx_rescale_patches_device", "mdx_tabulate_rescale_patches_device", "mdx_rescale_expand_device", "mdx_mr_round", "mdx_batch_fold", "mdx_bgzf_deflate",
     "mdx_gbam_rescale_slab", "mdx_gbam_write_rescaled", "mdx_gbam_record_name",
-    "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
+    "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_fasta_load_stats", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
     "mdx_source_open", "mdx_source_error", "mdx_source_is_stream", "mdx_source_peek", "mdx_source_read", "mdx_source_close",
     "mdx_bam_read_source", "mdx_bam_open_source", "mdx_gbam_open_source",
     "mdx_source_seek", "mdx_gsam_open", "mdx_gsam_open_source", "mdx_gsam_header", "mdx_gsam_error", "mdx_gsam_configure",
@@ -159,6 +159,7 @@ def load_library(path=None):
     lib.mdx_gbam_close.restype = None
     lib.mdx_gbam_close.argtypes = [ctypes.c_void_p]
     lib.mdx_fasta_index.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32]
+    lib.mdx_fasta_load_stats.argtypes = [ctypes.c_void_p]
     lib.mdx_set_reference_fasta.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
                                             ctypes.c_void_p]
     lib.mdx_reference_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
@@ -315,6 +316,13 @@ class DamageEngine:
         bases, offs = ref.concat()
         self._check(self._lib.mdx_set_reference(self._ctx, _ptr(bases), _ptr(offs),
                                                 ctypes.c_int32(len(ref.names))))
+
+    def fasta_load_stats(self):
+        """What this thread's last ``set_reference`` of a ``FastaOnDisk`` read (``mdx_fasta_load_stats``): BGZF blocks of the
+        file, blocks inflated on the device, slabs (or pieces of an uncompressed file) uploaded, bytes of the file uploaded."""
+        out = np.zeros(4, np.int64)
+        self._check(self._lib.mdx_fasta_load_stats(_ptr(out)))
+        return dict(zip(("blocks", "inflated", "slabs", "bytes"), (int(x) for x in out)))
 
     def reference_fetch(self, tid, start, end):
         """``ref.fetch(chrom, start, end).upper()`` (main.py:180) as the kernels see it: the four bases, '-', and 'N' for

@@ -47,6 +47,32 @@ def write_fasta(path, ref: Reference, width=60):
             offset += len(seq) + (len(seq) + width - 1) // width
 
 
+def is_bgzf(path):
+    """Is the file bgzip-compressed (BGZF, SAM specification 4.1)?  Told by its first bytes, not by its name: a gzip member
+    with FEXTRA whose extra field holds a 'BC' subfield of length 2, among other subfields or alone."""
+    try:
+        with open(path, "rb") as handle:
+            head = handle.read(12)
+            if len(head) < 12 or head[:4] != b"\x1f\x8b\x08\x04":
+                return False
+            extra = handle.read(int.from_bytes(head[10:12], "little"))
+    except OSError:
+        return False
+    at = 0
+    while at + 4 <= len(extra):
+        size = int.from_bytes(extra[at + 2:at + 4], "little")
+        if extra[at:at + 2] == b"BC" and size == 2 and at + 6 <= len(extra):
+            return True
+        at += 4 + size
+    return False
+
+
+def is_plain_gzip(path):
+    """A file named ``*.gz`` that is not BGZF: one gzip member, which cannot be split across the device's lanes (and which
+    ``pysam.FastaFile`` refuses); ``read_fasta`` reads it on the host."""
+    return str(path).endswith(".gz") and not is_bgzf(path)
+
+
 class FastaOnDisk:
     """The sequences of a BAM header (``tid`` order) as they lie in an indexed FASTA file: what ``pysam.FastaFile``
     (main.py:115) is to the reference's loop.  Nothing is read here: ``DamageEngine.set_reference`` hands the path to the
@@ -58,11 +84,12 @@ class FastaOnDisk:
 
 
 def ensure_fasta_index(path):
-    """``<path>.fai`` exists afterwards (htslib builds it when ``pysam.FastaFile`` opens a file without one, main.py:115);
+    """``<path>.fai`` exists afterwards (htslib builds it when ``pysam.FastaFile`` opens a file without one, main.py:115), and
+    for a bgzip-compressed file ``<path>.gzi`` beside it (htslib wants both; the library writes them together);
     raises ValueError with the library's message when the file cannot be indexed."""
     import ctypes
     import os
-    if os.path.exists(str(path) + ".fai"):
+    if os.path.exists(str(path) + ".fai") and (os.path.exists(str(path) + ".gzi") or not is_bgzf(path)):
         return
     from .engine import load_library
     err = ctypes.create_string_buffer(512)
@@ -142,9 +169,9 @@ def reference_for_bam(fasta_path, bam_names, missing_ok=False):
     """Contigs of the FASTA reordered to BAM ``tid`` order (chrom lookup is by name,
     main.py:175-180).  ``missing_ok``: a sequence the FASTA lacks becomes an empty contig — a record that maps to it
     is then a bad record when it is met (the reference fails in ``fetch`` at that read, not before).
-    An uncompressed FASTA stays on disk (``FastaOnDisk``: the library loads it, no pass over the bases here); a
-    gzip-compressed one is read here."""
-    if not str(fasta_path).endswith(".gz"):
+    An uncompressed or bgzip-compressed FASTA (BGZF under any name) stays on disk (``FastaOnDisk``: the library loads it —
+    a BGZF file is inflated on the device —, no pass over the bases here); a plain gzip file is read here."""
+    if not is_plain_gzip(fasta_path):
         ensure_fasta_index(fasta_path)
         have = dict(_fai_records(str(fasta_path) + ".fai"))
         if not missing_ok:
@@ -152,6 +179,9 @@ def reference_for_bam(fasta_path, bam_names, missing_ok=False):
                 if n not in have:
                     raise KeyError(n)
         return FastaOnDisk(fasta_path, bam_names, [have.get(n, 0) for n in bam_names], missing_ok)
+    logging.getLogger(__name__).info("Reference %r is plain gzip, not BGZF: one gzip member cannot be inflated in parallel, so it is "
+                                     "read line by line on the host (slow for a large genome); compress it with 'bgzip' to "
+                                     "have it loaded on the device", str(fasta_path))
     return reference_in_memory(fasta_path, bam_names, missing_ok)
 
 

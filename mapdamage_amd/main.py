@@ -16,7 +16,7 @@ import numpy as np
 from . import __version__
 from .batch import mark_unmaskable
 from .engine import BadReadError, DamageEngine, MdxError
-from .fasta import compare_sequence_dicts, read_fasta_index, reference_for_bam
+from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
 from .sam import BAMError
@@ -602,12 +602,25 @@ def main(argv):
                            chunk_bytes=int(options.chunk_mb * (1 << 20)), source=options.source,
                            sam_header_only=options.gpu_decode and _device_path_applies(options, ranks.world))
         reflengths = reader.get_references()
+        if not is_plain_gzip(options.ref):
+            # (pysam.FastaFile indexes a file that has no index, main.py:115; a bgzip-compressed one gets .fai and .gzi)
+            try:
+                ensure_fasta_index(options.ref)
+            except (ValueError, OSError) as error:
+                logger.error("%s", error)
+                return 1
         fai_lengths = read_fasta_index(str(options.ref) + ".fai")
         if not fai_lengths:
             return 1
         if not compare_sequence_dicts(fai_lengths, reflengths):
             return 1
         ref = reference_for_bam(options.ref, reader.handle.header.references)
+        if getattr(ref, "path", None) is not None:
+            logger.info("Reference: %s FASTA, loaded by the device (%s)", "bgzip-compressed" if is_bgzf(options.ref) else "uncompressed",
+                        "BGZF blocks inflated, CRC-checked and stripped of line ends in HBM" if is_bgzf(options.ref)
+                        else "stripped of line ends in HBM")
+        else:
+            logger.info("Reference: plain gzip FASTA, read by the host (Python reader)")
         libraries = reader.get_libraries()
         stages.mark("headers and index")
 
