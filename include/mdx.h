@@ -339,6 +339,12 @@ int64_t mdx_fused_launches(const mdx_ctx *ctx);
 int64_t mdx_packed_launches(const mdx_ctx *ctx);
 /* Calls so far that bucketed their batch by library themselves (several libraries, a batch without mdx_batch::libsort). */
 int64_t mdx_libsorts(const mdx_ctx *ctx);
+/* The geometry of the context's last tabulation launch (introspection for tests; all zero before the first): out[0] blocks of
+ * the grid, out[1] wavefronts per block, out[2] tiles of the call's whole batch, out[3] pools of blocks that share a tile
+ * counter.  (A launch of the packed kernels over several libraries hands out the tiles of its own libraries' kept records, a
+ * library's to the pools of that library; the split is made on the device and not reported: out[2] bounds it from above.)  MDX_TEST_CUS=n in the environment when the context is created sizes its launches as on a device
+ * of n compute units (never more than the device has): few wavefronts then take many tiles each of a small batch. */
+int mdx_last_launch_geometry(const mdx_ctx *ctx, int32_t out[4]);
 /* The integer content of the `subs` dictionary that _rescale_qual_read fills through _record_subs
  * (rescale.py:82-143) and _print_subs logs (:159-192), accumulated over every mdx_rescale_host call
  * since mdx_rescale_set_model.  words (uint64), npos = 1 + len5p + len3p:

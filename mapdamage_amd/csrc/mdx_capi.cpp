@@ -158,6 +158,7 @@ struct mdx_ctx {
     int64_t n_fused = 0;           // fused launches so far (mdx_fused_launches)
     int64_t n_packed = 0;          // launches of the packed kernel so far (mdx_packed_launches)
     int64_t fuse_list_cap = 0;     // entries per list of rs_in (the last fused launch)
+    int32_t last_geom[4] = {0, 0, 0, 0};   // the last tabulation launch: blocks, wavefronts per block, tiles of the batch, pools (mdx_last_launch_geometry)
     void *pin[2] = {nullptr, nullptr};
     hipEvent_t pin_done[2] = {nullptr, nullptr};
     bool pin_busy[2] = {false, false};
@@ -279,6 +280,14 @@ int mdx_create(const mdx_config *cfg, mdx_ctx **out) {
     hipDeviceProp_t prop;
     HIP_TRY(c, hipGetDeviceProperties(&prop, cfg->device));
     c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // (MDX_TEST_CUS=n in the environment, tests only: the launches of this context are sized as on a device of n CUs — never
+    // more than the device has — so that a wavefront takes many tiles of a small batch: rounds, wrapping rings, the early fold
+    // of the bit-sliced planes, tiles of other pools.  Read per context, not once per process.  Everything that sizes a
+    // launch — grids, pools, partial slots, tile counters, per-wavefront scratch — follows n_cu.)
+    if (const char *e = getenv("MDX_TEST_CUS")) {
+        const int n = atoi(e);
+        if (n >= 1 && n < c->n_cu) c->n_cu = n;
+    }
     HIP_TRY(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
     lap("context, stream");
@@ -800,6 +809,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
                                 (quota ? ": tabulate the batch in smaller pieces" : ""));
             }
             a.lists = (uint4 *)c->lists.p;
+            c->last_geom[0] = grid; c->last_geom[1] = wpb_l; c->last_geom[2] = (int32_t)n_tiles; c->last_geom[3] = (int32_t)n_pools;
         }
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (c->timing) {
@@ -1538,6 +1548,11 @@ int mdx_rescale_host(mdx_ctx *c, const mdx_batch *h, const int32_t *mtid, const 
 int64_t mdx_fused_launches(const mdx_ctx *c) { return c ? c->n_fused : -1; }
 int64_t mdx_packed_launches(const mdx_ctx *c) { return c ? c->n_packed : -1; }
 int64_t mdx_libsorts(const mdx_ctx *c) { return c ? c->n_libsorts : -1; }
+int mdx_last_launch_geometry(const mdx_ctx *c, int32_t out[4]) {
+    if (!c || !out) return MDX_ERR_ARG;
+    for (int i = 0; i < 4; i++) out[i] = c->last_geom[i];
+    return MDX_OK;
+}
 
 int mdx_rescale_timing_read(mdx_ctx *c, int64_t *n_launches, double *total_ms) {
     if (!c) return MDX_ERR_ARG;

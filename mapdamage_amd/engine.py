@@ -45,6 +45,7 @@ EXPORTS = (
     "mdx_source_seek", "mdx_gsam_open", "mdx_gsam_open_source", "mdx_gsam_header", "mdx_gsam_error", "mdx_gsam_configure",
     "mdx_gsam_set_seq_format", "mdx_gsam_set_min_basequal", "mdx_gsam_next", "mdx_gsam_at_end", "mdx_gsam_tell",
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
+    "mdx_last_launch_geometry",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -122,6 +123,8 @@ def load_library(path=None):
     lib.mdx_packed_launches.argtypes = [ctypes.c_void_p]
     lib.mdx_libsorts.restype = ctypes.c_int64
     lib.mdx_libsorts.argtypes = [ctypes.c_void_p]
+    lib.mdx_last_launch_geometry.restype = ctypes.c_int
+    lib.mdx_last_launch_geometry.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     for name in ("mdx_bam_error", "mdx_bam_header_text", "mdx_bam_ref_name", "mdx_bam_rg_name"):
         getattr(lib, name).restype = ctypes.c_char_p
     lib.mdx_bam_qnames.restype = ctypes.c_void_p
@@ -555,6 +558,15 @@ class DamageEngine:
         """Calls so far that bucketed their batch by library inside the launch (several libraries, a batch that did not
         bring the sorted columns: ``upload`` does)."""
         return int(self._lib.mdx_libsorts(self._ctx))
+
+    def last_launch_geometry(self):
+        """The context's last tabulation launch (``mdx_last_launch_geometry``): blocks of the grid, wavefronts per block, tiles
+        of the call's whole batch (a launch over several libraries hands out its own libraries' share of them), pools of blocks
+        that share a tile counter.  ``MDX_TEST_CUS=n`` in the environment when the engine is
+        made sizes its launches as on a device of ``n`` compute units (tests: many tiles per wavefront of a small batch)."""
+        out = np.zeros(4, np.int32)
+        self._check(self._lib.mdx_last_launch_geometry(self._ctx, _ptr(out)))
+        return dict(zip(("grid", "waves_per_block", "tiles", "pools"), (int(x) for x in out)))
 
     def rescale_timing_read(self):
         n = ctypes.c_int64(0)

@@ -119,8 +119,10 @@ def test_hip_sorted_batch_with_gap_run(mid_genome):
                                 dict(len_range=(20, 69), frac_ins=0.2, frac_del=0.2)])
 def test_hip_lists_full_in_every_round(kw, mid_genome):
     """Batches none of whose records is a plain one: every tile appends 63 entries to the wavefront's rings (the lists of
-    single insertions, single deletions, partial records; the ring of records handed to the general pass), which wrap
-    within a launch and are emptied round by round (csrc/mdx_internal.h: MDX_LIST_RING, MDX_ROUND_TILES, MDX_DRING)."""
+    single insertions, single deletions, partial records; the ring of records handed to the general pass).  At this size —
+    6 350 tiles over the 4 096 wavefronts of a whole device — a wavefront takes one or two tiles: one round, no ring wraps.
+    Rings that wrap and are emptied round by round (csrc/mdx_internal.h: MDX_LIST_RING, MDX_ROUND_TILES, MDX_DRING):
+    tests/test_gpu_few_cus.py::test_rings_wrap."""
     batch = synth.make_reads(mid_genome, 400_000, 31, read_len=100, **kw)
     libs = [("s", "l")]
     want = oracle_tableset(mid_genome, batch, libs, 70, 10, 0)
