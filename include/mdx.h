@@ -569,6 +569,22 @@ int mdx_gbam_inflate_blocks(mdx_ctx *ctx, const uint8_t *comp, int64_t comp_byte
  *   mdx_gsam_tell        byte offset of the first line of the slab mdx_gsam_next would decode.  A stream is never released
  *                        past it: a host parser can take the stream up there (mdx_source_seek) when a call fails — and the
  *                        slab handed out last stays readable until the next call.
+ * bgzip-compressed text (BGZF: the input's first gzip member carries the 'BC' extra subfield; what inflates from it does not
+ * start with "BAM\1") is taken by the same calls: mdx_gsam_open inflates the blocks the header lies in on the host, and a slab
+ * of mdx_gsam_next is then a run of whole BGZF blocks — chunk_bytes counts COMPRESSED bytes, as for mdx_gbam_next — whose
+ * compressed bytes go to HBM, where the BGZF kernels of the BAM path inflate and CRC-check them into the slab's text: the
+ * text never exists on the host.  Any BGZF layout (empty blocks, end-of-file blocks anywhere or missing, stored blocks, other
+ * extra subfields).  The last '\n' of a slab's text is found on the device; the bytes behind it — the start of a line that
+ * ends in a later block — are copied in front of the next slab's text, which is inflated at a fixed gap (up to the 32-byte
+ * boundary in front of the carried bytes the gap holds '\n': empty lines, which are no records and which the line number of
+ * mdx_gsam_error does not count).  A line may span any number of blocks and slabs.  A block that does not inflate, whose ISIZE
+ * disagrees or whose CRC32 is wrong: MDX_ERR_ARG; a later member that is not BGZF: MDX_ERR_UNSUPPORTED.
+ *   mdx_gsam_is_bgzf     1: the input is bgzip-compressed text (mdx_gsam_tell_bgzf tells its position), 0: plain text
+ *   mdx_gsam_tell_bgzf   (compressed offset of a BGZF block, inflated bytes in front of the line within it) of the first line
+ *                        of the slab mdx_gsam_next would decode — where the carried bytes START, which may be several blocks
+ *                        back —, modelled on mdx_gbam_tell.  A stream is never released past that block: a host inflater
+ *                        takes it up there (mdx_source_seek).  MDX_ERR_ARG for plain text (mdx_gsam_tell, which in turn
+ *                        refuses compressed text).
  * Lines are parsed as read_sam parses them: fewer than 11 fields (an empty line too) is no record; FLAG & 0x3FFF; RNAME the
  * header's index or -1; POS - 1; TLEN; CIGAR '*' no operations; SEQ '*' empty, upper-cased, every other symbol N; QUAL '*'
  * 0xFF per base; the last RG:Z: tag wins.  Where Python's int(), str.upper(), text decoding or ReadBatch.validate() could
@@ -591,6 +607,8 @@ int mdx_gsam_set_min_basequal(mdx_gsam *g, int32_t minqual);
 int mdx_gsam_next(mdx_gsam *g, int64_t chunk_bytes, mdx_batch *dev_view);
 int mdx_gsam_at_end(const mdx_gsam *g);
 int mdx_gsam_tell(const mdx_gsam *g, int64_t *offset);
+int mdx_gsam_is_bgzf(const mdx_gsam *g);
+int mdx_gsam_tell_bgzf(const mdx_gsam *g, int64_t *comp_off, int64_t *phase);
 /* the flag column of the view handed out last, to the host and back (--downsample), as mdx_gbam_view_flags / _set_flags */
 int mdx_gsam_view_flags(mdx_gsam *g, uint16_t *flags, int64_t n);
 int mdx_gsam_view_set_flags(mdx_gsam *g, const uint16_t *flags, int64_t n);

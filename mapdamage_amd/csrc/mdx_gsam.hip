@@ -12,6 +12,8 @@
 //                         over 32-bit words), FLAG / POS / TLEN, RNAME and the last RG:Z: through hashes of the header's
 //                         names, CIGAR operations and SEQ length counted, the line checked against what read_sam accepts
 //   gsam_fill_kernel      eight lanes per record: fixed fields, CIGAR words, SEQ (ASCII or 4-bit, -Q folded in), QUAL
+//   gsam_last_nl_kernel   (text inflated in HBM, which the host never sees) where the slab's last '\n' is: the bytes behind it
+//                         are the start of a line that ends in a later BGZF block, carried over to the next slab
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -145,6 +147,30 @@ __global__ __launch_bounds__(kBlock) void gsam_lines_kernel(const u32 *__restric
         const u32 k = (u32)__ffs(bits) - 1u;
         line_end[at++] = w * 32u + k;
         bits &= bits - 1u;
+    }
+}
+
+// The last set bit of the newline bitmap: *last = its byte offset + 1 (0, as zeroed beforehand: no newline).  A lane takes eight
+// consecutive words (two 16-byte loads; the bitmap is readable up to the next multiple of eight words), a block 64 KiB of
+// text; the block's maximum, where it has one, goes out with one atomic.
+__global__ __launch_bounds__(kBlock) void gsam_last_nl_kernel(const u32 *__restrict__ nl_bits, u32 n_words, u32 *__restrict__ last) {
+    __shared__ u32 ws[kBlock / 64];
+    const u32 w0 = (blockIdx.x * kBlock + threadIdx.x) * 8u;
+    u32 best = 0;
+    if (w0 < n_words) {
+        const uint4 *p = (const uint4 *)(nl_bits + w0);
+        const uint4 v0 = p[0], v1 = p[1];
+        const u32 x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+        for (u32 i = 0; i < 8u; i++)
+            if (w0 + i < n_words && x[i]) best = (w0 + i) * 32u + (32u - (u32)__clz(x[i]));
+    }
+    for (int o = 1; o < 64; o <<= 1) { const u32 other = (u32)__shfl_xor((int)best, o); best = other > best ? other : best; }
+    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (u32 k = 1; k < kBlock / 64; k++) best = ws[k] > best ? ws[k] : best;
+        if (best) atomicMax(last, best);
     }
 }
 
@@ -451,6 +477,11 @@ void mdx_k_gsam_classify(const uint8_t *txt, uint32_t n, uint32_t *nl_bits, uint
     if (nblk > 0)
         hipLaunchKernelGGL(gsam_classify_kernel, dim3(nblk), dim3(kBlock), 0, s, txt, n, nw, nl_bits, tab_bits, blk_nl, status);
     scan3(blk_nl, nblk, part, s);
+}
+
+void mdx_k_gsam_last_newline(const uint32_t *nl_bits, uint32_t n, uint32_t *last, hipStream_t s) {
+    const u32 nw = mdx_k_gsam_words(n);
+    if (nw > 0) hipLaunchKernelGGL(gsam_last_nl_kernel, dim3((nw + kBlock * 8u - 1u) / (kBlock * 8u)), dim3(kBlock), 0, s, nl_bits, nw, last);
 }
 
 void mdx_k_gsam_line_ends(const uint32_t *nl_bits, uint32_t n, const uint4 *blk_nl, uint32_t *line_end, hipStream_t s) {

@@ -518,6 +518,9 @@ size_t mdx_k_gsam_scan_parts(uint32_t n);      // uint4 of scratch a scan of n t
 // (txt readable up to 32 x words; blk_nl: n_blocks + 1 entries)
 void mdx_k_gsam_classify(const uint8_t *txt, uint32_t n, uint32_t *nl_bits, uint32_t *tab_bits, uint4 *blk_nl, uint4 *part, uint32_t *status,
                          hipStream_t s);
+// *last (zeroed beforehand) = the offset of the slab's last '\n' + 1, from the bitmap (nl_bits: readable up to the next
+// multiple of eight words)
+void mdx_k_gsam_last_newline(const uint32_t *nl_bits, uint32_t n, uint32_t *last, hipStream_t s);
 // ... and the newline bitmap compacted: line_end[k] = the offset of line k's '\n'
 void mdx_k_gsam_line_ends(const uint32_t *nl_bits, uint32_t n, const uint4 *blk_nl, uint32_t *line_end, hipStream_t s);
 // the field pass and the scan of its counts: cnt[line] = (records, operations, bases in front of it), cnt[n_lines] = totals

@@ -45,6 +45,7 @@ EXPORTS = (
     "mdx_source_seek", "mdx_gsam_open", "mdx_gsam_open_source", "mdx_gsam_header", "mdx_gsam_error", "mdx_gsam_configure",
     "mdx_gsam_set_seq_format", "mdx_gsam_set_min_basequal", "mdx_gsam_next", "mdx_gsam_at_end", "mdx_gsam_tell",
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
+    "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
 )
 

@@ -19,7 +19,7 @@ from .engine import BadReadError, DamageEngine, MdxError
 from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
-from .sam import BAMError
+from .sam import SAM_BGZF, SAM_GZIP, BAMError
 from .statistics import check_table_and_warn_if_dmg_freq_is_low
 
 _LOG_FORMAT = "%(asctime)s %(name)s %(levelname)s %(message)s"
@@ -362,13 +362,19 @@ def _device_path_applies(options, world=1, sam_text=True):
     """BAM files on disk; --downsample to a fraction too (the draws are made on the host from the flag column of every slab,
     reader.py:134-146) unless several ranks share the file (a rank steps over the slabs of the others without seeing their
     flags, and the stream of draws is the whole file's); a fixed number of reads is reservoir sampling over the whole file
-    (reader.py:148-164): the host's.  SAM text (``sam_text``: the tabulation pass, not --rescale-only) for one rank."""
-    from .sam import is_bam
+    (reader.py:148-164): the host's.  SAM text (``sam_text``: the tabulation pass, not --rescale-only) for one rank, plain or
+    bgzip-compressed; a plain gzip file's members have no blocks to share out among the device's lanes: the host's."""
+    from .sam import BAM, SAM_GZIP, input_format
     # (stdin and pipes as files: through the run's one Source, options.source — a stream is never opened twice)
     source = getattr(options, "source", None)
     if source is None and is_stream(options.filename):
         return False
-    bam = is_bam(source if source is not None else options.filename)
+    kind = getattr(options, "input_kind", None)
+    if kind is None:        # (sniffed once per run)
+        kind = options.input_kind = input_format(source if source is not None else options.filename)
+    if kind == SAM_GZIP:
+        return False
+    bam = kind == BAM
     return (bam or (sam_text and world == 1)) and (options.downsample is None or (options.downsample < 1 and world == 1))
 
 
@@ -522,7 +528,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         logger.warning("GPU decode path gave up: %s; decoding on the host (the whole file again)", reason)
     else:
         logger.warning("GPU decode path gave up: %s; decoding on the host (from %s offset %d on: %d records are counted)",
-                       reason, "byte" if sam_text else "compressed", carry[1] if sam_text else carry[1][0], carry[2])
+                       reason, "compressed" if isinstance(carry[1], tuple) else "byte",
+                       carry[1][0] if isinstance(carry[1], tuple) else carry[1], carry[2])
     return None, carry
 
 
@@ -632,6 +639,11 @@ def main(argv):
                         "BAM" if reader.is_bam else "SAM text")
         else:
             logger.info("Input: stdin redirected from a regular file (mapped)")
+        if reader.format == SAM_BGZF:
+            logger.info("Input: bgzip-compressed SAM text, %s", "inflated and parsed on the device"
+                        if options.gpu_decode and _device_path_applies(options, ranks.world) else "read by the host (zlib)")
+        elif reader.format == SAM_GZIP:
+            logger.info("Input: plain gzip SAM text, read by the host (a gzip member has no blocks to share out among the device's lanes)")
         if options.minqual != 0:
             logger.info("Filtering out bases with a Phred score < %d", options.minqual)
         logger.info("Writing results to '%s/'", options.folder)

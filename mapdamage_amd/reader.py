@@ -9,7 +9,8 @@ import numpy as np
 
 from . import layout as L
 from .batch import ReadBatch
-from .sam import Alignments, BamStream, BAMError, Source, input_is_stream, is_bam, read_alignments, read_sam, sam_header
+from .sam import (SAM_BGZF, SAM_GZIP, Alignments, BamStream, BAMError, Source, compressed_text, input_format, input_is_stream, is_bam,
+                  read_alignments, read_sam, sam_header)
 
 
 def is_stream(path):
@@ -66,7 +67,8 @@ class BAMReader:
         whole stream — but for -n N, which needs all of it.
         ``sam_header_only`` (the device path, ``sam.GpuSamStream``): SAM text is not parsed here — ``handle`` holds its header
         only, read without consuming a stream — and ``iter_batches`` parses the records (all of them, or a stream from
-        ``resume``, a byte offset, on) when the host has to count them after all."""
+        ``resume`` on: a byte offset, or for compressed text ``GpuSamStream.tell``'s pair) when the host has to count them
+        after all."""
         log = logging.getLogger(__name__)
         self.filepath = filepath
         self.downsample_to = downsample_to
@@ -77,7 +79,9 @@ class BAMReader:
         self._chunks = None
         if self.is_stream and not chunk_bytes:
             chunk_bytes = 256 << 20
-        self.is_bam = is_bam(src)
+        # (one of sam.BAM, SAM_TEXT, SAM_BGZF, SAM_GZIP: compressed SAM text is SAM text to everything but the decoders)
+        self.format = input_format(src)
+        self.is_bam = self.format == "BAM"
         self._sam_body = None
         if sam_header_only and not self.is_bam and (downsample_to is None or downsample_to < 1):
             header, self._sam_body = sam_header(src)
@@ -138,7 +142,12 @@ class BAMReader:
         if self._sam_body is not None:
             # SAM text the device path has not counted: the whole file, or a stream from `resume` (or its first record) on,
             # with the header read already and the run's --downsample generator
-            if self.source is not None and self.source.is_stream:
+            if self.format in (SAM_BGZF, SAM_GZIP) and (resume is not None or (self.source is not None and self.source.is_stream)):
+                # (zlib inflates from the told block on and drops what lies in front of the line; the header's lines, where
+                # they come by again, are skipped)
+                with compressed_text(self.source if self.source is not None else self.filepath, resume or (0, 0)) as text:
+                    handle = read_sam(text, header=self.handle.header)
+            elif self.source is not None and self.source.is_stream:
                 self.source.seek(self._sam_body if resume is None else resume)
                 handle = read_sam(self.source.text(), header=self.handle.header)
             else:

@@ -639,7 +639,8 @@ class GpuSamStream:
         lib = self._lib
         lib.mdx_gsam_error.restype = ctypes.c_char_p
         lib.mdx_gsam_header.restype = ctypes.c_void_p
-        for name in ("mdx_gsam_error", "mdx_gsam_header", "mdx_gsam_at_end", "mdx_gsam_missing_qualities", "mdx_gsam_close"):
+        for name in ("mdx_gsam_error", "mdx_gsam_header", "mdx_gsam_at_end", "mdx_gsam_missing_qualities", "mdx_gsam_close",
+                     "mdx_gsam_is_bgzf"):
             getattr(lib, name).argtypes = [ctypes.c_void_p]
         if isinstance(path, Source):
             rc = lib.mdx_gsam_open_source(engine._ctx, path.handle, ctypes.byref(self._g))
@@ -692,8 +693,15 @@ class GpuSamStream:
         return view
 
     def tell(self):
-        """Byte offset of the first line of the slab ``next_view`` would parse (a failed call: of the slab that failed)."""
+        """Where the first line of the slab ``next_view`` would parse starts (a failed call: of the slab that failed): a byte
+        offset for plain text; for bgzip-compressed text the pair (compressed offset of a BGZF block, inflated bytes in
+        front of the line within it) — what ``compressed_text`` and ``BAMReader.iter_batches(resume=...)`` take."""
         import ctypes
+        if self._lib.mdx_gsam_is_bgzf(self._g):
+            coff, phase = ctypes.c_int64(), ctypes.c_int64()
+            if self._lib.mdx_gsam_tell_bgzf(self._g, ctypes.byref(coff), ctypes.byref(phase)) != 0:
+                return None
+            return coff.value, phase.value
         off = ctypes.c_int64()
         if self._lib.mdx_gsam_tell(self._g, ctypes.byref(off)) != 0:
             return None
@@ -743,32 +751,46 @@ class GpuSamStream:
             pass
 
 
+def _header_run(data, complete):
+    """The leading run of '@' lines of ``data``: (its length, True if it is known to end there)."""
+    off = 0
+    while True:
+        if off >= len(data):
+            return off, complete
+        if data[off:off + 1] != b"@":
+            return off, True
+        e = data.find(b"\n", off)
+        if e < 0:
+            return (len(data), True) if complete else (off, False)
+        off = e + 1
+
+
 def sam_header(src):
     """The header of SAM text — its leading run of lines that start with '@', as ``read_sam`` reads it — and the byte
     offset of the first line behind it, without reading further: a ``Source`` is peeked (a stream keeps every byte for
-    whoever parses the body), a path is read line by line."""
-    if isinstance(src, Source):
-        n = 1 << 16
-        while True:
-            data = src.peek(n)
-            complete = len(data) < n            # (the whole input)
-            off, done = 0, False
+    whoever parses the body), a path is read line by line.  Compressed text (``input_format``): the offset counts inflated
+    bytes, and only as many compressed bytes are read (a ``Source``: peeked) as the header takes."""
+    compressed = input_format(src) in (SAM_BGZF, SAM_GZIP)
+    if isinstance(src, Source) or compressed:
+        handle = None if isinstance(src, Source) else open(src, "rb")
+        try:
+            n = 1 << 16
             while True:
-                if off >= len(data):
-                    done = complete
+                if handle is None:
+                    data = src.peek(n)
+                else:
+                    handle.seek(0)
+                    data = handle.read(n)
+                complete = len(data) < n            # (the whole input)
+                if compressed:
+                    data = _inflate_prefix(data)[0]
+                off, done = _header_run(data, complete)
+                if done:
                     break
-                if data[off:off + 1] != b"@":
-                    done = True
-                    break
-                e = data.find(b"\n", off)
-                if e < 0:
-                    if complete:
-                        off, done = len(data), True
-                    break
-                off = e + 1
-            if done:
-                break
-            n *= 2
+                n *= 2
+        finally:
+            if handle is not None:
+                handle.close()
         raw = data[:off]
     else:
         raw = b""
@@ -1006,33 +1028,185 @@ class Source:
             pass
 
 
-def is_bam(path):
-    """BGZF (BAM) or not (SAM text), by the first two bytes.  A ``Source`` is peeked; a path that is a stream
-    (``input_is_stream``) is never opened here — its bytes would be lost to the run — and must come as a ``Source``."""
-    if isinstance(path, Source):
-        return path.peek(2) == b"\x1f\x8b"
-    if input_is_stream(path):
+BAM, SAM_TEXT, SAM_BGZF, SAM_GZIP = "BAM", "SAM text", "bgzip-compressed SAM text", "plain gzip SAM text"
+
+
+def _inflate_prefix(data, want=None):
+    """(what the gzip members at the front of ``data`` — the first bytes of an input, cut anywhere — inflate to: all of it, or
+    ``want`` bytes at least where there are as many; True where bytes that do not inflate ended it).  Empty members are stepped
+    over."""
+    import zlib
+    out, rest = [], data
+    got = 0
+    while rest and (want is None or got < want):
+        z = zlib.decompressobj(31)
+        try:
+            piece = z.decompress(rest) if want is None else z.decompress(rest, max(1, want - got))
+        except zlib.error:
+            return b"".join(out), True
+        out.append(piece)
+        got += len(piece)
+        if not z.eof:
+            break
+        rest = z.unused_data
+    return b"".join(out), False
+
+
+def _bgzf_member(head):
+    """Do the bytes start a gzip member with the 'BC' extra subfield of BGZF (``fasta.is_bgzf``'s test)?"""
+    if len(head) < 12 or head[:4] != b"\x1f\x8b\x08\x04":
+        return False
+    extra = head[12:12 + int.from_bytes(head[10:12], "little")]
+    at = 0
+    while at + 4 <= len(extra):
+        size = int.from_bytes(extra[at + 2:at + 4], "little")
+        if extra[at:at + 2] == b"BC" and size == 2 and at + 6 <= len(extra):
+            return True
+        at += 4 + size
+    return False
+
+
+def input_format(path):
+    """``BAM``, ``SAM_TEXT``, ``SAM_BGZF`` or ``SAM_GZIP``, by content, as htslib sniffs through compression
+    (mapdamage/reader.py:38).  Two bytes tell uncompressed SAM text; an input that starts with 1f 8b is inflated until four
+    bytes of content have come or the input ends (empty members in front stepped over) — ``BAM\\1`` is BAM, anything else SAM
+    text, an input that inflates to nothing too; it is bgzip-compressed when the first member carries the 'BC' extra subfield
+    and plain gzip otherwise.  The one exception: first bytes that do not inflate at all are left to the BAM decoders, which
+    word what is wrong with such a file.  A ``Source`` is peeked; a path that is a stream (``input_is_stream``) is never
+    opened here — its bytes would be lost to the run — and must come as a ``Source``."""
+    if not isinstance(path, Source) and input_is_stream(path):
         raise ValueError("%r is a stream: it is read once, through a Source" % str(path))
-    with open(path, "rb") as handle:
-        return handle.read(2) == b"\x1f\x8b"
+
+    def first(n):
+        if isinstance(path, Source):
+            return path.peek(n)
+        with open(path, "rb") as handle:
+            return handle.read(n)
+
+    if first(2) != b"\x1f\x8b":
+        return SAM_TEXT
+    n = 1 << 16
+    while True:
+        data = first(n)
+        content, failed = _inflate_prefix(data, 4)
+        if len(content) >= 4 or failed or len(data) < n:
+            break
+        n *= 4
+    if content[:4] == b"BAM\x01" or (failed and not content):
+        return BAM
+    return SAM_BGZF if _bgzf_member(data) else SAM_GZIP
+
+
+def is_bam(path):
+    """BAM or not (SAM text, compressed or plain), by content (``input_format``)."""
+    return input_format(path) == BAM
+
+
+class _Inflated(io.RawIOBase):
+    """The gzip members of a compressed input — BGZF blocks or plain gzip, any number of them — inflated as they are read
+    (zlib checks every member's CRC32 and ISIZE), without the first ``drop`` inflated bytes.  ``readinto`` brings the
+    compressed bytes, from compressed offset ``base`` on; ``handle``: what to close with this.  zlib is fed a few KiB at a time
+    and rewound to where a member ended, so that small members cost no copy of everything behind them."""
+
+    PIECE = 4096
+
+    def __init__(self, name, readinto, drop=0, base=0, handle=None):
+        import zlib
+        self._name, self._readinto, self._drop, self._handle = name, readinto, int(drop), handle
+        self._z = zlib.decompressobj(31)
+        self._buf = bytearray(1 << 20)
+        self._data, self._pos, self._base = b"", 0, int(base)      # the bytes read last, how many zlib has, where they start
+        self._out = b""
+        self._member = int(base)                                    # where the current member starts
+        self._fresh, self._eof = True, False
+
+    def readable(self):
+        return True
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+        super().close()
+
+    def _more(self):
+        import zlib
+        if self._z.eof:
+            self._member = self._base + self._pos
+            self._z = zlib.decompressobj(31)
+            self._fresh = True
+        if self._pos >= len(self._data):
+            got = self._readinto(memoryview(self._buf))
+            if not got:
+                if not self._fresh:
+                    raise BAMError("%r: the gzip member at compressed offset %d is cut short" % (self._name, self._member))
+                self._eof = True
+                return b""
+            self._base += len(self._data)
+            self._data, self._pos = bytes(self._buf[:got]), 0
+        piece = self._data[self._pos:self._pos + self.PIECE]
+        self._pos += len(piece)
+        self._fresh = False
+        try:
+            out = self._z.decompress(piece)
+        except zlib.error as error:
+            raise BAMError("%r: the gzip member at compressed offset %d does not inflate or fails its CRC32 / ISIZE check (%s)"
+                           % (self._name, self._member, error)) from None
+        if self._z.eof:
+            self._pos -= len(self._z.unused_data)
+        return out
+
+    def readinto(self, view):
+        view = memoryview(view).cast("B")
+        while not self._out and not self._eof:
+            piece = self._more()
+            if self._drop:
+                cut = min(self._drop, len(piece))
+                self._drop -= cut
+                piece = piece[cut:]
+            self._out = piece
+        n = min(len(view), len(self._out))
+        view[:n] = self._out[:n]
+        self._out = self._out[n:]
+        return n
+
+
+def compressed_text(path, resume=(0, 0)):
+    """Compressed SAM text (``SAM_BGZF`` or ``SAM_GZIP``) as a text handle for ``read_sam``, inflated by zlib as it is read.
+    ``resume``: (compressed offset of a gzip member — a BGZF block —, inflated bytes to drop behind it): the text from there
+    on (``GpuSamStream.tell``; a ``Source`` that is a stream must still hold that block).  A ``Source`` is decoded as
+    ``sys.stdin`` decodes, a path as ``open(path, "rt")`` does."""
+    import sys
+    coff, drop = int(resume[0]), int(resume[1])
+    if isinstance(path, Source):
+        path.seek(coff)
+        stdin = sys.__stdin__
+        raw = _Inflated(str(path), path.readinto, drop, coff)
+        return io.TextIOWrapper(io.BufferedReader(raw, 1 << 20), encoding=getattr(stdin, "encoding", None) or "utf-8",
+                                errors=getattr(stdin, "errors", None) or "strict")
+    handle = open(path, "rb")
+    handle.seek(coff)
+    raw = _Inflated(str(path), handle.readinto, drop, coff, handle)
+    return io.TextIOWrapper(io.BufferedReader(raw, 1 << 20))
 
 
 def read_alignments(path):
-    """SAM or BAM by content (mapdamage/reader.py:38 lets htslib sniff the format).  BAM goes through
-    the native decoder of libmdx.so; the pure-Python ``read_bam`` remains as its cross-check.  ``path``: a file's, or a
+    """SAM or BAM by content (mapdamage/reader.py:38 lets htslib sniff the format, through compression too).  BAM goes through
+    the native decoder of libmdx.so; the pure-Python ``read_bam`` remains as its cross-check.  Compressed SAM text — BGZF or
+    plain gzip, any number of members — is inflated by zlib on the way into ``read_sam``.  ``path``: a file's, or a
     ``Source`` (stdin and pipes: SAM text is read through it, the sniffed bytes included)."""
-    if isinstance(path, Source):
-        if is_bam(path):
-            return read_bam_native(path)
-        return read_sam(path.text())
-    if str(path) == "-":
+    if not isinstance(path, Source) and str(path) == "-":
         import sys
         return read_sam(sys.stdin)
-    with open(path, "rb") as handle:
-        magic = handle.read(2)
-    if magic != b"\x1f\x8b":
-        return read_sam(str(path))
-    return read_bam_native(path)
+    kind = input_format(path)
+    if kind == BAM:
+        return read_bam_native(path)
+    if kind != SAM_TEXT:
+        with compressed_text(path) as handle:
+            return read_sam(handle)
+    if isinstance(path, Source):
+        return read_sam(path.text())
+    return read_sam(str(path))
 
 
 def header_text(ref_names, ref_lengths, read_groups):

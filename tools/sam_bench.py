@@ -6,9 +6,10 @@ of the command line, each under a time limit of its own:
   T_host  `python -m mapdamage_amd -i x.sam -r x.fa --host-decode ...`    the host parser (sam.read_sam)
 
 with reads/s for each (records over wall time, start-up included) and whether the tables of the three are byte-identical.
-One JSON line on stdout.
+--bgzf: the same records bgzipped (x.sam.gz, the project's BGZF writer) as three more legs — the file and the pipe inflated and
+parsed on the device, and `--host-decode` (zlib into sam.read_sam) — with the compressed size.  One JSON line on stdout.
 
-    python tools/sam_bench.py [--reads N] [--with-qual] [--dir DIR] [--timeout S] [--no-host]"""
+    python tools/sam_bench.py [--reads N] [--with-qual] [--dir DIR] [--timeout S] [--no-host] [--bgzf]"""
 import argparse
 import json
 import os
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--dir", help="where the SAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
     ap.add_argument("--timeout", type=int, default=600, help="seconds each timed step may take")
     ap.add_argument("--no-host", action="store_true", help="skip the host parser's run")
+    ap.add_argument("--bgzf", action="store_true", help="the same records bgzipped: file and pipe on the device, and --host-decode")
     args = ap.parse_args()
     import multiprocessing
 
@@ -86,6 +88,20 @@ def main():
                 ("pipe", "cat %s | %s -i -" % (path, cli + os.path.join(work, "pipe")))]
         if not args.no_host:
             runs.append(("host", cli + os.path.join(work, "host") + " --host-decode -i " + path))
+        if args.bgzf:
+            gz = path + ".gz"
+            t0 = time.perf_counter()
+            with sam.BgzfWriter(gz) as out, open(path, "rb") as text:
+                while True:
+                    piece = text.read(64 << 20)
+                    if not piece:
+                        break
+                    out.write(piece)
+            result["bgzf_bytes"], result["bgzip_s"] = os.path.getsize(gz), round(time.perf_counter() - t0, 1)
+            runs += [("bgzf_file", cli + os.path.join(work, "bgzf_file") + " -i " + gz),
+                     ("bgzf_pipe", "cat %s | %s -i -" % (gz, cli + os.path.join(work, "bgzf_pipe")))]
+            if not args.no_host:
+                runs.append(("bgzf_host", cli + os.path.join(work, "bgzf_host") + " --host-decode -i " + gz))
         status = 0
         for name, cmd in runs:
             t, rc, err = timed(cmd, args.timeout)
@@ -96,7 +112,7 @@ def main():
                 status = 1
                 break
             log = open(os.path.join(work, name, "Runtime_log.txt")).read()
-            if name != "host":
+            if not name.endswith("host"):
                 result["%s_decode_path" % name] = "device" if "Decode path: device; fallbacks from the device path: 0" in log else "host decoder"
         if status == 0:
             tables = {name: [open(os.path.join(work, name, f)).read() for f in FILES] for name, _ in runs}
