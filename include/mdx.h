@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 6   /* 6: mdx_fasta_index, mdx_set_reference_fasta, mdx_reference_fetch, mdx_host_threads, mdx_warm, mdx_*_patches_device, mdx_rescale_expand_device, mdx_mr_round, mdx_batch_fold, mdx_bgzf_deflate, mdx_gbam_rescale_slab / _write_rescaled / _record_name; 2: mdx_batch::seq_format, mdx_pack_seq, mdx_gbam_set_seq_format; 3: mdx_gbam_tell / _fixups, mdx_bam_seek; 4: mdx_batch::lowq (the struct grew by one pointer); 5: mdx_batch::libsort (another one), mdx_libsorts, mdx_gbam_view_flags / _set_flags */
+#define MDX_ABI_VERSION 6   /* 6: mdx_set_strata, mdx_strata_groups, mdx_strata_kept, mdx_finish_merged, mdx_finish_merged_host, mdx_merged_words, mdx_lgd_copies (additions only: no structure and no existing call changed, so the number stays); mdx_fasta_index, mdx_set_reference_fasta, mdx_reference_fetch, mdx_host_threads, mdx_warm, mdx_*_patches_device, mdx_rescale_expand_device, mdx_mr_round, mdx_batch_fold, mdx_bgzf_deflate, mdx_gbam_rescale_slab / _write_rescaled / _record_name; 2: mdx_batch::seq_format, mdx_pack_seq, mdx_gbam_set_seq_format; 3: mdx_gbam_tell / _fixups, mdx_bam_seek; 4: mdx_batch::lowq (the struct grew by one pointer); 5: mdx_batch::libsort (another one), mdx_libsorts, mdx_gbam_view_flags / _set_flags */
 
 #define MDX_OK 0
 #define MDX_ERR_ARG (-1)          /* bad argument / unsupported configuration */
@@ -262,6 +262,45 @@ int mdx_comm_size(const mdx_ctx *ctx);   /* 0 = no communicator attached */
  * benchmark line quotes as proof that the collective ran over that many ranks. */
 int mdx_comm_count(mdx_ctx *ctx);
 int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
+
+/* Strata: the tables per (library, group of reference sequences) in one pass.  mapDamage 2.0 keyed its tables by reference
+ * sequence as well (the `Chr` column of its misincorporation.txt); the reference snapshot merges the sequences (the hidden
+ * --merge-reference-sequences of mapdamage/config.py is all that is left of the choice), so a user who wants mitochondrion
+ * against nuclear genome, or every contig of an assembly, filters the file once per sequence.  Here a stratified context is
+ * an ordinary one created with nlib = libraries x n_groups; the table of a record is lib * n_groups + group_of_tid[tid].
+ *   mdx_set_strata     after mdx_create, before the first tabulation (MDX_ERR_STATE once records were counted; mdx_reset
+ *                      lifts that).  group_of_tid: host, n_contig entries in [0, n_groups) — n_contig the reference's number
+ *                      of sequences (checked at the first tabulation).  cfg.nlib no multiple of n_groups: MDX_ERR_ARG.
+ *                      The key is made on the device, in front of every launch, into a scratch column of the context (8 bytes
+ *                      per record); the batch's lib column — which keeps naming the LIBRARY, below cfg.nlib / n_groups — is
+ *                      not written.  A record whose library is 0xFFFF or not below the number of libraries keeps 0xFFFF:
+ *                      MDX_ERR_BAD_READ at mdx_sync if the flag filter keeps it, as in any context.  mdx_batch_upload on a
+ *                      stratified context buckets the resident batch by stratum (mdx_batch::libsort), so set the strata first.
+ *                      The fused calls (mdx_tabulate_rescale_*) count one library and refuse such a context (MDX_ERR_ARG).
+ *   mdx_strata_groups  n_groups, 0 for a context without strata
+ *   mdx_strata_kept    kept[cfg.nlib] (host): the records the flag filter (reader.py:121-132) kept, per stratum, of this
+ *                      context's batches since mdx_create / mdx_reset — the block's n_kept is one word for the whole run.
+ *                      Counted by the kernel that makes the key; synchronous.  The strata sum to n_kept.
+ * mdx_finish, mdx_finish_device and mdx_finish_allreduce need nothing new: the block holds cfg.nlib tables in stratum order.
+ *   mdx_finish_merged  d_tables (device: a block of mdx_table_words(), from mdx_finish_device or all-reduced) -> d_merged
+ *                      (device, mdx_merged_words() words, another buffer): the block of cfg.nlib / n_groups tables, the groups
+ *                      of each library summed, the two tail words copied — what the run without strata would have counted.
+ *                      Enqueued on the context's stream.  Without strata: a copy.
+ *   mdx_finish_merged_host  the same of this context's own counts into host memory (mdx_merged_words() words), for a
+ *                      caller without device buffers of its own: synchronises (deferred errors as mdx_sync), finalises and
+ *                      sums in HBM, copies the sum.
+ * Many tables: the launches take MDX_ML_MAX_LIBS (64) tables at a time, fewer on a device with fewer pools of blocks.  The
+ * dense fragment-length histogram is kept in several copies to spread its atomics (32 for a context of few tables); their
+ * number halves while the copies together would pass 1 GiB, down to one: 1 000 tables at the default lgd_max of 65 536 are
+ * 2.1 GB.  mdx_lgd_copies: how many this context has (introspection).  More than 65 535 tables: MDX_ERR_ARG from mdx_create,
+ * with a context to read the message from (the 16-bit library column names no more). */
+int mdx_set_strata(mdx_ctx *ctx, int32_t n_groups, const int32_t *group_of_tid, int32_t n_contig);
+int mdx_strata_groups(const mdx_ctx *ctx);
+int mdx_strata_kept(mdx_ctx *ctx, uint64_t *kept);
+int64_t mdx_merged_words(const mdx_ctx *ctx);
+int mdx_finish_merged(mdx_ctx *ctx, const uint64_t *d_tables, uint64_t *d_merged);
+int mdx_finish_merged_host(mdx_ctx *ctx, uint64_t *merged);
+int mdx_lgd_copies(const mdx_ctx *ctx);
 
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);

@@ -154,6 +154,14 @@ struct mdx_ctx {
     const void *libsort_checked = nullptr;   // the batch's own blob (mdx_batch::libsort) whose signature was read back last
     uint64_t libsort_checked_sig = 0;        // ... and that signature
     DevBuf ml_partials;    // ... and the plan of a launch over several libraries: which library a pool of blocks counts (MdxTabArgs::ml_plan)
+    // strata (mdx_set_strata): cfg.nlib = libraries x n_groups tables, a record's table lib * n_groups + group_of_tid[tid]
+    int n_groups = 0;              // 0: not stratified
+    int32_t *d_group_of_tid = nullptr;
+    unsigned long long *d_strata_kept = nullptr;   // [cfg.nlib]: the records the flag filter kept, per stratum
+    int strata_n_contig = 0;
+    DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
+    bool counted = false;          // records were tabulated since mdx_create / mdx_reset
+    int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
     int64_t n_fused = 0;           // fused launches so far (mdx_fused_launches)
     int64_t n_packed = 0;          // launches of the packed kernel so far (mdx_packed_launches)
@@ -203,9 +211,10 @@ int64_t comp_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * (c->cfg
 
 int zero_accumulators(mdx_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(c->d_raw, 0, (size_t)c->dims.w_total * 8, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_lgd_dense, 0, (size_t)lgd_words(c) * 8 * MDX_LGD_COPIES, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_lgd_dense, 0, (size_t)lgd_words(c) * 8 * c->lgd_copies, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_n_lgd_over, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, 8, c->stream));
+    if (c->d_strata_kept) HIP_TRY(c, hipMemsetAsync(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8, c->stream));
     return MDX_OK;
 }
 
@@ -256,7 +265,7 @@ int mdx_create(const mdx_config *cfg, mdx_ctx **out) {
     if (!cfg || !out) return MDX_ERR_ARG;
     *out = nullptr;
     if (cfg->length < 1 || cfg->around < 0 || cfg->minqual < 0 || cfg->minqual > 93 || cfg->nlib < 1 ||
-        cfg->nlib > 65535 || cfg->lgd_max < 1 || cfg->lgd_over_cap < 0)
+        cfg->lgd_max < 1 || cfg->lgd_over_cap < 0)
         return MDX_ERR_ARG;
     mdx_ctx *c = new (std::nothrow) mdx_ctx();
     if (!c) return MDX_ERR_ARG;
@@ -276,6 +285,9 @@ int mdx_create(const mdx_config *cfg, mdx_ctx **out) {
         return MDX_ERR_HIP;
     }
     *out = c;  // from here on the caller destroys it, also on error (mdx_last_error stays readable)
+    if (cfg->nlib > 65535)
+        return fail(c, MDX_ERR_ARG, "more than 65535 tables (libraries x reference groups): the 16-bit library column names "
+                                    "no more, 0xFFFF being the record without a library");
     HIP_TRY(c, hipSetDevice(cfg->device));
     hipDeviceProp_t prop;
     HIP_TRY(c, hipGetDeviceProperties(&prop, cfg->device));
@@ -330,7 +342,8 @@ int mdx_create(const mdx_config *cfg, mdx_ctx **out) {
         c->max_grid = c->n_cu * (2048 / mdx_k_block_threads());
     }
     HIP_TRY(c, hipMalloc((void **)&c->d_raw, (size_t)c->dims.w_total * 8));
-    HIP_TRY(c, hipMalloc((void **)&c->d_lgd_dense, (size_t)lgd_words(c) * 8 * MDX_LGD_COPIES));
+    c->lgd_copies = mdx_lgd_copies_for(cfg->nlib, cfg->lgd_max);
+    HIP_TRY(c, hipMalloc((void **)&c->d_lgd_dense, (size_t)lgd_words(c) * 8 * c->lgd_copies));
     HIP_TRY(c, hipMalloc((void **)&c->d_lgd_over, (size_t)(cfg->lgd_over_cap > 0 ? cfg->lgd_over_cap : 1) * 32));
     HIP_TRY(c, hipMalloc((void **)&c->d_n_lgd_over, 8));
     HIP_TRY(c, hipMalloc((void **)&c->d_err, 8));
@@ -363,6 +376,7 @@ void mdx_destroy(mdx_ctx *c) {
     c->lowq.release();
     c->libsort.release();
     c->libsort_scratch.release();
+    c->strata_key.release();
     c->ml_partials.release();
     c->rs_part.release();
     c->rs_lists.release();
@@ -372,7 +386,7 @@ void mdx_destroy(mdx_ctx *c) {
         if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
     }
     void *ptrs[] = {c->d_ref, c->d_ref4, c->d_contig_off, c->d_raw, c->d_lgd_dense, c->d_lgd_over,
-                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr};
+                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_strata_kept};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -529,17 +543,32 @@ static int ascii_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out) {
 // What a blob of mdx_k_libsort was laid out for, in the spare word of its header: the layout is a function of the batch's
 // sizes and of the libraries of the context that built it — a resident batch handed to a context of another nlib, or a
 // sub-view of it, would be read through the wrong offsets.
-static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, int nlib) {
+// (a stratified context's blob is ordered by stratum: its groups are part of the signature)
+static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, int nlib, int n_groups) {
     uint64_t h = 0x9E3779B97F4A7C15ull;
-    for (uint64_t v : {(uint64_t)n, (uint64_t)n_cigar, (uint64_t)n_bases, (uint64_t)nlib}) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; }
+    for (uint64_t v : {(uint64_t)n, (uint64_t)n_cigar, (uint64_t)n_bases, (uint64_t)nlib | (uint64_t)n_groups << 32}) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; }
     return h | 1ull;
 }
+// A stratified context (mdx_set_strata): *out = the device batch b with the key column — library x groups + group of the
+// record's sequence — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
+// stream; valid until the next such call).  count: the kept records are added to the context's counts per stratum.
+static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool count) {
+    *out = *b;
+    if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
+    HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
+    mdx_k_strata_key(b->n_reads, b->flag, b->lib, b->tid, c->d_group_of_tid, c->strata_n_contig, c->n_groups, c->cfg.nlib / c->n_groups,
+                     (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    out->lib = (const uint16_t *)c->strata_key.p;
+    return MDX_OK;
+}
+
 // A device batch with a 4-bit SEQ column (either form), ordered by library, into `blob` (mdx_k_libsort_bytes; enqueued on
 // the stream)
 static int build_libsort(mdx_ctx *c, const mdx_batch *b, void *blob) {
     MdxLibSort ls;
     mdx_k_libsort_layout(blob, b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, &ls);
-    const uint64_t sig = libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib);
+    const uint64_t sig = libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->n_groups);
     HIP_TRY(c, hipMemcpyAsync((char *)blob + 8, &sig, 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, c->libsort_scratch.reserve(mdx_k_libsort_scratch_bytes(b->n_reads, c->cfg.nlib)));
     mdx_k_libsort(b->n_reads, b->n_cigar, b->n_bases, b->flag, b->lib, b->tid, b->pos, b->tlen, b->cigar_off, b->cigar, b->seq_off, b->seq,
@@ -600,7 +629,11 @@ int mdx_batch_upload(mdx_ctx *c, const mdx_batch *h, mdx_batch *dv) {
         HIP_TRY(c, hipMalloc(&p, mdx_k_libsort_bytes(n, h->n_cigar, h->n_bases, c->cfg.nlib)));
         dv->libsort = (const uint8_t *)p;
         // (a record with a library the context does not know has no place: the blob remembers the first, the launches report it)
-        rc = build_libsort(c, dv, p);
+        // (a stratified context: ordered by stratum)
+        mdx_batch keyed;
+        rc = strata_view(c, dv, &keyed, false);
+        if (rc != MDX_OK) return rc;
+        rc = build_libsort(c, &keyed, p);
         if (rc != MDX_OK) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -666,6 +699,21 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     // launch's timed region.  (MDX_NO_ML=1 in the environment: one launch per library, each over all records, for A/B runs)
     static const bool no_ml = [] { const char *e = getenv("MDX_NO_ML"); return e && *e && *e != '0'; }();
     const bool ml = packed && !fuse && c->cfg.nlib > 1 && !no_ml;
+    // A stratified context: the launches read the key column in place of the batch's lib column — all of them but the launch
+    // over a batch that brings its own columns bucketed by stratum, which reads neither
+    mdx_batch b_key;
+    if (c->n_groups > 0) {
+        if (fuse) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
+        if (c->strata_n_contig != c->n_contig)
+            return fail(c, MDX_ERR_ARG, "mdx_set_strata named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
+                                        std::to_string(c->n_contig));
+        if (!(ml && b_in->libsort)) {
+            rc = strata_view(c, b_in, &b_key, true);
+            if (rc != MDX_OK) return rc;
+            b_in = &b_key;
+        }
+    }
+    c->counted = true;
     mdx_batch b_ascii;
     const mdx_batch *b = b_in;
     if (!packed) {
@@ -688,6 +736,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     a.partials = c->d_partials;
     a.raw = c->d_raw;
     a.lgd_dense = c->d_lgd_dense;
+    a.lgd_copies = c->lgd_copies;
     a.lgd_over = c->d_lgd_over;
     a.lgd_over_cap = c->cfg.lgd_over_cap;
     a.n_lgd_over = c->d_n_lgd_over;
@@ -850,7 +899,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
                     c->libsort_checked = blob;
                     c->libsort_checked_sig = sig;
                 }
-                if (c->libsort_checked_sig != libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib))
+                if (c->libsort_checked_sig != libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->n_groups))
                     return fail(c, MDX_ERR_ARG, "mdx_batch::libsort was built for another batch or a context with another number of libraries: "
                                                 "upload the batch with the context that tabulates it, whole");
             }
@@ -865,6 +914,8 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
             }
             MdxLibSort ls;
             mdx_k_libsort_layout(const_cast<void *>(blob), b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, &ls);
+            // (strata, a batch that brings its buckets: their sizes are the kept records per stratum — no key kernel has counted them)
+            if (c->n_groups > 0 && b->libsort && lo == 0) mdx_k_strata_kept_from_sort(ls.lib_start, c->cfg.nlib, c->d_strata_kept, c->stream);
             a.flag = ls.flag; a.tid = ls.tid; a.pos = ls.pos; a.tlen = ls.tlen;
             a.cigar_off = ls.cigar_off; a.cigar = ls.cigar; a.seq_off = ls.seq_off; a.seq = ls.seq;
             a.perm = ls.perm; a.lib_start = ls.lib_start; a.sort_bad = ls.bad;
@@ -1021,7 +1072,7 @@ int64_t mdx_table_words(const mdx_ctx *c) {
 int mdx_finish_device(mdx_ctx *c, uint64_t *d_tables) {
     if (!c || !d_tables) return MDX_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    mdx_k_finalize(c->d_raw, c->d_lgd_dense, c->d_n_lgd_over, c->dims, (unsigned long long *)d_tables, c->stream);
+    mdx_k_finalize(c->d_raw, c->d_lgd_dense, c->d_n_lgd_over, c->dims, c->lgd_copies, (unsigned long long *)d_tables, c->stream);
     HIP_TRY(c, hipGetLastError());
     return MDX_OK;
 }
@@ -1189,6 +1240,80 @@ int mdx_reset(mdx_ctx *c) {
     if (rc != MDX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->err.clear();
+    c->counted = false;
+    return MDX_OK;
+}
+
+int mdx_set_strata(mdx_ctx *c, int32_t n_groups, const int32_t *group_of_tid, int32_t n_contig) {
+    if (!c) return MDX_ERR_ARG;
+    if (n_groups < 1 || n_contig < 1 || !group_of_tid) return fail(c, MDX_ERR_ARG, "set_strata: bad arguments");
+    if (c->cfg.nlib % n_groups != 0)
+        return fail(c, MDX_ERR_ARG, "set_strata: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of " +
+                                    std::to_string(n_groups) + " groups (create it with nlib = libraries x groups)");
+    for (int32_t t = 0; t < n_contig; t++)
+        if (group_of_tid[t] < 0 || group_of_tid[t] >= n_groups)
+            return fail(c, MDX_ERR_ARG, "set_strata: the group of sequence " + std::to_string(t) + " is outside [0, n_groups)");
+    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata: records have been counted already (mdx_reset first)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->d_group_of_tid) { (void)hipFree(c->d_group_of_tid); c->d_group_of_tid = nullptr; }
+    c->n_groups = 0;
+    HIP_TRY(c, hipMalloc((void **)&c->d_group_of_tid, (size_t)n_contig * 4));
+    HIP_TRY(c, hipMemcpy(c->d_group_of_tid, group_of_tid, (size_t)n_contig * 4, hipMemcpyHostToDevice));
+    if (!c->d_strata_kept) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
+        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
+    }
+    c->n_groups = n_groups;
+    c->strata_n_contig = n_contig;
+    return MDX_OK;
+}
+
+int mdx_strata_groups(const mdx_ctx *c) { return c ? c->n_groups : 0; }
+
+int mdx_strata_kept(mdx_ctx *c, uint64_t *kept) {
+    if (!c || !kept) return MDX_ERR_ARG;
+    if (c->n_groups <= 0) return fail(c, MDX_ERR_STATE, "strata_kept: mdx_set_strata has not been called");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(kept, c->d_strata_kept, (size_t)c->cfg.nlib * 8, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+int mdx_lgd_copies(const mdx_ctx *c) { return c ? c->lgd_copies : 0; }
+
+int64_t mdx_merged_words(const mdx_ctx *c) {
+    if (!c) return 0;
+    const int64_t g = c->n_groups > 0 ? c->n_groups : 1;
+    return (mis_words(c) + comp_words(c) + lgd_words(c)) / g + 2;
+}
+
+int mdx_finish_merged_host(mdx_ctx *c, uint64_t *merged) {
+    if (!c || !merged) return MDX_ERR_ARG;
+    int rc = mdx_sync(c, nullptr);
+    if (rc != MDX_OK) return rc;
+    const int64_t words = mdx_table_words(c), m_words = mdx_merged_words(c);
+    uint64_t *d = nullptr;      // [block | merged block]
+    HIP_TRY(c, hipMalloc((void **)&d, (size_t)(words + m_words) * 8));
+    rc = mdx_finish_device(c, d);
+    if (rc == MDX_OK) rc = mdx_finish_merged(c, d, d + words);
+    if (rc == MDX_OK) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(merged, d + words, (size_t)m_words * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, MDX_ERR_HIP, hipGetErrorString(e));
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+int mdx_finish_merged(mdx_ctx *c, const uint64_t *d_tables, uint64_t *d_merged) {
+    if (!c || !d_tables || !d_merged) return MDX_ERR_ARG;
+    if (d_tables == d_merged) return fail(c, MDX_ERR_ARG, "finish_merged: the merged block needs a buffer of its own");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const int g = c->n_groups > 0 ? c->n_groups : 1;
+    mdx_k_merge_strata((const unsigned long long *)d_tables, (unsigned long long *)d_merged, c->cfg.nlib / g, g,
+                       (int64_t)4 * c->cfg.length * MDX_N_MIS_COLS, (int64_t)4 * (c->cfg.length + c->cfg.around) * 4,
+                       (int64_t)4 * c->cfg.lgd_max, c->stream);
+    HIP_TRY(c, hipGetLastError());
     return MDX_OK;
 }
 
@@ -1421,6 +1546,7 @@ static int tabulate_rescale_impl(mdx_ctx *c, const mdx_batch *b_in, const int32_
     // one pass over one resident batch: the tables and, from the same columns in HBM, the rescaled qualities
     int rc = check_batch(c, b_in);
     if (rc != MDX_OK) return rc;
+    if (c->n_groups > 0) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
     // (the fused kernel copies the quality column in 16-byte units: both columns at the same 16-byte phase — true of any two
     // device allocations; patch mode: no second column)
     const bool args_ok = c->d_ref && c->d_lut && b_in->qual && d_mtid && d_mpos && d_mr_raw && d_status &&

@@ -103,6 +103,15 @@ static inline __host__ __device__ int mdx_stage_entries(const MdxDims &d) {
 // blockIdx & (copies - 1), finalize_kernel sums them) — a paired-end library with 350 bp inserts put every
 // second record on a few hundred words of a single copy: 0.73 ms instead of 0.13 ms per 2 M records
 #define MDX_LGD_COPIES 32
+// ... as many of them as a context's tables leave room for (a power of two, MdxTabArgs::lgd_copies): all 32 while they stay
+// within MDX_LGD_COPIES_BYTES together, then halved, down to one — a context of a thousand tables (libraries x reference groups,
+// mdx_set_strata) at the default lgd_max of 65 536 holds 2.1 GB per copy
+#define MDX_LGD_COPIES_BYTES ((int64_t)1 << 30)
+static inline int mdx_lgd_copies_for(int nlib, int lgd_max) {
+    int copies = MDX_LGD_COPIES;
+    while (copies > 1 && (int64_t)copies * nlib * 4 * lgd_max * 8 > MDX_LGD_COPIES_BYTES) copies >>= 1;
+    return copies;
+}
 
 static inline MdxDims mdx_make_dims(int L, int A, int nlib, int lgd_max, int lgd_lds) {
     MdxDims d;
@@ -201,7 +210,8 @@ struct MdxTabArgs {
     // accumulators
     uint32_t *partials;              // [grid][w_total] (LDS mode)
     unsigned long long *raw;         // [w_total] u64 (global-atomic mode writes here directly)
-    unsigned long long *lgd_dense;   // [MDX_LGD_COPIES][nlib_total][2][2][lgd_max] (+ the launch's first library)
+    unsigned long long *lgd_dense;   // [lgd_copies][nlib_total][2][2][lgd_max] (+ the launch's first library)
+    int lgd_copies;                  // a power of two, at most MDX_LGD_COPIES (mdx_lgd_copies_for)
     long long *lgd_over;             // [cap][4]
     long long lgd_over_cap;
     unsigned long long *n_lgd_over;
@@ -352,8 +362,21 @@ void mdx_k_libsort(int64_t n, int64_t n_cigar, int64_t n_bases, const uint16_t *
                    const int32_t *pos, const int32_t *tlen, const uint32_t *cigar_off, const uint32_t *cigar, const uint32_t *seq_off,
                    const uint8_t *seq4, int nlib, void *scratch, const MdxLibSort &out, hipStream_t s);
 void mdx_k_finalize(const unsigned long long *raw, const unsigned long long *lgd_dense,
-                    const unsigned long long *n_lgd_over, MdxDims d, unsigned long long *out,
+                    const unsigned long long *n_lgd_over, MdxDims d, int lgd_copies, unsigned long long *out,
                     hipStream_t s);
+// ---- strata (mdx_set_strata; mdx_libsort.hip): the table index of a record in a context of n_libraries x n_groups tables,
+// key[i] = lib[i] * n_groups + group_of_tid[tid[i]] — 0xFFFF where the library is not below n_libraries (no or unknown read
+// group: the tabulation kernels report it if they count the record); a tid outside [0, n_contig) takes group 0 (the kernels
+// report that one too)
+// kept[key] += 1 for every record the flag filter keeps (kept == null: the key only); mdx_k_strata_kept_from_sort: the same
+// counts from the buckets of a batch sorted by stratum
+void mdx_k_strata_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *group_of_tid, int n_contig,
+                      int n_groups, int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
+void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
+// a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
+// n_libraries tables, the groups of each library summed
+void mdx_k_merge_strata(const unsigned long long *in, unsigned long long *out, int n_libraries, int n_groups, int64_t w_mis,
+                        int64_t w_comp, int64_t w_lgd, hipStream_t s);
 void mdx_k_genome_comp(const uint8_t *ref, const int64_t *contig_off, int n_contig, unsigned long long *out,
                        hipStream_t s);
 

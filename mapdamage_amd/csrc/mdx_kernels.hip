@@ -2358,7 +2358,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     if (flen < d.lgd_lds) {
                         lkey = lbase + d.off_lgd() + (kind * 2 + rev) * d.lgd_lds + (int)flen;
                     } else if (flen < d.lgd_max) {
-                        atomicAdd(&p.lgd_dense[(i64)(blockIdx.x & (MDX_LGD_COPIES - 1)) * ((i64)a.nlib_total * 4 * d.lgd_max) +
+                        atomicAdd(&p.lgd_dense[(i64)(blockIdx.x & (a.lgd_copies - 1)) * ((i64)a.nlib_total * 4 * d.lgd_max) +
                                                (((i64)lg_lib * 2 + kind) * 2 + rev) * d.lgd_max + flen], 1ull);
                     } else {
                         const u64 slot = atomicAdd(p.n_lgd_over, 1ull);
@@ -3180,7 +3180,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     if (__ballot(counts && flen >= (u32)d.lgd_lds)) {          // (a tile in five at the survey's insert sizes)
                         if (counts && flen >= (u32)d.lgd_lds) {
                             if (flen < (u32)d.lgd_max) {
-                                atomicAdd(&p.lgd_dense[(i64)(blockIdx.x & (MDX_LGD_COPIES - 1)) * ((i64)a.nlib_total * 4 * d.lgd_max) +
+                                atomicAdd(&p.lgd_dense[(i64)(blockIdx.x & (a.lgd_copies - 1)) * ((i64)a.nlib_total * 4 * d.lgd_max) +
                                                        ((i64)lg_lib * 4 + krow) * d.lgd_max + flen], 1ull);
                             } else {
                                 const u64 slot = atomicAdd(p.n_lgd_over, 1ull);
@@ -3825,7 +3825,7 @@ void mdx_k_reduce_partials(const uint32_t *partials, unsigned long long *raw, un
 // raw (reference orientation) -> canonical tables (mapdamage_amd/layout.py):
 //   out = [ mis nlib*2*2*L*25 | comp nlib*2*2*(L+A)*4 | lgd nlib*2*2*lgd_max | n_kept | n_lgd_over ]
 __global__ void finalize_kernel(const u64 *__restrict__ raw, const u64 *__restrict__ lgd_dense,
-                                const u64 *__restrict__ n_lgd_over, MdxDims d, u64 *__restrict__ out) {
+                                const u64 *__restrict__ n_lgd_over, MdxDims d, int lgd_copies, u64 *__restrict__ out) {
     const int L = d.L, A = d.A;
     const i64 n_mis = (i64)d.nlib * 2 * 2 * L * 25;
     const i64 n_comp = (i64)d.nlib * 2 * 2 * (L + A) * 4;
@@ -3900,7 +3900,7 @@ __global__ void finalize_kernel(const u64 *__restrict__ raw, const u64 *__restri
             const int strand = x % 2; x /= 2;
             const int kind = x % 2; x /= 2;
             v = 0;
-            for (int c = 0; c < MDX_LGD_COPIES; c++) v += lgd_dense[(i64)c * n_lgd + (i - n_mis - n_comp)];
+            for (int c = 0; c < lgd_copies; c++) v += lgd_dense[(i64)c * n_lgd + (i - n_mis - n_comp)];
             if (len < d.lgd_lds) v += raw[x * d.w_lib + d.off_lgd() + (kind * 2 + strand) * d.lgd_lds + len];
         } else if (i == total - 2) {
             v = raw[d.w_total - 1];
@@ -3912,9 +3912,9 @@ __global__ void finalize_kernel(const u64 *__restrict__ raw, const u64 *__restri
 }
 
 void mdx_k_finalize(const unsigned long long *raw, const unsigned long long *lgd_dense,
-                    const unsigned long long *n_lgd_over, MdxDims d, unsigned long long *out,
+                    const unsigned long long *n_lgd_over, MdxDims d, int lgd_copies, unsigned long long *out,
                     hipStream_t s) {
-    hipLaunchKernelGGL(finalize_kernel, dim3(512), dim3(256), 0, s, raw, lgd_dense, n_lgd_over, d, out);
+    hipLaunchKernelGGL(finalize_kernel, dim3(512), dim3(256), 0, s, raw, lgd_dense, n_lgd_over, d, lgd_copies, out);
 }
 
 // Genome base composition (mapdamage/composition.py:6-25 over seqtk.c:79-104): per-contig counts of

@@ -374,3 +374,86 @@ void mdx_k_libsort(int64_t n, int64_t n_cigar, int64_t n_bases, const uint16_t *
     const u32 seq_words = (u32)((((size_t)seq4 & 3) + ((size_t)n_bases + 1) / 2 + 3) / 4);
     hipLaunchKernelGGL(libsort_copy_kernel, dim3(cgrid), dim3(64 * LS_COPY_WAVES), 0, s, kept_p, sc.src_co, sc.src_so, cigar, seq32, ph, seq_words, out);
 }
+
+// ---- strata: a key column in front of the launch, and the sum over a library's groups behind mdx_finish_device
+
+// The caller's lib column is const and a decoder's view is read again by the caller: the key goes to a scratch column of the
+// context.  10 bytes per record — flag, tid and lib in, a key out — against the 240 the tabulation moves.  On the way the
+// records the flag filter keeps (reader.py:121-132) are counted per stratum: the tables hold one count of kept reads for the
+// run, not one per table.  A block takes STRATA_KEY_PER consecutive records and counts in the LDS (up to LS_LDS_LIBS strata;
+// beyond: global atomics).
+#define STRATA_KEY_PER 4096
+__global__ __launch_bounds__(256) void strata_key_kernel(i64 n, const u16 *__restrict__ flag, const u16 *__restrict__ lib,
+                                                         const int32_t *__restrict__ tid, const int32_t *__restrict__ group_of_tid,
+                                                         int n_contig, int n_groups, int n_libraries, u16 *__restrict__ key,
+                                                         u64 *__restrict__ kept) {
+    __shared__ u32 h[LS_LDS_LIBS];
+    const int n_strata = n_libraries * n_groups;
+    const bool in_lds = n_strata <= LS_LDS_LIBS;
+    if (in_lds) {
+        for (int l = threadIdx.x; l < n_strata; l += 256) h[l] = 0u;
+        __syncthreads();
+    }
+    const i64 lo = (i64)blockIdx.x * STRATA_KEY_PER, hi = lo + STRATA_KEY_PER < n ? lo + STRATA_KEY_PER : n;
+    for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
+        const u32 lb = lib[i], fl = flag[i];
+        const int32_t t = tid[i];
+        u32 k = 0xFFFFu;
+        if (lb < (u32)n_libraries) k = lb * (u32)n_groups + (t >= 0 && t < n_contig ? (u32)group_of_tid[t] : 0u);
+        key[i] = (u16)k;
+        if (kept && k != 0xFFFFu && !(fl & 0xF04u)) {
+            if (in_lds) atomicAdd(&h[k], 1u);
+            else atomicAdd(&kept[k], 1ull);
+        }
+    }
+    if (in_lds && kept) {
+        __syncthreads();
+        for (int l = threadIdx.x; l < n_strata; l += 256)
+            if (h[l]) atomicAdd(&kept[l], (u64)h[l]);
+    }
+}
+
+void mdx_k_strata_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *group_of_tid, int n_contig,
+                      int n_groups, int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(strata_key_kernel, dim3((unsigned)((n + STRATA_KEY_PER - 1) / STRATA_KEY_PER)), dim3(256), 0, s, (i64)n, flag, lib, tid,
+                       group_of_tid, n_contig, n_groups, n_libraries, key, (u64 *)kept);
+}
+
+// ... and for a batch that brings its columns bucketed by stratum (mdx_batch::libsort): the sizes of the buckets
+__global__ void strata_kept_from_sort_kernel(const u32 *__restrict__ lib_start, int n_strata, u64 *__restrict__ kept) {
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < n_strata) kept[l] += (u64)(lib_start[l + 1] - lib_start[l]);
+}
+void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s) {
+    hipLaunchKernelGGL(strata_kept_from_sort_kernel, dim3((n_strata + 255) / 256), dim3(256), 0, s, lib_start, n_strata, (u64 *)kept);
+}
+
+// out word i of section [n_libraries][w] = the sum over g of in word [(library * n_groups + g)][w]; the two tail words
+// (kept records, out-of-range lengths) are the run's and are copied
+__global__ __launch_bounds__(256) void merge_strata_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, int n_libraries, int n_groups,
+                                                           i64 w_mis, i64 w_comp, i64 w_lgd) {
+    const i64 nl = n_libraries, ns = (i64)n_libraries * n_groups;
+    const i64 o_comp = nl * w_mis, o_lgd = o_comp + nl * w_comp, o_tail = o_lgd + nl * w_lgd;
+    const i64 i_comp = ns * w_mis, i_lgd = i_comp + ns * w_comp, i_tail = i_lgd + ns * w_lgd;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < o_tail + 2; i += (i64)gridDim.x * blockDim.x) {
+        if (i >= o_tail) { out[i] = in[i_tail + (i - o_tail)]; continue; }
+        i64 w, base_in, x;
+        if (i < o_comp) { w = w_mis; base_in = 0; x = i; }
+        else if (i < o_lgd) { w = w_comp; base_in = i_comp; x = i - o_comp; }
+        else { w = w_lgd; base_in = i_lgd; x = i - o_lgd; }
+        const i64 l = x / w, r = x - l * w;
+        u64 v = 0;
+        for (int g = 0; g < n_groups; g++) v += in[base_in + (l * n_groups + g) * w + r];
+        out[i] = v;
+    }
+}
+
+void mdx_k_merge_strata(const unsigned long long *in, unsigned long long *out, int n_libraries, int n_groups, int64_t w_mis,
+                        int64_t w_comp, int64_t w_lgd, hipStream_t s) {
+    const i64 total = (i64)n_libraries * (w_mis + w_comp + w_lgd) + 2;
+    i64 blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(merge_strata_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const u64 *)in, (u64 *)out, n_libraries, n_groups,
+                       (i64)w_mis, (i64)w_comp, (i64)w_lgd);
+}

@@ -47,6 +47,7 @@ EXPORTS = (
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
     "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
+    "mdx_set_strata", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -180,6 +181,14 @@ def load_library(path=None):
     lib.mdx_bam_read_source.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mdx_bam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mdx_gbam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_set_strata.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_strata_groups.argtypes = [ctypes.c_void_p]
+    lib.mdx_strata_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_merged_words.restype = ctypes.c_int64
+    lib.mdx_merged_words.argtypes = [ctypes.c_void_p]
+    lib.mdx_finish_merged.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_finish_merged_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_lgd_copies.argtypes = [ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -245,7 +254,15 @@ class DamageEngine:
     """Device-side counterpart of MisincorporationRates + DNAComposition + FragmentLengths.
 
     ``libraries``: list of (sample, library) tuples indexed by the ``lib`` column (unique
-    libraries in header order, or ``[("*", "*")]`` for --merge-libraries)."""
+    libraries in header order, or ``[("*", "*")]`` for --merge-libraries).
+
+    ``groups``: names of groups of reference sequences — the engine then keeps one table set per (library, group), a
+    *stratum* (include/mdx.h ``mdx_set_strata``): ``set_strata(group_of_tid)`` says which group each sequence of the
+    header belongs to, the batches keep naming the library in their ``lib`` column, and ``finish()`` returns a
+    ``tables.StratifiedTables``.  ``libraries`` then holds one entry per stratum, library-major (``base_libraries`` the
+    caller's list)."""
+
+    MAX_TABLES = 65535      # the 16-bit library column, 0xFFFF being the record without a library
 
     # the form in which ``upload`` / ``tabulate`` hand a host batch's SEQ column over when the caller does not say
     # (False: ASCII as it stands, True: packed to 4 bits first); the tests run every parity case through both
@@ -253,9 +270,18 @@ class DamageEngine:
     default_packed = os.environ.get("MDX_SEQ_4BIT", "") == "1"
 
     def __init__(self, libraries, length=70, around=10, minqual=0, lgd_max=65536, device=0,
-                 lgd_over_cap=1 << 20):
+                 lgd_over_cap=1 << 20, groups=None):
+        self.base_libraries = [tuple(x) for x in libraries]
+        self.groups = None if groups is None else [str(g) for g in groups]
+        if self.groups is not None and not self.groups:
+            raise ValueError("groups: at least one group of reference sequences")
+        n_tables = len(self.base_libraries) * (len(self.groups) if self.groups is not None else 1)
+        if n_tables > self.MAX_TABLES:
+            raise ValueError("%d libraries x %d reference groups = %d tables; the 16-bit library column names at most %d"
+                             % (len(self.base_libraries), len(self.groups or [None]), n_tables, self.MAX_TABLES))
         self._lib = load_library()
-        self.libraries = [tuple(x) for x in libraries]
+        self._strata_set = False
+        self.libraries = [lib for lib in self.base_libraries for _ in (self.groups or [None])]
         self.length, self.around, self.minqual, self.lgd_max = length, around, minqual, lgd_max
         self.lgd_over_cap = lgd_over_cap
         cfg = MdxConfig(length, around, minqual, len(self.libraries), lgd_max, device, lgd_over_cap)
@@ -305,6 +331,25 @@ class DamageEngine:
         self._check(self._lib.mdx_set_stream(self._ctx, ctypes.c_void_p(hip_stream or 0)))
 
     # ------------------------------------------------------------------ inputs
+    def set_strata(self, group_of_tid):
+        """``group_of_tid[t]``: index into ``groups`` of sequence ``t`` of the header (include/mdx.h ``mdx_set_strata``);
+        before the first ``tabulate`` / ``upload``."""
+        if self.groups is None:
+            raise ValueError("set_strata: the engine was made without groups")
+        m = np.ascontiguousarray(group_of_tid, dtype=np.int32)
+        self._check(self._lib.mdx_set_strata(self._ctx, ctypes.c_int32(len(self.groups)), _ptr(m), ctypes.c_int32(m.shape[0])))
+        self._strata_set = True
+
+    def strata_kept(self):
+        """Records the flag filter kept, per stratum (library-major), of this engine's batches (``mdx_strata_kept``)."""
+        kept = np.zeros(len(self.libraries), np.uint64)
+        self._check(self._lib.mdx_strata_kept(self._ctx, _ptr(kept)))
+        return kept
+
+    def lgd_copies(self):
+        """Copies of the dense fragment-length histogram this context keeps (``mdx_lgd_copies``; tests)."""
+        return int(self._lib.mdx_lgd_copies(self._ctx))
+
     def set_reference(self, ref):
         """``ref``: a ``Reference`` (contigs in host memory) or a ``fasta.FastaOnDisk`` — the FASTA file itself, which the
         library sends to HBM as it lies on disk and strips of its line ends there (``mdx_set_reference_fasta``)."""
@@ -460,6 +505,11 @@ class DamageEngine:
     def finish(self) -> TableSet:
         """Synchronise and fetch the canonical tables (main.py:229-231 reads them next).  With a communicator
         attached (``comm_init``) the call is collective and returns the totals over all ranks."""
+        if self.groups is not None:
+            return self._finish_strata()
+        return self._finish_block()
+
+    def _finish_block(self):
         if not self.comm_size:
             self.sync()
         nlib, Ln, A = len(self.libraries), self.length, self.around
@@ -478,6 +528,21 @@ class DamageEngine:
         self._check(rc)
         return TableSet(self.libraries, Ln, A, mis, comp, lgd, over[:n_over.value].copy(),
                         n_kept.value)
+
+    def _finish_strata(self):
+        """The block of all strata and — summed on the device, ``mdx_finish_merged_host`` — the block of the libraries."""
+        from .tables import StratifiedTables, unpack_words
+        if not self._strata_set:
+            raise ValueError("finish: set_strata has not been called")
+        if self.comm_size:
+            raise ValueError("finish of a stratified engine with a communicator attached: reduce the block "
+                             "(finish_allreduce) and split it with tables.StratifiedTables.from_block")
+        strata = self._finish_block()
+        out = StratifiedTables.from_block(strata, self.base_libraries, self.groups, self.strata_kept())
+        merged = np.zeros(int(self._lib.mdx_merged_words(self._ctx)), np.uint64)
+        self._check(self._lib.mdx_finish_merged_host(self._ctx, _ptr(merged)))
+        out.merged = unpack_words(merged, self.base_libraries, self.length, self.around, self.lgd_max, out.merged.lgd_over)
+        return out
 
     def lgd_overflow_only(self):
         """Out-of-range fragment-length records of this context (used after an all-reduce)."""

@@ -120,6 +120,14 @@ def build_parser():
     g.add_argument("--freq-files", action="store_true",
                    help="EXPERIMENTAL: also write 5pCtoT_freq.txt / 3pGtoA_freq.txt (mapDamage 2.0-2.2 outputs that "
                         "this reference snapshot no longer produces; format unpinned)")
+    g.add_argument("--by-reference", action="store_true",
+                   help="also tabulate every reference sequence of the header on its own, in the same pass: the usual three files "
+                        "are what the run writes without the option, and by_reference/ holds groups.tsv and the three files of each "
+                        "sequence in a directory named by its index (not a reference option: mapdamage/config.py has none; "
+                        "mapDamage 2.0 printed a Chr column for this)")
+    g.add_argument("--reference-groups", type=Path, metavar="TSV",
+                   help="like --by-reference for groups of sequences: lines 'sequence name<TAB>group name'; the sequences not "
+                        "listed form a last group named '*' (not a reference option either)")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -144,6 +152,10 @@ def parse_args(argv):
         parser.error("plotting and the Bayesian estimation are not part of this engine; run them with the "
                      "reference on the emitted tables (--rescale-only works from an existing "
                      "Stats_out_MCMC_correct_prob.csv)")
+    if o.by_reference and o.reference_groups:
+        parser.error("--by-reference and --reference-groups exclude each other")
+    if (o.by_reference or o.reference_groups) and o.rescale_only:
+        parser.error("--by-reference / --reference-groups belong to the tabulation pass; --rescale-only counts nothing")
     if o.rescale_only and not o.folder:
         parser.error("--folder required when using --rescale-only")
     if not o.filename:
@@ -274,15 +286,32 @@ class _Ranks:
             import torch
             dev = torch.device("cuda", self.device)
             distributed.agree_on_error(error, dev)
-            return distributed.reduce_engine_tables(engine, dev)
+            return self._strata(engine, distributed.reduce_engine_tables(engine, dev), dev)
         own = None
         if error is None:
             try:
                 own = engine.finish()
+                if engine.groups is not None:
+                    own = own.strata
             except (BadReadError, MdxError) as exc:
                 error = exc
         distributed.agree_on_error(error)
-        return distributed.reduce_tableset(own, engine.lgd_max)
+        return self._strata(engine, distributed.reduce_tableset(own, engine.lgd_max), None)
+
+    @staticmethod
+    def _strata(engine, block, device):
+        """The summed block of a stratified engine (its layout is the one of any block: ``nlib`` tables in stratum order)
+        split by group, with the kept reads per stratum summed over the ranks as well."""
+        if engine.groups is None:
+            return block
+        import torch
+        from .distributed import allreduce_words
+        from .tables import StratifiedTables
+        kept = torch.from_numpy(engine.strata_kept().view(np.int64).copy())
+        if device is not None:
+            kept = kept.to(device)
+        kept = allreduce_words(kept).cpu().numpy().view(np.uint64)
+        return StratifiedTables.from_block(block, engine.base_libraries, engine.groups, kept)
 
     def close(self):
         if self.world > 1:
@@ -303,6 +332,31 @@ def launch_command(argv, gpus):
             "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "mapdamage_amd"] + keep
 
 
+def reference_strata(options, references):
+    """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, or None."""
+    from .tables import groups_by_reference, parse_reference_groups
+    if options.by_reference:
+        return groups_by_reference(references)
+    if options.reference_groups:
+        return parse_reference_groups(Path(options.reference_groups).read_text(), references)
+    return None
+
+
+def _make_engine(options, libraries, device):
+    """The run's engine; with --by-reference / --reference-groups one table set per (library, group) — the input routes
+    hand it the same batches either way."""
+    strata = getattr(options, "strata", None)
+    engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=device,
+                          groups=None if strata is None else strata[0])
+    if strata is not None:
+        try:
+            engine.set_strata(strata[1])
+        except Exception:
+            engine.close()
+            raise
+    return engine
+
+
 def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None):
     """The records decoded on the host (native BGZF/BAM decoder or SAM text), uploaded batch by batch.
     ``carry``: (engine, resume position, records counted so far, --downsample generator or None) of a device decode that
@@ -311,8 +365,7 @@ def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None
     import contextlib
     with contextlib.ExitStack() as stack:
         if carry is None:
-            engine = stack.enter_context(DamageEngine(libraries, options.length, options.around, options.minqual,
-                                                      device=ranks.device))
+            engine = stack.enter_context(_make_engine(options, libraries, ranks.device))
             engine.set_reference(ref)
             n_reads, resume, rand = 0, None, None
         else:
@@ -414,7 +467,7 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     else:
         readgroups = [(rg, libraries.index(lib)) for rg, lib in reader._readgroups.items()]
         lib_default = None
-    engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=ranks.device)
+    engine = _make_engine(options, libraries, ranks.device)
     stages.mark("engine")
     carry = None
     try:
@@ -629,6 +682,17 @@ def main(argv):
         else:
             logger.info("Reference: plain gzip FASTA, read by the host (Python reader)")
         libraries = reader.get_libraries()
+        try:
+            options.strata = reference_strata(options, list(reader.handle.header.references))
+        except (ValueError, OSError) as error:
+            logger.error("%s", error)
+            return 1
+        if options.strata is not None:
+            logger.info("Tabulating %d groups of reference sequences x %d libraries in one pass", len(options.strata[0]), len(libraries))
+            if len(options.strata[0]) * len(libraries) > DamageEngine.MAX_TABLES:
+                logger.error("%d groups of reference sequences x %d libraries: more than the %d tables a run can keep",
+                             len(options.strata[0]), len(libraries), DamageEngine.MAX_TABLES)
+                return 1
         stages.mark("headers and index")
 
         logger.info("Reading from '%s'", options.filename)
@@ -661,7 +725,12 @@ def main(argv):
         stages.mark("tables")
         if not first:
             return 0
-        tables.write(options.folder)
+        if options.strata is not None:
+            # the three usual files from the sum over the groups, and by_reference/ beside them
+            tables.write(options.folder, options.strata[1])
+            tables = tables.merged
+        else:
+            tables.write(options.folder)
         if options.freq_files:
             (options.folder / "5pCtoT_freq.txt").write_text(tables.damage_frequency_text("5p", options.readplot))
             (options.folder / "3pGtoA_freq.txt").write_text(tables.damage_frequency_text("3p", options.readplot))

@@ -161,3 +161,117 @@ def merge_library_ids(libraries):
             uniq.append(lib)
         remap.append(index[lib])
     return uniq, np.asarray(remap, dtype=np.uint16)
+
+
+# ---------------------------------------------------------------------- strata: tables per (library, reference group)
+CATCH_ALL_GROUP = "*"
+
+
+def parse_reference_groups(text, references):
+    """``--reference-groups FILE``: lines ``sequence name<TAB>group name``.  Returns (group names, group_of_tid): groups
+    numbered in order of first appearance in the file; the sequences of ``references`` (the header's, tid order) that the
+    file does not list go to a last group named ``*``.  A listed name the header lacks, a sequence listed twice, a line
+    without two columns: ValueError naming it.  Empty lines and lines starting with ``#`` are skipped."""
+    index = {name: tid for tid, name in enumerate(references)}
+    names, number, group_of_tid = [], {}, [-1] * len(references)
+    for lineno, line in enumerate(text.splitlines(), 1):
+        line = line.rstrip("\r")
+        if not line.strip() or line.startswith("#"):
+            continue
+        cols = line.split("\t")
+        if len(cols) != 2 or not cols[0] or not cols[1]:
+            raise ValueError("reference groups, line %d: expected 'sequence name<TAB>group name', found %r" % (lineno, line))
+        seq, group = cols
+        if seq not in index:
+            raise ValueError("reference groups, line %d: the header has no sequence named %r" % (lineno, seq))
+        if group == CATCH_ALL_GROUP:
+            raise ValueError("reference groups, line %d: the group name %r is taken by the sequences the file does not list"
+                             % (lineno, CATCH_ALL_GROUP))
+        if group_of_tid[index[seq]] >= 0:
+            raise ValueError("reference groups, line %d: sequence %r is listed twice" % (lineno, seq))
+        if group not in number:
+            number[group] = len(names)
+            names.append(group)
+        group_of_tid[index[seq]] = number[group]
+    if any(g < 0 for g in group_of_tid):
+        names.append(CATCH_ALL_GROUP)
+        group_of_tid = [len(names) - 1 if g < 0 else g for g in group_of_tid]
+    return names, np.asarray(group_of_tid, dtype=np.int32)
+
+
+def groups_by_reference(references):
+    """``--by-reference``: every sequence of the header its own group."""
+    return [str(r) for r in references], np.arange(len(references), dtype=np.int32)
+
+
+@dataclass
+class StratifiedTables:
+    """What a stratified ``DamageEngine.finish()`` returns: ``strata`` — the block as the device holds it, one table per
+    (library, group), library-major —, ``group(g)`` — the ``TableSet`` of group ``g`` over the libraries —, and ``merged`` —
+    the groups of each library summed: the tables of the run without strata.  ``kept``: records the flag filter kept, per
+    stratum (``DamageEngine.strata_kept``; the block itself counts them once for the whole run)."""
+    libraries: list
+    groups: list
+    strata: TableSet
+    kept: np.ndarray = None
+    merged: TableSet = None
+
+    @classmethod
+    def from_block(cls, strata, libraries, groups, kept=None):
+        libraries = [tuple(x) for x in libraries]
+        nl, ng = len(libraries), len(groups)
+        assert strata.mis.shape[0] == nl * ng, (strata.mis.shape, nl, ng)
+        kept = np.zeros(nl * ng, np.uint64) if kept is None else np.asarray(kept, np.uint64).reshape(nl * ng)
+        out = cls(libraries, [str(g) for g in groups], strata, kept)
+        over = strata.lgd_over.copy()
+        if over.shape[0]:
+            over[:, 0] //= ng
+        out.merged = TableSet(libraries, strata.length, strata.around, out._split(strata.mis).sum(axis=1, dtype=np.uint64),
+                              out._split(strata.comp).sum(axis=1, dtype=np.uint64), out._split(strata.lgd).sum(axis=1, dtype=np.uint64),
+                              over, strata.n_kept)
+        return out
+
+    @property
+    def n_kept(self):
+        return self.strata.n_kept
+
+    def _split(self, a):
+        return a.reshape((len(self.libraries), len(self.groups)) + a.shape[1:])
+
+    def group_kept(self, g):
+        return int(self._split(self.kept)[:, g].sum())
+
+    def group(self, g):
+        """The tables of group ``g`` (index or name), indexed by library."""
+        if not isinstance(g, (int, np.integer)):
+            g = self.groups.index(g)
+        ng = len(self.groups)
+        s = self.strata
+        over = s.lgd_over[s.lgd_over[:, 0] % ng == g].copy() if s.lgd_over.shape[0] else s.lgd_over.copy()
+        if over.shape[0]:
+            over[:, 0] //= ng
+        return TableSet(self.libraries, s.length, s.around, self._split(s.mis)[:, g].copy(), self._split(s.comp)[:, g].copy(),
+                        self._split(s.lgd)[:, g].copy(), over, self.group_kept(g))
+
+    def groups_text(self, group_of_tid):
+        """``groups.tsv``: index, group name, number of sequences, kept reads."""
+        n_seq = np.bincount(np.asarray(group_of_tid, dtype=np.int64), minlength=len(self.groups))
+        out = io.StringIO()
+        out.write("Index\tGroup\tSequences\tReads\n")
+        for g, name in enumerate(self.groups):
+            out.write("%d\t%s\t%d\t%d\n" % (g, name, int(n_seq[g]), self.group_kept(g)))
+        return out.getvalue()
+
+    def write(self, folder, group_of_tid):
+        """The run's three files into ``folder`` from the merged block, and ``folder/by_reference``: ``groups.tsv`` and
+        one directory per group, named by its index (sequence names hold ``*``, ``:`` and ``/``), with the three files of
+        that group written by the same emitters."""
+        import pathlib
+        folder = pathlib.Path(folder)
+        self.merged.write(folder)
+        sub = folder / "by_reference"
+        sub.mkdir(parents=True, exist_ok=True)
+        (sub / "groups.tsv").write_text(self.groups_text(group_of_tid))
+        for g in range(len(self.groups)):
+            (sub / str(g)).mkdir(exist_ok=True)
+            self.group(g).write(sub / str(g))
