@@ -579,14 +579,15 @@ int mdx_gsam_open_source(mdx_ctx *ctx, mdx_source *source, mdx_gsam **out) {
             g->pos = off;
         }
         // (sam.Header parses it in Python: the references here must be the same list — text decoding and str.splitlines() are
-        // Python's, so anything they could read otherwise is left to the host)
+        // Python's, so anything they could read otherwise is left to the host; so is a NUL, at which the header text that
+        // mdx_bam_header_text hands to Python ends)
         std::vector<std::string> names;
         std::vector<int64_t> lengths;
         std::unordered_set<std::string> seen;
         for (const char ch : text)
-            if ((unsigned char)ch >= 0x80 || ch == '\r' || ch == '\v' || ch == '\f' || (ch >= 0x1c && ch <= 0x1e)) {
+            if ((unsigned char)ch >= 0x80 || ch == '\0' || ch == '\r' || ch == '\v' || ch == '\f' || (ch >= 0x1c && ch <= 0x1e)) {
                 g->head = mdx_bam_header_only(text, names, lengths);
-                g->error = "a SAM header byte the host parser reads (>= 0x80 or a line separator other than '\\n')";
+                g->error = "a SAM header byte the host parser reads (NUL, >= 0x80 or a line separator other than '\\n')";
                 return MDX_ERR_UNSUPPORTED;
             }
         size_t a = 0;
