@@ -376,6 +376,9 @@ int64_t mdx_fused_launches(const mdx_ctx *ctx);
  * one per call whatever the number of libraries — up to 64 libraries per launch, MDX_ML_MAX_LIBS, and as many as the
  * launch has pools of two blocks). */
 int64_t mdx_packed_launches(const mdx_ctx *ctx);
+/* ... and those of them that ran the packed kernel compiled for the default geometry: --length 70 --around 10, one library,
+ * no --min-basequal (MDX_NO_GEO_SPEC=1 in the environment: none — the kernel that takes its geometry from its arguments). */
+int64_t mdx_geo_spec_launches(const mdx_ctx *ctx);
 /* Calls so far that bucketed their batch by library themselves (several libraries, a batch without mdx_batch::libsort). */
 int64_t mdx_libsorts(const mdx_ctx *ctx);
 /* The geometry of the context's last tabulation launch (introspection for tests; all zero before the first): out[0] blocks of

@@ -19,7 +19,7 @@
 
 namespace {
 
-constexpr size_t kLdsLimit = 160 * 1024;  // MI355X: 160 KiB LDS per CU
+constexpr size_t kLdsLimit = MDX_LDS_LIMIT;  // MI355X: 160 KiB LDS per CU
 #ifdef MDX_WAVE_CLK
 static unsigned long long *g_dbg_clk = nullptr;
 extern "C" int mdx_dbg_clk_read(unsigned long long *out, int n) {
@@ -39,7 +39,6 @@ extern "C" int mdx_dbg_phase_read(unsigned long long *out, int reset) {
     return rc;
 }
 #endif
-constexpr int kLgdLds = 256;           // fragment lengths below this are counted in the LDS
 
 struct DevBuf {
     void *p = nullptr;
@@ -165,6 +164,7 @@ struct mdx_ctx {
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
     int64_t n_fused = 0;           // fused launches so far (mdx_fused_launches)
     int64_t n_packed = 0;          // launches of the packed kernel so far (mdx_packed_launches)
+    int64_t n_geo_spec = 0;        // ... those of them that ran the kernel compiled for the default geometry (mdx_geo_spec_launches)
     int64_t fuse_list_cap = 0;     // entries per list of rs_in (the last fused launch)
     int32_t last_geom[4] = {0, 0, 0, 0};   // the last tabulation launch: blocks, wavefronts per block, tiles of the batch, pools (mdx_last_launch_geometry)
     void *pin[2] = {nullptr, nullptr};
@@ -304,12 +304,10 @@ int mdx_create(const mdx_config *cfg, mdx_ctx **out) {
     c->stream = c->own_stream;
     lap("context, stream");
 
-    int lgd_lds = cfg->lgd_max < kLgdLds ? cfg->lgd_max : kLgdLds;
     // two blocks per CU need half of the LDS each: the short-fragment histogram gives way first (lengths beyond it
     // take the dense histogram's global atomics) — at --length 70 --around 10 it ends up at 226 entries instead of 256
-    while (lgd_lds > 128 && mdx_k_lds_bytes(mdx_make_dims(cfg->length, cfg->around, 1, cfg->lgd_max, lgd_lds)) > kLdsLimit / 2 &&
-           mdx_k_lds_bytes(mdx_make_dims(cfg->length, cfg->around, 1, cfg->lgd_max, 128)) <= kLdsLimit / 2)
-        lgd_lds -= 2;
+    // (mdx_k_lgd_lds: the function the kernel compiled for the default geometry takes its own lgd_lds from)
+    const int lgd_lds = mdx_k_lgd_lds(cfg->length, cfg->around, cfg->lgd_max);
     if ((int64_t)cfg->nlib * (4LL * cfg->length * 29 + 8LL * (2LL * cfg->around + 512) +
                               4LL * lgd_lds + 128) > 0x7FFFFFF0LL || cfg->length > (1 << 24) || cfg->around > (1 << 24))
         return fail(c, MDX_ERR_ARG, "table too large (nlib * length)");
@@ -943,7 +941,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
             if (fused_grid) *fused_grid = grid;
         } else if (packed) {
             if (pmask) mdx_k_tabulate_packed_masked(a, grid, c->pk.threads, lds, c->stream);
-            else mdx_k_tabulate_packed(a, grid, c->pk.threads, lds, c->stream);
+            else if (mdx_k_tabulate_packed(a, grid, c->pk.threads, lds, c->stream)) c->n_geo_spec++;
             c->n_packed++;
         } else {
             mdx_k_tabulate(a, c->mode, mask, grid, lds, c->stream);
@@ -1673,6 +1671,7 @@ int mdx_rescale_host(mdx_ctx *c, const mdx_batch *h, const int32_t *mtid, const 
 
 int64_t mdx_fused_launches(const mdx_ctx *c) { return c ? c->n_fused : -1; }
 int64_t mdx_packed_launches(const mdx_ctx *c) { return c ? c->n_packed : -1; }
+int64_t mdx_geo_spec_launches(const mdx_ctx *c) { return c ? c->n_geo_spec : -1; }
 int64_t mdx_libsorts(const mdx_ctx *c) { return c ? c->n_libsorts : -1; }
 int mdx_last_launch_geometry(const mdx_ctx *c, int32_t out[4]) {
     if (!c || !out) return MDX_ERR_ARG;

@@ -96,7 +96,7 @@ static inline __host__ __device__ unsigned mdx_n_pools(unsigned grid) {
 #define MDX_POOL_CHUNK 24  // consecutive tiles a pool of two blocks takes at a time (the fast kernels' hand-out of tiles)
 #endif
 // staging entries (16 B) per wavefront: a tile of 64 - 64 % R records and the R - 1 entries that pad its last step
-static inline __host__ __device__ int mdx_stage_entries(const MdxDims &d) {
+static constexpr inline __host__ __device__ int mdx_stage_entries(const MdxDims &d) {
     return d.R > 0 ? 64 - 64 % d.R + d.R - 1 : 64;
 }
 // copies of the dense fragment-length histogram (lengths >= lgd_lds take global atomics: a block adds to copy
@@ -113,8 +113,9 @@ static inline int mdx_lgd_copies_for(int nlib, int lgd_max) {
     return copies;
 }
 
-static inline MdxDims mdx_make_dims(int L, int A, int nlib, int lgd_max, int lgd_lds) {
-    MdxDims d;
+// (constexpr: the kernel compiled for the default geometry — MDX_GEO_*, below — derives its constants with it)
+static constexpr inline __host__ __device__ MdxDims mdx_make_dims(int L, int A, int nlib, int lgd_max, int lgd_lds) {
+    MdxDims d{};
     d.L = L; d.A = A; d.nlib = nlib; d.lgd_max = lgd_max; d.lgd_lds = lgd_lds;
     d.nl8 = (L + A + 7) / 8;
     d.G = 2 * d.nl8;
@@ -263,8 +264,19 @@ struct MdxTabArgs {
 
 enum { MDX_MODE_LDS = 0, MDX_MODE_GLOBAL = 1 };
 
+#define MDX_LDS_LIMIT (160 * 1024)     // MI355X: 160 KiB LDS per CU
+#define MDX_LGD_LDS_MAX 256            // fragment lengths below this are counted in the LDS ...
+// The default geometry — mapDamage's --length 70 --around 10, one library, the lgd_lds a context of that geometry gets —, for
+// which the plain packed one-library kernel is compiled a second time with every dimension and image offset a constant
+// (tabulate_kernel<.., GEO>, mdx_k_tabulate_packed)
+#define MDX_GEO_L 70
+#define MDX_GEO_A 10
+
 int mdx_k_block_threads();
 size_t mdx_k_lds_bytes(const MdxDims &d);
+// ... as many of them as leave the ASCII kernels' image of one library within half of the LDS — two blocks per CU — (at
+// --length 70 --around 10: 226), never fewer than 128 for that
+int mdx_k_lgd_lds(int L, int A, int lgd_max);
 int mdx_k_stage_off(const MdxDims &d);
 int mdx_k_queue_off(const MdxDims &d);
 hipError_t mdx_k_prepare(size_t lds_bytes);
@@ -315,7 +327,7 @@ int mdx_k_pk_pfl_off(const MdxDims &d, int threads);
 size_t mdx_k_pk_lds_bytes(const MdxDims &d, const MdxPkConfig &k);
 // records of a tile of the fast kernels: a multiple of R (the ASCII kernels' steps); at most 63 where the columns are
 // prefetched (a record's end offsets are its neighbour's start offsets: lane 63 brings the last one)
-static inline __host__ __device__ int mdx_tile_records(const MdxDims &d, bool pfl) {
+static constexpr inline __host__ __device__ int mdx_tile_records(const MdxDims &d, bool pfl) {
     const int t = d.R > 0 ? 64 - 64 % d.R : 64;
     return pfl && t > 63 ? 63 : t;
 }
@@ -327,7 +339,9 @@ void mdx_k_tabulate_packed_masked(const MdxTabArgs &a, int grid, int threads, si
 // seq4_out may be seq4_in
 void mdx_k_fold_mask(const uint8_t *seq4_in, uint8_t *seq4_out, const uint8_t *qual, const uint8_t *lowq, int64_t n_bases, int minqual,
                      hipStream_t s);
-void mdx_k_tabulate_packed(const MdxTabArgs &a, int grid, int threads, size_t lds_bytes, hipStream_t s);
+// (true: the launch was the kernel compiled for the default geometry — every value that one has folded equals what this
+// launch passes; MDX_NO_GEO_SPEC=1 in the environment: never, for A/B runs and the tests)
+bool mdx_k_tabulate_packed(const MdxTabArgs &a, int grid, int threads, size_t lds_bytes, hipStream_t s);
 void mdx_k_tabulate(const MdxTabArgs &a, int mode, bool mask, int grid, size_t lds_bytes, hipStream_t s);
 void mdx_k_tabulate_fused(const MdxTabArgs &a, int grid, size_t lds_bytes, hipStream_t s);
 // (tile_ctr, if not null and w_total >= 4096: 4096 words zeroed on the way — the next launch's tile counters)

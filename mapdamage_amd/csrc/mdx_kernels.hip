@@ -204,11 +204,24 @@ __constant__ u8 c_comp_col[25] = {3, 2, 1, 0, 5, 4, 7, 6, 12, 13, 14, 15, 8,
 
 int mdx_k_block_threads() { return MDX_BLOCK; }
 // LDS image: [tables w_total words, padded to 16 B][staging, 12 x mdx_stage_entries x 16 B][event queues, 12 x EVQ_BYTES]
-int mdx_k_stage_off(const MdxDims &d) { return (int)((d.w_total + 3) / 4 * 4); }
-int mdx_k_queue_off(const MdxDims &d) { return mdx_k_stage_off(d) + (MDX_BLOCK / 64) * mdx_stage_entries(d) * 4; }
+// (the layout as constexpr functions, mdx_c_*: the kernel compiled for the default geometry folds them, the mdx_k_* the host
+// calls are the same functions)
+static constexpr int mdx_c_stage_off(const MdxDims &d) { return (int)((d.w_total + 3) / 4 * 4); }
+static constexpr int mdx_c_queue_off(const MdxDims &d) { return mdx_c_stage_off(d) + (MDX_BLOCK / 64) * mdx_stage_entries(d) * 4; }
+int mdx_k_stage_off(const MdxDims &d) { return mdx_c_stage_off(d); }
+int mdx_k_queue_off(const MdxDims &d) { return mdx_c_queue_off(d); }
 // ... [byte-mask table: 9 x u64, entry n = the low n bytes set; PK: 17 x u64, entry n = the low n nibbles set]
 #define LT_BYTES 136
-size_t mdx_k_lds_bytes(const MdxDims &d) { return (size_t)mdx_k_queue_off(d) * 4 + (size_t)(MDX_BLOCK / 64) * EVQ_BYTES + LT_BYTES; }
+static constexpr size_t mdx_c_lds_bytes(const MdxDims &d) { return (size_t)mdx_c_queue_off(d) * 4 + (size_t)(MDX_BLOCK / 64) * EVQ_BYTES + LT_BYTES; }
+size_t mdx_k_lds_bytes(const MdxDims &d) { return mdx_c_lds_bytes(d); }
+static constexpr int mdx_c_lgd_lds(int L, int A, int lgd_max) {
+    int lgd_lds = lgd_max < MDX_LGD_LDS_MAX ? lgd_max : MDX_LGD_LDS_MAX;
+    while (lgd_lds > 128 && mdx_c_lds_bytes(mdx_make_dims(L, A, 1, lgd_max, lgd_lds)) > MDX_LDS_LIMIT / 2 &&
+           mdx_c_lds_bytes(mdx_make_dims(L, A, 1, lgd_max, 128)) <= MDX_LDS_LIMIT / 2)
+        lgd_lds -= 2;
+    return lgd_lds;
+}
+int mdx_k_lgd_lds(int L, int A, int lgd_max) { return mdx_c_lgd_lds(L, A, lgd_max); }
 // The fused tabulate + rescale kernel (tabulate_kernel<.., RS>): one block of 1024 threads per CU — 16 wavefronts with
 // 128 registers each instead of 24 with 80 (measured with the plain kernel: +3 % on config 3) — because its image does
 // not fit twice: behind the plain image [second TC table, 256-byte aligned][4 words][lookup table][terms]
@@ -252,11 +265,25 @@ int mdx_k_fuse_block_threads() { return MDX_FUSE_BLOCK; }
 #define MDX_PK_WPS 4
 #endif
 int mdx_k_pk_blocks_per_cu(int threads) { return MDX_PK_WPS * 256 / threads; }
-int mdx_k_pk_queue_off(const MdxDims &d, int threads) { return mdx_k_stage_off(d) + (threads / 64) * mdx_stage_entries(d) * 4; }
+static constexpr int mdx_c_pk_queue_off(const MdxDims &d, int threads) { return mdx_c_stage_off(d) + (threads / 64) * mdx_stage_entries(d) * 4; }
+int mdx_k_pk_queue_off(const MdxDims &d, int threads) { return mdx_c_pk_queue_off(d, threads); }
 // (behind the queues and the two tables, 16-byte aligned)
-int mdx_k_pk_pfl_off(const MdxDims &d, int threads) {
-    return (int)((((size_t)mdx_k_pk_queue_off(d, threads) * 4 + (size_t)(threads / 64) * MDX_PK_EVQ_BYTES + LT_BYTES + MDX_PK_TAB_BYTES + 15) & ~(size_t)15) / 4);
+static constexpr int mdx_c_pk_pfl_off(const MdxDims &d, int threads) {
+    return (int)((((size_t)mdx_c_pk_queue_off(d, threads) * 4 + (size_t)(threads / 64) * MDX_PK_EVQ_BYTES + LT_BYTES + MDX_PK_TAB_BYTES + 15) & ~(size_t)15) / 4);
 }
+int mdx_k_pk_pfl_off(const MdxDims &d, int threads) { return mdx_c_pk_pfl_off(d, threads); }
+// The default geometry (MDX_GEO_L, MDX_GEO_A: one library, a block of MDX_PK_BLOCK threads with the prefetch areas) as
+// constants — what tabulate_kernel<.., GEO = 1> has folded, and what mdx_k_tabulate_packed compares a launch with.
+// (lgd_max is not among them: the kernel reads it from its arguments; any lgd_max that leaves lgd_lds where it is will do)
+struct MdxGeo {
+    static constexpr MdxDims dims = mdx_make_dims(MDX_GEO_L, MDX_GEO_A, 1, 0, mdx_c_lgd_lds(MDX_GEO_L, MDX_GEO_A, 1 << 16));
+    static constexpr int threads = MDX_PK_BLOCK;
+    static constexpr int stage_off = mdx_c_stage_off(dims);
+    static constexpr int queue_off = mdx_c_pk_queue_off(dims, threads);
+    static constexpr int pfl_off = mdx_c_pk_pfl_off(dims, threads);
+    static constexpr size_t lds_bytes = (size_t)pfl_off * 4 + (size_t)(threads / 64) * MDX_PFL_WAVE_BYTES;
+};
+static_assert(MdxGeo::dims.nl8 > 0 && MdxGeo::lds_bytes <= MDX_LDS_LIMIT, "the default geometry runs the packed kernel in one block of MDX_PK_BLOCK threads");
 size_t mdx_k_pk_lds_bytes(const MdxDims &d, const MdxPkConfig &k) {
     if (k.pfl) return (size_t)mdx_k_pk_pfl_off(d, k.threads) * 4 + (size_t)(k.threads / 64) * MDX_PFL_WAVE_BYTES;
     return (size_t)mdx_k_pk_queue_off(d, k.threads) * 4 + (size_t)(k.threads / 64) * MDX_PK_EVQ_BYTES + LT_BYTES + MDX_PK_TAB_BYTES;
@@ -758,20 +785,33 @@ void mdx_k_unpack_seq(const u8 *d_packed, u8 *d_ascii, int64_t n, hipStream_t s)
 //     the pools of a one-library launch share the batch's, and the reduction adds a block's image to the tables of its pool's
 //     library.  (Until the end of round 5 every block went through all libraries, an epoch each: 8 libraries 1.27 x the
 //     one-library launch; now 1.03 x.)
-template <bool USE_LDS, bool MASK, bool FAST, bool RS = false, bool PK = false, bool ML = false>
+// GEO: the geometry is the default one, compiled in (MdxGeo: --length 70 --around 10, one library from library 0, a block of
+//     MDX_PK_BLOCK threads with the prefetch areas) — dimensions, table and image offsets, the block and the library base are
+//     constants instead of kernel arguments held in (and spilled from) scalar registers.  The plain packed one-library kernel
+//     only; the launch checks that what it would have passed is what was folded (mdx_k_tabulate_packed).
+template <bool USE_LDS, bool MASK, bool FAST, bool RS = false, bool PK = false, bool ML = false, int GEO = 0>
 __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOCK), RS ? MDX_FUSE_WPS : (PK ? MDX_PK_WPS : MDX_WPS)) void tabulate_kernel(MdxTabArgs a) {
+    static_assert(!GEO || (PK && !MASK && !RS && !ML), "the default geometry is compiled into the plain packed one-library kernel only");
+    constexpr bool GEOC = GEO != 0;
     static_assert(!RS || (USE_LDS && FAST && !MASK), "the fused kernel is the unmasked fast LDS kernel");
     static_assert(!PK || (USE_LDS && FAST), "the packed kernel is the fast LDS kernel (plain, with the fused rescaling, or with --min-basequal)");
     static_assert(!ML || (PK && !RS), "a library per pool: the packed kernels (plain and --min-basequal)");
     // (the packed kernels: the launch's own block, 512 or 1024 threads — MdxPkConfig)
-    const int BLOCK = RS ? MDX_FUSE_BLOCK : (PK ? (int)blockDim.x : MDX_BLOCK);
+    const int BLOCK = RS ? MDX_FUSE_BLOCK : (PK ? (GEOC ? MdxGeo::threads : (int)blockDim.x) : MDX_BLOCK);
     // pfl: the phase-1 columns of a tile come out of the wavefront's prefetch area in the LDS (see the tile loop) — the packed
     // kernels but the fused one (its image has no room for the areas)
     constexpr bool PFLC = PK && !RS;
     constexpr bool pfl = PFLC;
     extern __shared__ __attribute__((aligned(16))) u32 lds[];
-    const MdxDims d = a.dims;
+    // (GEO: every dimension a constant but lgd_max, which stays the launch's)
+    constexpr MdxDims geo_d = MdxGeo::dims;
+    MdxDims d_ = GEOC ? geo_d : a.dims;
+    if (GEOC) d_.lgd_max = a.dims.lgd_max;
+    const MdxDims d = d_;
     const int L = d.L, A = d.A;
+    // the image offsets and the launch's first library (GEO: constants)
+    const int k_stage_off = GEOC ? MdxGeo::stage_off : a.stage_off, k_queue_off = GEOC ? MdxGeo::queue_off : a.queue_off,
+              k_pfl_off = GEOC ? MdxGeo::pfl_off : a.pfl_off, k_lib_lo = GEOC ? 0 : a.lib_lo;
     const int lane = threadIdx.x & 63;
     // (wave-uniform, and told so: the staging and queue addresses derived from it live in scalar registers)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -801,7 +841,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     // nine-entry LDS table of byte masks (entry n = the low n bytes of a 64-bit word set): the per-record byte masks
     // of the partial steps are two or three lookups instead of 64-bit shifts
     const int QCAP = RS ? a.rs.qcap : EVQ_CAP;      // events of the ASCII kernels' queue (20 bytes each)
-    u64 *const ltab = (u64 *)((u8 *)(lds + a.queue_off) + (BLOCK / 64) * (PK ? MDX_PK_EVQ_BYTES : QCAP * 20));
+    u64 *const ltab = (u64 *)((u8 *)(lds + k_queue_off) + (BLOCK / 64) * (PK ? MDX_PK_EVQ_BYTES : QCAP * 20));
     // RS: the fused records count into a TC table of their own (the reference bases of their columns are part of the
     // rescale summary, rescale.py:142-143), added to the first one at block end; behind it four words for those counts,
     // the lookup table and the terms of the model
@@ -918,11 +958,11 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     // complete records first, {rfL, sq, nq | nbefore << 16 | nafter << 24,
     //                          TC base bytes [17:8] | library [29:24] | has qualities [30] | reverse strand [31]};
     // phase 2 reads the entry of its slot with one ds_read_b128 (no v_readlane broadcast).
-    uint4 *const stg = (uint4 *)(lds + a.stage_off) + wave * mdx_stage_entries(d);
+    uint4 *const stg = (uint4 *)(lds + k_stage_off) + wave * mdx_stage_entries(d);
     // Rare-event queue (wave-private, LDS): the lanes holding a byte that is not a plain match append
     // {read 8 bytes, reference 8 bytes, record word | lane << 18 | masked-quality flags [7:0]}; the queue is
     // drained completely, 64 events in parallel, whenever the next step might not fit.
-    u32x2 *const qS = (u32x2 *)((u8 *)(lds + a.queue_off) + wave * (QCAP * 20));
+    u32x2 *const qS = (u32x2 *)((u8 *)(lds + k_queue_off) + wave * (QCAP * 20));
     u32x2 *const qR = qS + QCAP;
     u32 *const qW = (u32 *)(qR + QCAP);
     // RS: a step that finds the queue too full for a step's worth of events does nothing and says so (count()); the run
@@ -939,14 +979,14 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     // Nothing in a run stores to global memory: with a store possibly pending the compiler waits for vmcnt(0) at the head
     // of the pipelined loop — loads and stores share the counter and may retire out of order — instead of for the oldest
     // step's loads only.
-    uint4 *const qQ = (uint4 *)(lds + a.queue_off + (PK ? wave * (MDX_PK_EVQ_BYTES / 4) : 0));
+    uint4 *const qQ = (uint4 *)(lds + k_queue_off + (PK ? wave * (MDX_PK_EVQ_BYTES / 4) : 0));
     u32 *const qE = (u32 *)(qQ + MDX_PK_QCAP);
     // (their LDS addresses: the dynamic LDS starts at address 0)
     typedef __attribute__((address_space(3))) u32x4 lds_u4;
     typedef __attribute__((address_space(3))) u32 lds_u1;
     const u32 qQ_a = (u32)(size_t)(lds_u4 *)qQ, qE_a = qQ_a + 16u * MDX_PK_QCAP;
     // the wavefront's prefetch area (MdxTabArgs::pfl_off): [column][lane] dwords
-    const u32 pfl_a = PFLC ? (u32)__builtin_amdgcn_readfirstlane((int)((u32)(size_t)(lds_u1 *)(lds + a.pfl_off) + (u32)wave * (u32)MDX_PFL_WAVE_BYTES)) : 0u;
+    const u32 pfl_a = PFLC ? (u32)__builtin_amdgcn_readfirstlane((int)((u32)(size_t)(lds_u1 *)(lds + k_pfl_off) + (u32)wave * (u32)MDX_PFL_WAVE_BYTES)) : 0u;
     static_assert(MDX_PK_QCAP >= 64 && MDX_PK_QCAP % 4 == 0, "a step's events fit an empty queue");
     const u32x2 *const emtab = (const u32x2 *)(ltab + 17);
     const u16 *const pktab = (const u16 *)(ltab + 17 + 64);
@@ -1314,10 +1354,10 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         const u32 tb = tile * T, rh = tb + T < n_rec ? tb + T : n_rec;
         const lds_u1 *const C = (const lds_u1 *)(size_t)(pfl_a + 4u * (u32)lane);
         const u32 fl_ = tb + (u32)lane < rh ? C[0] : 0x4u;
-        const int lib_ = ML ? a.lib_lo + ml_lib : (int)C[64], tid_ = (int)C[128];
+        const int lib_ = ML ? k_lib_lo + ml_lib : (int)C[64], tid_ = (int)C[128];
         const u32 co0_ = C[320], co1_ = C[321];
         bool kept_ = (fl_ & 0xF04u) == 0;
-        if (!ML && lib_ < a.nlib_total && (lib_ < a.lib_lo || lib_ >= a.lib_lo + d.nlib)) kept_ = false;
+        if (!ML && lib_ < a.nlib_total && (lib_ < k_lib_lo || lib_ >= k_lib_lo + d.nlib)) kept_ = false;
         const u32 cn_ = co1_ - co0_;
         const bool cand_ = kept_ && cn_ - 1u < 3u && tid_ >= 0 && tid_ < a.n_contig && lib_ < a.nlib_total;
         if (cand_) pfl_dma_rt2(pfl_a + 7u * 256u, co0_ * 4u, (co0_ + (cn_ >= 2u ? 1u : 0u)) * 4u, (co0_ + (cn_ >= 3u ? 2u : 0u)) * 4u,
@@ -2182,10 +2222,10 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         bool kept = valid && (fl & 0xF04u) == 0;  // reader.py:121-132
         // a launch counts the libraries [lib_lo, lib_lo + d.nlib) (mdx_capi.cpp: as many as fit the LDS); records of
         // the others are left to their own launch (a library id beyond the last one is an error in every launch)
-        if (!ML && c_lib < a.nlib_total && (c_lib < a.lib_lo || c_lib >= a.lib_lo + d.nlib)) kept = false;
+        if (!ML && c_lib < a.nlib_total && (c_lib < k_lib_lo || c_lib >= k_lib_lo + d.nlib)) kept = false;
         // (ML: the image holds the pool's library alone — table offsets are library 0's, the fragment lengths beyond the
         // LDS histogram go by lg_lib)
-        const int lg_lib = ML ? ml_lib : c_lib - a.lib_lo;
+        const int lg_lib = ML ? ml_lib : c_lib - k_lib_lo;
         int w1 = 0, nq = 0, libid = 0, n0 = 0, ncols = 0, nI = 0, cig_n = 0;
         int vlr = 0;   // gapped records: columns of the first / last match run, capped at L (vl | vr << 8)
         bool one = false;   // [H][S] M {I|D} M [S][H]: one indel between two match runs
@@ -2196,7 +2236,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         int lkey = -1;  // fragment-length key for the LDS histogram
         if (kept) {
             const int rev = (fl >> 4) & 1;
-            libid = ML ? 0 : c_lib - a.lib_lo;
+            libid = ML || GEOC ? 0 : c_lib - k_lib_lo;      // (GEO: a kept record is of library 0)
             const int tid = c_tid;
             const int pos = c_pos;
             cig_o = c_co0;
@@ -2363,7 +2403,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     } else {
                         const u64 slot = atomicAdd(p.n_lgd_over, 1ull);
                         if ((i64)slot < p.lgd_over_cap) {
-                            p.lgd_over[4 * slot + 0] = lg_lib + a.lib_lo;
+                            p.lgd_over[4 * slot + 0] = lg_lib + k_lib_lo;
                             p.lgd_over[4 * slot + 1] = kind;
                             p.lgd_over[4 * slot + 2] = rev;
                             p.lgd_over[4 * slot + 3] = flen;
@@ -2710,8 +2750,8 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         ml_k = (u32)__builtin_amdgcn_readfirstlane((int)pl.y);
         ml_m = (u32)__builtin_amdgcn_readfirstlane((int)pl.z);
         ml_first = (u32)__builtin_amdgcn_readfirstlane((int)pl.w);
-        rec_lo = kp->lib_start[a.lib_lo + ml_lib];
-        n_rec = kp->lib_start[a.lib_lo + ml_lib + 1] - rec_lo;
+        rec_lo = kp->lib_start[k_lib_lo + ml_lib];
+        n_rec = kp->lib_start[k_lib_lo + ml_lib + 1] - rec_lo;
     }
     if (!FAST) {
         for (u32 it = 0; it < n_it; it++) {
@@ -2965,11 +3005,11 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 u32 c_co0, c_co1, c_so0, c_so1;
                 if (pfl) {
                     fl = valid ? P_fl : 0x4u;
-                    c_lib = ML ? a.lib_lo + ml_lib : (int)P_lib; c_tid = (int)P_tid; c_pos = (int)P_pos; c_tlen = (int)P_tlen;
+                    c_lib = ML ? k_lib_lo + ml_lib : (int)P_lib; c_tid = (int)P_tid; c_pos = (int)P_pos; c_tlen = (int)P_tlen;
                     c_co0 = P_co0; c_co1 = P_co1; c_so0 = P_so0; c_so1 = P_so1;
                 } else {
                     fl = valid ? (u32)ld32(a.flag, rj) : 0x4u;
-                    c_lib = ML ? a.lib_lo + ml_lib : ld32(a.lib, rj); c_tid = ld32(a.tid, rj); c_pos = ld32(a.pos, rj); c_tlen = ld32(a.tlen, rj);
+                    c_lib = ML ? k_lib_lo + ml_lib : ld32(a.lib, rj); c_tid = ld32(a.tid, rj); c_pos = ld32(a.pos, rj); c_tlen = ld32(a.tlen, rj);
                     c_co0 = ld32(a.cigar_off, rj); c_co1 = ld32(a.cigar_off, rj + 1); c_so0 = ld32(a.seq_off, rj); c_so1 = ld32(a.seq_off, rj + 1);
                 }
                 int c_mtid = 0, c_mpos = 0;
@@ -3018,7 +3058,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     MDX_PH(1);
                 }
                 bool kept = (fl & 0xF04u) == 0;  // reader.py:121-132
-                if (!ML && c_lib < a.nlib_total && (c_lib < a.lib_lo || c_lib >= a.lib_lo + d.nlib)) kept = false;
+                if (!ML && c_lib < a.nlib_total && (c_lib < k_lib_lo || c_lib >= k_lib_lo + d.nlib)) kept = false;
                 // second round trip of the tile: the (up to three) operations, the contig bounds and (MASK) the first quality
                 // together.  The tile loop's own records: one match operation (M, = or X), alone or between soft clips —
                 // [S] M [S] — over the whole of SEQ.
@@ -3125,7 +3165,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     }
                     nDef += __popcll(mDef);
                 }
-                const int rev = (fl >> 4) & 1, libid = ML ? 0 : c_lib - a.lib_lo, nq = (int)len;
+                const int rev = (fl >> 4) & 1, libid = ML || GEOC ? 0 : c_lib - k_lib_lo, nq = (int)len;
                 const int lg_lib = ML ? ml_lib : libid;       // (the library for the dense length histogram and the overflow list)
                 const int lbase = __mul24(libid, d.w_lib);
                 const bool isF = triv && nq >= L;
@@ -3185,7 +3225,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                             } else {
                                 const u64 slot = atomicAdd(p.n_lgd_over, 1ull);
                                 if ((i64)slot < p.lgd_over_cap) {
-                                    p.lgd_over[4 * slot + 0] = lg_lib + a.lib_lo;
+                                    p.lgd_over[4 * slot + 0] = lg_lib + k_lib_lo;
                                     p.lgd_over[4 * slot + 1] = paired ? 0 : 1;
                                     p.lgd_over[4 * slot + 2] = rev;
                                     p.lgd_over[4 * slot + 3] = (i64)flen;
@@ -3695,16 +3735,38 @@ hipError_t mdx_k_prepare_packed(size_t lds_bytes) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *)tabulate_kernel<true, false, true, false, true, true>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    // (the kernel of the default geometry: its own image, whatever this context's is)
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)tabulate_kernel<true, false, true, false, true, false, 1>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)MdxGeo::lds_bytes);
     return e;
+}
+
+// Is this launch what tabulate_kernel<.., GEO = 1> was compiled for?  Every dimension it has folded (all of MdxDims but
+// lgd_max, which it reads from its arguments), the block, the image and its offsets, one library from library 0 on.
+static bool geo_matches(const MdxTabArgs &a, int threads, size_t lds_bytes) {
+    constexpr MdxDims g = MdxGeo::dims;
+    const MdxDims &d = a.dims;
+    return d.L == g.L && d.A == g.A && d.nlib == g.nlib && d.lgd_lds == g.lgd_lds && d.nl8 == g.nl8 && d.G == g.G && d.R == g.R &&
+           d.nl16 == g.nl16 && d.G4 == g.G4 && d.H4 == g.H4 && d.t_pad == g.t_pad && d.w_mis == g.w_mis && d.w_cmp == g.w_cmp &&
+           d.w_mc == g.w_mc && d.w_tc == g.w_tc && d.w_dmp == g.w_dmp && d.w_lgd == g.w_lgd && d.w_lib == g.w_lib && d.w_total == g.w_total &&
+           threads == MdxGeo::threads && lds_bytes == MdxGeo::lds_bytes && a.stage_off == MdxGeo::stage_off &&
+           a.queue_off == MdxGeo::queue_off && a.pfl_off == MdxGeo::pfl_off && a.n_libs == 0 && a.lib_lo == 0;
 }
 
 // the packed kernel: 4-bit SEQ column and 4-bit reference; one library per launch, or (a.n_libs > 0) the libraries
 // [lib_lo, lib_lo + n_libs) side by side over the bucketed columns, a library per pool
-void mdx_k_tabulate_packed(const MdxTabArgs &a, int grid, int threads, size_t lds_bytes, hipStream_t s) {
-    if (a.n_reads <= 0) return;
+// (a one-library launch of the default geometry: the kernel compiled for it — geo_matches; MDX_NO_GEO_SPEC=1: never)
+bool mdx_k_tabulate_packed(const MdxTabArgs &a, int grid, int threads, size_t lds_bytes, hipStream_t s) {
+    static const bool no_geo = [] { const char *e = getenv("MDX_NO_GEO_SPEC"); return e && *e && *e != '0'; }();
+    if (a.n_reads <= 0) return false;
     if (a.n_libs > 0) hipLaunchKernelGGL((tabulate_kernel<true, false, true, false, true, true>), dim3(grid), dim3(threads), lds_bytes, s, a);
+    else if (!no_geo && geo_matches(a, threads, lds_bytes)) {
+        hipLaunchKernelGGL((tabulate_kernel<true, false, true, false, true, false, 1>), dim3(grid), dim3(threads), lds_bytes, s, a);
+        return true;
+    }
     else
     hipLaunchKernelGGL((tabulate_kernel<true, false, true, false, true>), dim3(grid), dim3(threads), lds_bytes, s, a);
+    return false;
 }
 
 hipError_t mdx_k_prepare(size_t lds_bytes) {

@@ -34,7 +34,7 @@ EXPORTS = (
     "mdx_bam_stream_keep_raw", "mdx_bam_raw", "mdx_bam_patch_rescaled", "mdx_bam_qmin",
     "mdx_ctx_stream", "mdx_gbam_open", "mdx_gbam_header", "mdx_gbam_error", "mdx_gbam_configure", "mdx_gbam_next",
     "mdx_gbam_at_end", "mdx_gbam_close", "mdx_gbam_set_min_basequal", "mdx_gbam_missing_qualities",
-    "mdx_gbam_inflate_blocks", "mdx_set_record_base", "mdx_pack_seq", "mdx_gbam_set_seq_format", "mdx_packed_launches",
+    "mdx_gbam_inflate_blocks", "mdx_set_record_base", "mdx_pack_seq", "mdx_gbam_set_seq_format", "mdx_packed_launches", "mdx_geo_spec_launches",
     "mdx_gbam_skip", "mdx_comm_count", "mdx_gbam_tell", "mdx_gbam_fixups", "mdx_bam_seek", "mdx_libsorts",
     "mdx_gbam_view_flags", "mdx_gbam_view_set_flags",
     "mdx_rescale_patches_device", "mdx_tabulate_rescale_patches_device", "mdx_rescale_expand_device", "mdx_mr_round", "mdx_batch_fold", "mdx_bgzf_deflate",
@@ -123,6 +123,8 @@ def load_library(path=None):
     lib.mdx_fused_launches.argtypes = [ctypes.c_void_p]
     lib.mdx_packed_launches.restype = ctypes.c_int64
     lib.mdx_packed_launches.argtypes = [ctypes.c_void_p]
+    lib.mdx_geo_spec_launches.restype = ctypes.c_int64
+    lib.mdx_geo_spec_launches.argtypes = [ctypes.c_void_p]
     lib.mdx_libsorts.restype = ctypes.c_int64
     lib.mdx_libsorts.argtypes = [ctypes.c_void_p]
     lib.mdx_last_launch_geometry.restype = ctypes.c_int
@@ -619,6 +621,11 @@ class DamageEngine:
     def packed_launches(self):
         """Kernel launches so far that ran as the packed kernel (4-bit SEQ column and reference)."""
         return int(self._lib.mdx_packed_launches(self._ctx))
+
+    def geo_spec_launches(self):
+        """... and those of them that ran the packed kernel compiled for the default geometry (--length 70 --around 10, one
+        library, no --min-basequal; ``MDX_NO_GEO_SPEC=1`` in the environment: none)."""
+        return int(self._lib.mdx_geo_spec_launches(self._ctx))
 
     def libsorts(self):
         """Calls so far that bucketed their batch by library inside the launch (several libraries, a batch that did not
