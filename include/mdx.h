@@ -277,6 +277,20 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
  *                      MDX_ERR_BAD_READ at mdx_sync if the flag filter keeps it, as in any context.  mdx_batch_upload on a
  *                      stratified context buckets the resident batch by stratum (mdx_batch::libsort), so set the strata first.
  *                      The fused calls (mdx_tabulate_rescale_*) count one library and refuse such a context (MDX_ERR_ARG).
+ *   mdx_set_strata_regions  the group from a set of genomic regions (a BED file) instead of the sequence alone: on-target
+ *                      against off-target of a capture panel, without a `samtools view -L` in front.  A record occupies
+ *                      [pos, pos + max(1, reference bases of its CIGAR)) — M D N = X consume, clips and insertions do not
+ *                      (htslib's bam_endpos) — and takes the group of the first interval of its sequence it shares a base
+ *                      with (start < rec_end && end > rec_pos); rest_group where there is none, or where tid is outside
+ *                      [0, n_contig).  The intervals of sequence t are iv_off[t] .. iv_off[t + 1] of the parallel arrays
+ *                      iv_start, iv_end, iv_group (host; 0-based, half-open), sorted and disjoint within a sequence
+ *                      (iv_end[k] <= iv_start[k + 1]): the key kernel binary-searches the slice.  MDX_ERR_ARG, with a
+ *                      message naming the first offending interval, for offsets that decrease, an interval that is not
+ *                      0 <= start < end, one that begins before its predecessor ends, a group or rest_group outside
+ *                      [0, n_groups).  State rules, cfg.nlib, n_contig, mdx_batch_upload and the fused calls as for
+ *                      mdx_set_strata.  A context has tid strata or region strata: calling the other kind is
+ *                      MDX_ERR_STATE.  The arrays are copied to the device and stay there for the context's life.  The
+ *                      flag filter is unchanged: a record it drops gets a key and is not counted in mdx_strata_kept.
  *   mdx_strata_groups  n_groups, 0 for a context without strata
  *   mdx_strata_kept    kept[cfg.nlib] (host): the records the flag filter (reader.py:121-132) kept, per stratum, of this
  *                      context's batches since mdx_create / mdx_reset — the block's n_kept is one word for the whole run.
@@ -295,6 +309,8 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
  * 2.1 GB.  mdx_lgd_copies: how many this context has (introspection).  More than 65 535 tables: MDX_ERR_ARG from mdx_create,
  * with a context to read the message from (the 16-bit library column names no more). */
 int mdx_set_strata(mdx_ctx *ctx, int32_t n_groups, const int32_t *group_of_tid, int32_t n_contig);
+int mdx_set_strata_regions(mdx_ctx *ctx, int32_t n_groups, int32_t n_contig, const int64_t *iv_off /* n_contig+1 */,
+                           const int32_t *iv_start, const int32_t *iv_end, const int32_t *iv_group, int32_t rest_group);
 int mdx_strata_groups(const mdx_ctx *ctx);
 int mdx_strata_kept(mdx_ctx *ctx, uint64_t *kept);
 int64_t mdx_merged_words(const mdx_ctx *ctx);

@@ -158,6 +158,10 @@ struct mdx_ctx {
     int32_t *d_group_of_tid = nullptr;
     unsigned long long *d_strata_kept = nullptr;   // [cfg.nlib]: the records the flag filter kept, per stratum
     int strata_n_contig = 0;
+    // ... or (mdx_set_strata_regions) the group of the first interval the record overlaps: one allocation, resident for the
+    // context's life — [iv_off n_contig + 1][iv_start][iv_end][iv_group]
+    void *d_regions = nullptr;
+    MdxRegions regions = {};
     DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -384,7 +388,7 @@ void mdx_destroy(mdx_ctx *c) {
         if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
     }
     void *ptrs[] = {c->d_ref, c->d_ref4, c->d_contig_off, c->d_raw, c->d_lgd_dense, c->d_lgd_over,
-                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_strata_kept};
+                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_regions, c->d_strata_kept};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -547,15 +551,19 @@ static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, i
     for (uint64_t v : {(uint64_t)n, (uint64_t)n_cigar, (uint64_t)n_bases, (uint64_t)nlib | (uint64_t)n_groups << 32}) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; }
     return h | 1ull;
 }
-// A stratified context (mdx_set_strata): *out = the device batch b with the key column — library x groups + group of the
-// record's sequence — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
+// A stratified context (mdx_set_strata, mdx_set_strata_regions): *out = the device batch b with the key column — library x
+// groups + group of the record's sequence, or of the first region it overlaps — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
 // stream; valid until the next such call).  count: the kept records are added to the context's counts per stratum.
 static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool count) {
     *out = *b;
     if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
     HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
-    mdx_k_strata_key(b->n_reads, b->flag, b->lib, b->tid, c->d_group_of_tid, c->strata_n_contig, c->n_groups, c->cfg.nlib / c->n_groups,
-                     (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
+    if (c->d_regions)
+        mdx_k_strata_region_key(b->n_reads, b->flag, b->lib, b->tid, b->pos, b->cigar_off, b->cigar, b->n_cigar, c->regions, c->n_groups,
+                                c->cfg.nlib / c->n_groups, (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
+    else
+        mdx_k_strata_key(b->n_reads, b->flag, b->lib, b->tid, c->d_group_of_tid, c->strata_n_contig, c->n_groups, c->cfg.nlib / c->n_groups,
+                         (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
     HIP_TRY(c, hipGetLastError());
     out->lib = (const uint16_t *)c->strata_key.p;
     return MDX_OK;
@@ -703,7 +711,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     if (c->n_groups > 0) {
         if (fuse) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
         if (c->strata_n_contig != c->n_contig)
-            return fail(c, MDX_ERR_ARG, "mdx_set_strata named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
+            return fail(c, MDX_ERR_ARG, std::string(c->d_regions ? "mdx_set_strata_regions" : "mdx_set_strata") + " named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
                                         std::to_string(c->n_contig));
         if (!(ml && b_in->libsort)) {
             rc = strata_view(c, b_in, &b_key, true);
@@ -1252,12 +1260,65 @@ int mdx_set_strata(mdx_ctx *c, int32_t n_groups, const int32_t *group_of_tid, in
         if (group_of_tid[t] < 0 || group_of_tid[t] >= n_groups)
             return fail(c, MDX_ERR_ARG, "set_strata: the group of sequence " + std::to_string(t) + " is outside [0, n_groups)");
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata: records have been counted already (mdx_reset first)");
+    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata: the context has region strata (mdx_set_strata_regions); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_group_of_tid) { (void)hipFree(c->d_group_of_tid); c->d_group_of_tid = nullptr; }
     c->n_groups = 0;
     HIP_TRY(c, hipMalloc((void **)&c->d_group_of_tid, (size_t)n_contig * 4));
     HIP_TRY(c, hipMemcpy(c->d_group_of_tid, group_of_tid, (size_t)n_contig * 4, hipMemcpyHostToDevice));
+    if (!c->d_strata_kept) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
+        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
+    }
+    c->n_groups = n_groups;
+    c->strata_n_contig = n_contig;
+    return MDX_OK;
+}
+
+int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const int64_t *iv_off, const int32_t *iv_start,
+                           const int32_t *iv_end, const int32_t *iv_group, int32_t rest_group) {
+    if (!c) return MDX_ERR_ARG;
+    if (n_groups < 1 || n_contig < 1 || !iv_off) return fail(c, MDX_ERR_ARG, "set_strata_regions: bad arguments");
+    if (c->cfg.nlib % n_groups != 0)
+        return fail(c, MDX_ERR_ARG, "set_strata_regions: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of " +
+                                    std::to_string(n_groups) + " groups (create it with nlib = libraries x groups)");
+    if (rest_group < 0 || rest_group >= n_groups) return fail(c, MDX_ERR_ARG, "set_strata_regions: rest_group is outside [0, n_groups)");
+    if (iv_off[0] != 0) return fail(c, MDX_ERR_ARG, "set_strata_regions: iv_off[0] is not 0");
+    for (int32_t t = 0; t < n_contig; t++)
+        if (iv_off[t + 1] < iv_off[t])
+            return fail(c, MDX_ERR_ARG, "set_strata_regions: the offsets decrease at sequence " + std::to_string(t));
+    const int64_t n_iv = iv_off[n_contig];
+    if (n_iv > 0 && (!iv_start || !iv_end || !iv_group)) return fail(c, MDX_ERR_ARG, "set_strata_regions: bad arguments");
+    for (int32_t t = 0; t < n_contig; t++)
+        for (int64_t k = iv_off[t]; k < iv_off[t + 1]; k++) {
+            const std::string which = "set_strata_regions: interval " + std::to_string(k) + " (sequence " + std::to_string(t) + ", [" +
+                                      std::to_string(iv_start[k]) + ", " + std::to_string(iv_end[k]) + ")) ";
+            if (iv_start[k] < 0 || iv_start[k] >= iv_end[k]) return fail(c, MDX_ERR_ARG, which + "is not 0 <= start < end");
+            if (k > iv_off[t] && iv_end[k - 1] > iv_start[k])
+                return fail(c, MDX_ERR_ARG, which + "begins before interval " + std::to_string(k - 1) + " ends: not sorted and disjoint");
+            if (iv_group[k] < 0 || iv_group[k] >= n_groups)
+                return fail(c, MDX_ERR_ARG, which + "has group " + std::to_string(iv_group[k]) + ", outside [0, n_groups)");
+        }
+    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_regions: records have been counted already (mdx_reset first)");
+    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has tid strata (mdx_set_strata); a context has one kind");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->d_regions) { (void)hipFree(c->d_regions); c->d_regions = nullptr; }
+    c->n_groups = 0;
+    const size_t off_bytes = ((size_t)(n_contig + 1) * 8 + 15) & ~(size_t)15, col_bytes = ((size_t)n_iv * 4 + 15) & ~(size_t)15;
+    HIP_TRY(c, hipMalloc(&c->d_regions, off_bytes + 3 * col_bytes + 64));
+    char *p = (char *)c->d_regions;
+    HIP_TRY(c, hipMemcpy(p, iv_off, (size_t)(n_contig + 1) * 8, hipMemcpyHostToDevice));
+    const int32_t *cols[3] = {iv_start, iv_end, iv_group};
+    for (int k = 0; k < 3 && n_iv > 0; k++)
+        HIP_TRY(c, hipMemcpy(p + off_bytes + k * col_bytes, cols[k], (size_t)n_iv * 4, hipMemcpyHostToDevice));
+    c->regions.iv_off = (const int64_t *)p;
+    c->regions.iv_start = (const int32_t *)(p + off_bytes);
+    c->regions.iv_end = (const int32_t *)(p + off_bytes + col_bytes);
+    c->regions.iv_group = (const int32_t *)(p + off_bytes + 2 * col_bytes);
+    c->regions.rest_group = rest_group;
+    c->regions.n_contig = n_contig;
     if (!c->d_strata_kept) {
         HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
         HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));

@@ -386,6 +386,17 @@ void mdx_k_finalize(const unsigned long long *raw, const unsigned long long *lgd
 // counts from the buckets of a batch sorted by stratum
 void mdx_k_strata_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *group_of_tid, int n_contig,
                       int n_groups, int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
+// region strata (mdx_set_strata_regions): the group is that of the first interval of the record's sequence that shares a base
+// with [pos, pos + max(1, reference bases of the CIGAR)), rest_group where none does or tid is outside [0, n_contig).  The
+// intervals (device) of sequence t are iv_off[t] .. iv_off[t + 1], sorted and disjoint.  CIGAR offsets are clamped to n_cigar.
+struct MdxRegions {
+    const int64_t *iv_off;       // [n_contig + 1]
+    const int32_t *iv_start, *iv_end, *iv_group;
+    int32_t rest_group, n_contig;
+};
+void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *pos,
+                             const uint32_t *cigar_off, const uint32_t *cigar, int64_t n_cigar, const MdxRegions &r, int n_groups,
+                             int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
 void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
 // a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
 // n_libraries tables, the groups of each library summed

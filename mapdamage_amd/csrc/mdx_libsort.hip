@@ -420,6 +420,83 @@ void mdx_k_strata_key(int64_t n, const uint16_t *flag, const uint16_t *lib, cons
                        group_of_tid, n_contig, n_groups, n_libraries, key, (u64 *)kept);
 }
 
+// The same with the group taken from a set of genomic regions (mdx_set_strata_regions) instead of the sequence alone.  A
+// record occupies [pos, pos + max(1, reference bases of its CIGAR)) — M D N = X consume, clips and insertions do not
+// (htslib's bam_endpos) — and takes the group of the first interval of its sequence that shares a base with it, the rest
+// group where none does or the sequence is not one of the reference's.  The intervals of a sequence are sorted and disjoint
+// (checked by the caller), so the first one with iv_end > pos is the only candidate: a binary search of the sequence's
+// slice.  On top of the 10 bytes of the tid key: pos, two offsets (the neighbour's are in the same line) and the CIGAR words,
+// one or two for most records; the search's upper levels stay in the L2.  Offsets outside the CIGAR column are clamped:
+// a malformed batch reads nothing behind it (the tabulation kernels report such a record).
+__global__ __launch_bounds__(256) void strata_region_key_kernel(i64 n, const u16 *__restrict__ flag, const u16 *__restrict__ lib,
+                                                                const int32_t *__restrict__ tid, const int32_t *__restrict__ pos,
+                                                                const u32 *__restrict__ cigar_off, const u32 *__restrict__ cigar,
+                                                                u32 n_cigar, const i64 *__restrict__ iv_off,
+                                                                const int32_t *__restrict__ iv_start, const int32_t *__restrict__ iv_end,
+                                                                const int32_t *__restrict__ iv_group, int rest_group, int n_contig,
+                                                                int n_groups, int n_libraries, u16 *__restrict__ key,
+                                                                u64 *__restrict__ kept) {
+    __shared__ u32 h[LS_LDS_LIBS];
+    const int n_strata = n_libraries * n_groups;
+    const bool in_lds = n_strata <= LS_LDS_LIBS;
+    if (in_lds) {
+        for (int l = threadIdx.x; l < n_strata; l += 256) h[l] = 0u;
+        __syncthreads();
+    }
+    const i64 lo = (i64)blockIdx.x * STRATA_KEY_PER, hi = lo + STRATA_KEY_PER < n ? lo + STRATA_KEY_PER : n;
+    for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
+        const u32 lb = lib[i], fl = flag[i];
+        const int32_t t = tid[i];
+        u32 k = 0xFFFFu;
+        if (lb < (u32)n_libraries) {
+            u32 g = (u32)rest_group;
+            if (t >= 0 && t < n_contig) {
+                i64 a = iv_off[t];
+                const i64 e = iv_off[t + 1];
+                if (a < e) {
+                    const i64 p = pos[i];
+                    u32 c1 = cigar_off[i + 1], c0 = cigar_off[i];
+                    if (c1 > n_cigar) c1 = n_cigar;
+                    i64 span = 0;
+                    for (u32 c = c0; c < c1; c++) {
+                        const u32 w = cigar[c], op = w & 15u;
+                        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) span += (i64)(w >> 4);
+                    }
+                    const i64 end = p + (span > 0 ? span : 1);
+                    // the first interval of [a, e) with iv_end > pos
+                    i64 b = e;
+                    while (a < b) {
+                        const i64 m = a + ((b - a) >> 1);
+                        if ((i64)iv_end[m] > p) b = m;
+                        else a = m + 1;
+                    }
+                    if (a < e && (i64)iv_start[a] < end) g = (u32)iv_group[a];
+                }
+            }
+            k = lb * (u32)n_groups + g;
+        }
+        key[i] = (u16)k;
+        if (kept && k != 0xFFFFu && !(fl & 0xF04u)) {
+            if (in_lds) atomicAdd(&h[k], 1u);
+            else atomicAdd(&kept[k], 1ull);
+        }
+    }
+    if (in_lds && kept) {
+        __syncthreads();
+        for (int l = threadIdx.x; l < n_strata; l += 256)
+            if (h[l]) atomicAdd(&kept[l], (u64)h[l]);
+    }
+}
+
+void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *pos,
+                             const uint32_t *cigar_off, const uint32_t *cigar, int64_t n_cigar, const MdxRegions &r, int n_groups,
+                             int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(strata_region_key_kernel, dim3((unsigned)((n + STRATA_KEY_PER - 1) / STRATA_KEY_PER)), dim3(256), 0, s, (i64)n, flag, lib,
+                       tid, pos, cigar_off, cigar, (u32)n_cigar, (const i64 *)r.iv_off, r.iv_start, r.iv_end, r.iv_group, r.rest_group,
+                       r.n_contig, n_groups, n_libraries, key, (u64 *)kept);
+}
+
 // ... and for a batch that brings its columns bucketed by stratum (mdx_batch::libsort): the sizes of the buckets
 __global__ void strata_kept_from_sort_kernel(const u32 *__restrict__ lib_start, int n_strata, u64 *__restrict__ kept) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;

@@ -47,7 +47,7 @@ EXPORTS = (
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
     "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
-    "mdx_set_strata", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
+    "mdx_set_strata", "mdx_set_strata_regions", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -184,6 +184,8 @@ def load_library(path=None):
     lib.mdx_bam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
     lib.mdx_gbam_open_source.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_set_strata.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_set_strata_regions.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
     lib.mdx_strata_groups.argtypes = [ctypes.c_void_p]
     lib.mdx_strata_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_merged_words.restype = ctypes.c_int64
@@ -260,8 +262,8 @@ class DamageEngine:
 
     ``groups``: names of groups of reference sequences — the engine then keeps one table set per (library, group), a
     *stratum* (include/mdx.h ``mdx_set_strata``): ``set_strata(group_of_tid)`` says which group each sequence of the
-    header belongs to, the batches keep naming the library in their ``lib`` column, and ``finish()`` returns a
-    ``tables.StratifiedTables``.  ``libraries`` then holds one entry per stratum, library-major (``base_libraries`` the
+    header belongs to (or ``set_strata_regions(...)`` which group each region of a BED file does), the batches keep naming
+    the library in their ``lib`` column, and ``finish()`` returns a ``tables.StratifiedTables``.  ``libraries`` then holds one entry per stratum, library-major (``base_libraries`` the
     caller's list)."""
 
     MAX_TABLES = 65535      # the 16-bit library column, 0xFFFF being the record without a library
@@ -340,6 +342,24 @@ class DamageEngine:
             raise ValueError("set_strata: the engine was made without groups")
         m = np.ascontiguousarray(group_of_tid, dtype=np.int32)
         self._check(self._lib.mdx_set_strata(self._ctx, ctypes.c_int32(len(self.groups)), _ptr(m), ctypes.c_int32(m.shape[0])))
+        self._strata_set = True
+
+    def set_strata_regions(self, iv_off, iv_start, iv_end, iv_group, rest_group=None):
+        """The group of a record from a set of regions (include/mdx.h ``mdx_set_strata_regions``): the intervals of sequence
+        ``t`` are ``iv_off[t]:iv_off[t + 1]`` of ``iv_start, iv_end, iv_group`` (0-based, half-open, sorted and disjoint
+        within a sequence, ``iv_group`` an index into ``groups``); a record that overlaps none goes to ``rest_group`` (default:
+        the last group).  Before the first ``tabulate`` / ``upload``."""
+        if self.groups is None:
+            raise ValueError("set_strata_regions: the engine was made without groups")
+        off = np.ascontiguousarray(iv_off, dtype=np.int64)
+        cols = [np.ascontiguousarray(a, dtype=np.int32) for a in (iv_start, iv_end, iv_group)]
+        if off.ndim != 1 or off.shape[0] < 2 or any(a.ndim != 1 or a.shape[0] != cols[0].shape[0] for a in cols) \
+                or int(off[-1]) != cols[0].shape[0]:
+            raise ValueError("set_strata_regions: iv_off must hold one entry per sequence and one more, its last the "
+                             "length of the three interval columns")
+        rest = len(self.groups) - 1 if rest_group is None else int(rest_group)
+        self._check(self._lib.mdx_set_strata_regions(self._ctx, ctypes.c_int32(len(self.groups)), ctypes.c_int32(off.shape[0] - 1),
+                                                     _ptr(off), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ctypes.c_int32(rest)))
         self._strata_set = True
 
     def strata_kept(self):

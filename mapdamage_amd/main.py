@@ -128,6 +128,19 @@ def build_parser():
     g.add_argument("--reference-groups", type=Path, metavar="TSV",
                    help="like --by-reference for groups of sequences: lines 'sequence name<TAB>group name'; the sequences not "
                         "listed form a last group named '*' (not a reference option either)")
+    g.add_argument("--regions", type=Path, metavar="BED",
+                   help="also tabulate the records that overlap the regions of a BED file (sequence<TAB>start<TAB>end, 0-based, "
+                        "half-open) apart from the rest, in the same pass: a record occupies [pos, pos + max(1, reference bases of "
+                        "its CIGAR)) and belongs to the first region it shares a base with, as `samtools view -L` decides; the usual "
+                        "three files are what the run writes without the option, and by_region/ holds groups.tsv and the three files "
+                        "of the groups 'regions' and '*' (everything else) in directories named by their index")
+    g.add_argument("--region-groups", type=Path, metavar="BED",
+                   help="like --regions with the group of a region named by column 4 of the BED file; overlapping regions of "
+                        "different groups are an error, a record that overlaps several goes to the one that begins first")
+    g.add_argument("--only-regions", action="store_true",
+                   help="with --regions / --region-groups: the usual three files hold the records inside the regions only (the sum "
+                        "of the named groups, '*' left out) — what `samtools view -L BED` in front would have produced; by_region/ "
+                        "is still complete")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -156,6 +169,15 @@ def parse_args(argv):
         parser.error("--by-reference and --reference-groups exclude each other")
     if (o.by_reference or o.reference_groups) and o.rescale_only:
         parser.error("--by-reference / --reference-groups belong to the tabulation pass; --rescale-only counts nothing")
+    if o.regions and o.region_groups:
+        parser.error("--regions and --region-groups exclude each other")
+    if (o.regions or o.region_groups) and (o.by_reference or o.reference_groups):
+        parser.error("--regions / --region-groups and --by-reference / --reference-groups exclude each other: a run has one "
+                     "kind of groups")
+    if (o.regions or o.region_groups) and o.rescale_only:
+        parser.error("--regions / --region-groups belong to the tabulation pass; --rescale-only counts nothing")
+    if o.only_regions and not (o.regions or o.region_groups):
+        parser.error("--only-regions needs --regions or --region-groups")
     if o.rescale_only and not o.folder:
         parser.error("--folder required when using --rescale-only")
     if not o.filename:
@@ -332,25 +354,34 @@ def launch_command(argv, gpus):
             "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "mapdamage_amd"] + keep
 
 
-def reference_strata(options, references):
-    """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, or None."""
-    from .tables import groups_by_reference, parse_reference_groups
+def reference_strata(options, references, lengths=None):
+    """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, (group names,
+    tables.Regions) of --regions / --region-groups (``lengths``: the sequences' lengths), or None."""
+    from .tables import Regions, groups_by_reference, parse_reference_groups, parse_regions
     if options.by_reference:
         return groups_by_reference(references)
     if options.reference_groups:
         return parse_reference_groups(Path(options.reference_groups).read_text(), references)
+    bed = getattr(options, "regions", None) or getattr(options, "region_groups", None)
+    if bed:
+        names, *columns = parse_regions(Path(bed).read_text(), references, lengths, named=not options.regions)
+        return names, Regions(*columns, [int(x) for x in lengths])
     return None
 
 
 def _make_engine(options, libraries, device):
-    """The run's engine; with --by-reference / --reference-groups one table set per (library, group) — the input routes
-    hand it the same batches either way."""
+    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups one table set per (library,
+    group) — the input routes hand it the same batches either way."""
+    from .tables import Regions
     strata = getattr(options, "strata", None)
     engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=device,
                           groups=None if strata is None else strata[0])
     if strata is not None:
         try:
-            engine.set_strata(strata[1])
+            if isinstance(strata[1], Regions):
+                engine.set_strata_regions(strata[1].iv_off, strata[1].iv_start, strata[1].iv_end, strata[1].iv_group)
+            else:
+                engine.set_strata(strata[1])
         except Exception:
             engine.close()
             raise
@@ -683,15 +714,16 @@ def main(argv):
             logger.info("Reference: plain gzip FASTA, read by the host (Python reader)")
         libraries = reader.get_libraries()
         try:
-            options.strata = reference_strata(options, list(reader.handle.header.references))
+            options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
         except (ValueError, OSError) as error:
             logger.error("%s", error)
             return 1
         if options.strata is not None:
-            logger.info("Tabulating %d groups of reference sequences x %d libraries in one pass", len(options.strata[0]), len(libraries))
+            kind = "regions" if options.regions or options.region_groups else "reference sequences"
+            logger.info("Tabulating %d groups of %s x %d libraries in one pass", len(options.strata[0]), kind, len(libraries))
             if len(options.strata[0]) * len(libraries) > DamageEngine.MAX_TABLES:
-                logger.error("%d groups of reference sequences x %d libraries: more than the %d tables a run can keep",
-                             len(options.strata[0]), len(libraries), DamageEngine.MAX_TABLES)
+                logger.error("%d groups of %s x %d libraries: more than the %d tables a run can keep",
+                             len(options.strata[0]), kind, len(libraries), DamageEngine.MAX_TABLES)
                 return 1
         stages.mark("headers and index")
 
@@ -727,8 +759,18 @@ def main(argv):
             return 0
         if options.strata is not None:
             # the three usual files from the sum over the groups, and by_reference/ beside them
-            tables.write(options.folder, options.strata[1])
-            tables = tables.merged
+            if options.regions or options.region_groups:
+                from .tables import region_groups_text
+                r, ng = options.strata[1], len(options.strata[0])
+                text = region_groups_text(options.strata[0], r.iv_start, r.iv_end, r.iv_group, r.lengths,
+                                          [tables.group_kept(g) for g in range(ng)])
+                # (--only-regions: the usual files from the named groups alone, summed on the host; by_region/ keeps '*')
+                usual = tables.sum_of_groups(range(ng - 1)) if options.only_regions else None
+                tables.write(options.folder, subdir="by_region", groups_text=text, usual=usual)
+                tables = tables.merged if usual is None else usual
+            else:
+                tables.write(options.folder, options.strata[1])
+                tables = tables.merged
         else:
             tables.write(options.folder)
         if options.freq_files:

@@ -8,6 +8,7 @@
 
 import io
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -204,6 +205,97 @@ def groups_by_reference(references):
     return [str(r) for r in references], np.arange(len(references), dtype=np.int32)
 
 
+def parse_regions(text, references, lengths, named):
+    """``--regions BED`` (``named=False``) / ``--region-groups BED`` (``named=True``): lines
+    ``sequence<TAB>start<TAB>end[<TAB>name...]``, 0-based and half-open.  Returns (group names, iv_off, iv_start, iv_end,
+    iv_group): the intervals of sequence ``t`` of ``references`` (the header's, tid order) are ``iv_off[t]:iv_off[t + 1]`` of
+    the three parallel int32 columns, sorted and disjoint — overlapping or abutting regions of the same group are merged.
+    ``named=False``: one group ``regions``; ``named=True``: column 4 names the group, numbered in order of first appearance.
+    A last group named ``*`` always follows: the records that overlap no region.  ValueError naming the line for fewer than
+    three columns, coordinates that are no integers, ``start >= end`` or ``start < 0``, an end beyond the sequence's length,
+    a sequence the header lacks, a group named ``*``, a missing name with ``named=True``; naming both lines for overlapping
+    regions of different groups.  Empty lines and lines starting with ``#``, ``track`` or ``browser`` are skipped."""
+    index = {name: tid for tid, name in enumerate(references)}
+    names, number = ([], {}) if named else (["regions"], {})
+    per_seq = [[] for _ in references]          # (start, end, group, line number)
+    for lineno, line in enumerate(text.splitlines(), 1):
+        line = line.rstrip("\r")
+        if not line.strip() or line.startswith("#") or line.split(None, 1)[0] in ("track", "browser"):
+            continue
+        cols = line.split("\t")
+        if len(cols) < 3:
+            raise ValueError("regions, line %d: expected 'sequence<TAB>start<TAB>end', found %r" % (lineno, line))
+        seq = cols[0]
+        try:
+            start, end = int(cols[1]), int(cols[2])
+        except ValueError:
+            raise ValueError("regions, line %d: the coordinates %r and %r are no integers" % (lineno, cols[1], cols[2])) from None
+        if seq not in index:
+            raise ValueError("regions, line %d: the header has no sequence named %r" % (lineno, seq))
+        if start < 0 or start >= end:
+            raise ValueError("regions, line %d: [%d, %d) is not 0 <= start < end" % (lineno, start, end))
+        if end > int(lengths[index[seq]]):
+            raise ValueError("regions, line %d: the end %d lies beyond the %d bases of sequence %r"
+                             % (lineno, end, int(lengths[index[seq]]), seq))
+        group = 0
+        if named:
+            if len(cols) < 4 or not cols[3]:
+                raise ValueError("regions, line %d: no group name in column 4" % lineno)
+            if cols[3] == CATCH_ALL_GROUP:
+                raise ValueError("regions, line %d: the group name %r is taken by the records outside every region"
+                                 % (lineno, CATCH_ALL_GROUP))
+            if cols[3] not in number:
+                number[cols[3]] = len(names)
+                names.append(cols[3])
+            group = number[cols[3]]
+        per_seq[index[seq]].append((start, end, group, lineno))
+    iv_off, iv_start, iv_end, iv_group = [0], [], [], []
+    for ivs in per_seq:
+        ivs.sort()
+        first = len(iv_start)
+        members = []                            # the lines merged into the last interval
+        for start, end, group, lineno in ivs:
+            if len(iv_start) > first and start <= iv_end[-1] and group == iv_group[-1]:
+                iv_end[-1] = max(iv_end[-1], end)
+                members.append((start, end, lineno))
+                continue
+            if len(iv_start) > first and start < iv_end[-1]:
+                other = next(n for s, e, n in members if s < end and e > start)
+                raise ValueError("regions, lines %d and %d: regions of the groups %r and %r overlap"
+                                 % (min(other, lineno), max(other, lineno), names[iv_group[-1]], names[group]))
+            iv_start.append(start); iv_end.append(end); iv_group.append(group)
+            members = [(start, end, lineno)]
+        iv_off.append(len(iv_start))
+    names.append(CATCH_ALL_GROUP)
+    return (names, np.asarray(iv_off, dtype=np.int64), np.asarray(iv_start, dtype=np.int32), np.asarray(iv_end, dtype=np.int32),
+            np.asarray(iv_group, dtype=np.int32))
+
+
+class Regions(NamedTuple):
+    """The intervals of ``parse_regions`` and the lengths of the header's sequences: what a region run hands to
+    ``DamageEngine.set_strata_regions`` and to ``region_groups_text``."""
+    iv_off: np.ndarray
+    iv_start: np.ndarray
+    iv_end: np.ndarray
+    iv_group: np.ndarray
+    lengths: list
+
+
+def region_groups_text(groups, iv_start, iv_end, iv_group, lengths, kept):
+    """``by_region/groups.tsv``: index, group name, regions and bases after merging, kept reads (``kept[g]``); the last
+    group — ``*`` — has no regions and the bases of the genome that no region covers."""
+    ng = len(groups)
+    span = np.asarray(iv_end, np.int64) - np.asarray(iv_start, np.int64)
+    n_regions = np.bincount(np.asarray(iv_group, np.int64), minlength=ng)
+    n_bases = np.bincount(np.asarray(iv_group, np.int64), weights=span, minlength=ng).astype(np.int64)
+    n_bases[ng - 1] = int(np.sum(np.asarray(lengths, np.int64))) - int(span.sum())
+    out = io.StringIO()
+    out.write("Index\tGroup\tRegions\tBases\tReads\n")
+    for g, name in enumerate(groups):
+        out.write("%d\t%s\t%d\t%d\t%d\n" % (g, name, int(n_regions[g]), int(n_bases[g]), int(kept[g])))
+    return out.getvalue()
+
+
 @dataclass
 class StratifiedTables:
     """What a stratified ``DamageEngine.finish()`` returns: ``strata`` — the block as the device holds it, one table per
@@ -262,16 +354,24 @@ class StratifiedTables:
             out.write("%d\t%s\t%d\t%d\n" % (g, name, int(n_seq[g]), self.group_kept(g)))
         return out.getvalue()
 
-    def write(self, folder, group_of_tid):
-        """The run's three files into ``folder`` from the merged block, and ``folder/by_reference``: ``groups.tsv`` and
-        one directory per group, named by its index (sequence names hold ``*``, ``:`` and ``/``), with the three files of
-        that group written by the same emitters."""
+    def write(self, folder, group_of_tid=None, subdir="by_reference", groups_text=None, usual=None):
+        """The run's three files into ``folder`` from the merged block (``usual``: from that ``TableSet`` instead), and
+        ``folder/subdir``: ``groups.tsv`` (``groups_text``; default: that of the sequence groups ``group_of_tid``) and one
+        directory per group, named by its index (sequence names hold ``*``, ``:`` and ``/``), with the three files of that
+        group written by the same emitters."""
         import pathlib
         folder = pathlib.Path(folder)
-        self.merged.write(folder)
-        sub = folder / "by_reference"
+        (self.merged if usual is None else usual).write(folder)
+        sub = folder / subdir
         sub.mkdir(parents=True, exist_ok=True)
-        (sub / "groups.tsv").write_text(self.groups_text(group_of_tid))
+        (sub / "groups.tsv").write_text(self.groups_text(group_of_tid) if groups_text is None else groups_text)
         for g in range(len(self.groups)):
             (sub / str(g)).mkdir(exist_ok=True)
             self.group(g).write(sub / str(g))
+
+    def sum_of_groups(self, groups):
+        """The ``TableSet`` of the libraries summed over the groups ``groups`` (indices) — ``TableSet.add`` on the host."""
+        total = None
+        for g in groups:
+            total = self.group(g) if total is None else total.add(self.group(g))
+        return total
