@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define MDX_ABI_VERSION 6   /* 6: mdx_set_strata, mdx_strata_groups, mdx_strata_kept, mdx_finish_merged, mdx_finish_merged_host, mdx_merged_words, mdx_lgd_copies (additions only: no structure and no existing call changed, so the number stays); mdx_fasta_index, mdx_set_reference_fasta, mdx_reference_fetch, mdx_host_threads, mdx_warm, mdx_*_patches_device, mdx_rescale_expand_device, mdx_mr_round, mdx_batch_fold, mdx_bgzf_deflate, mdx_gbam_rescale_slab / _write_rescaled / _record_name; 2: mdx_batch::seq_format, mdx_pack_seq, mdx_gbam_set_seq_format; 3: mdx_gbam_tell / _fixups, mdx_bam_seek; 4: mdx_batch::lowq (the struct grew by one pointer); 5: mdx_batch::libsort (another one), mdx_libsorts, mdx_gbam_view_flags / _set_flags */
+#define MDX_ABI_VERSION 6   /* 6: mdx_stats_loglik, mdx_stats_run, mdx_stats_pmat (additions again: the number stays); mdx_set_strata, mdx_strata_groups, mdx_strata_kept, mdx_finish_merged, mdx_finish_merged_host, mdx_merged_words, mdx_lgd_copies (additions only: no structure and no existing call changed, so the number stays); mdx_fasta_index, mdx_set_reference_fasta, mdx_reference_fetch, mdx_host_threads, mdx_warm, mdx_*_patches_device, mdx_rescale_expand_device, mdx_mr_round, mdx_batch_fold, mdx_bgzf_deflate, mdx_gbam_rescale_slab / _write_rescaled / _record_name; 2: mdx_batch::seq_format, mdx_pack_seq, mdx_gbam_set_seq_format; 3: mdx_gbam_tell / _fixups, mdx_bam_seek; 4: mdx_batch::lowq (the struct grew by one pointer); 5: mdx_batch::libsort (another one), mdx_libsorts, mdx_gbam_view_flags / _set_flags */
 
 #define MDX_OK 0
 #define MDX_ERR_ARG (-1)          /* bad argument / unsupported configuration */
@@ -673,6 +673,53 @@ int mdx_gsam_view_set_flags(mdx_gsam *g, const uint16_t *flags, int64_t n);
 /* a record the kernel counts has come by without qualities so far (under mdx_gsam_set_min_basequal; main.py:185-192) */
 int mdx_gsam_missing_qualities(const mdx_gsam *g);
 void mdx_gsam_close(mdx_gsam *g);
+
+/* ---- The Bayesian estimate of the damage parameters on the device (additions of ABI 6): mapdamage/r/stats/ — the model of
+ * function.r, the priors and proposals of priorPropose.r, the seven Metropolis updates of postConditonal.r in the order of
+ * runGibbs, adjustPropVar between the burn-in rounds, the correcting probabilities of postPredCheck.  One wavefront per
+ * chain, any number of chains in a launch, everything in double; a chain's result depends on its own inputs alone.
+ * A table is the m x 16 matrix of readMapDamData (data.r), row-major, columns A C G T A.C A.G A.T C.A C.G C.T G.A G.C G.T
+ * T.A T.C T.G, as doubles; with it go the constant of its likelihood (the sum over rows and reference bases of
+ * lnfact(N) - sum lnfact(S), function.r:124-128, which no parameter moves), its nick vector nuVec [m] (main.r:98-148) and
+ * its base frequencies acgt [4].  A parameter vector is Theta, Rho, DeltaD, DeltaS, Lambda, LambdaRight, LambdaDisp; a trace
+ * row is that vector and LogLik.
+ * Random numbers: Philox4x32-10 with key (seed, chain id) and counter (phase, iteration, update index, draw index); words 0-1
+ * and 2-3 of a block make two uniforms ((x >> 11) + 0.5) * 2^-53, a normal is Box–Muller of the two.  Phase 0 is the start
+ * search (iteration = start, draws 0..3: the uniforms of Theta, DeltaD, DeltaS, Lambda, LambdaRight, the picks of LambdaDisp
+ * and Rho), phases 1..R the burn-in rounds (R = max(n_adjust, 1)), R + 1 the kept iterations — update index = the
+ * parameter's index, draw 0 its proposal's normal, draw 1 the uniform of the accept step —, R + 2 the correcting
+ * probabilities (iteration = draw of the posterior, draws 0..3: the row picked from the trace for Lambda, LambdaDisp,
+ * LambdaRight, LambdaDisp again, DeltaS, DeltaD, Theta, Rho).
+ *   mdx_stats_loglik   n log-likelihoods: evaluation e takes table table_of[e] and params[e][7].  -inf outside the
+ *                      parameters' ranges, logLikAll (function.r:142-161) inside, with the overhang vector of
+ *                      logLikAllOptimize (start.r:28-44).  What the start search evaluates, and the tests' window onto it.
+ *   mdx_stats_run      n_chains chains from the start search to the correcting probabilities.  trace [chain][n_iter][8],
+ *                      prop_sd [chain][7] (the proposal SDs after the last adjustment), acc [chain][8] (distinct
+ *                      consecutive values of each column / n_iter), corr [chain][m][2] (C.T, G.A of row i), start
+ *                      [chain][8] (the start the chain took and its log-likelihood; may be NULL).  Synchronous.
+ *   mdx_stats_pmat     n substitution matrices [n][16] (row = from) for in[n][6] = Theta, Rho, acgt: getPmat
+ *                      (function.r:8-64), HKY85 in closed form or (jukes_cantor != 0) Jukes–Cantor. */
+#define MDX_STATS_MAX_M 256
+typedef struct {
+    int32_t m;               /* rows of a table: 2 x --seq-length with both termini (even), else --seq-length */
+    int32_t termini;         /* 0 both, 1 5p, 2 3p */
+    int32_t fix_ti_tv;       /* --jukes-cantor */
+    int32_t same_overhangs;  /* 0 with --diff-hangs (both termini only) */
+    int32_t fix_disp;        /* 0 with --var-disp */
+    int32_t n_rand;          /* --rand (0: the start values of runGeneral.r) */
+    int32_t n_adjust;        /* --adjust */
+    int32_t n_burn;          /* --burn, >= 1 */
+    int32_t n_iter;          /* --iter, >= 1 */
+    int32_t n_pred;          /* draws behind a correcting probability (10000 in postPredCheck) */
+    uint32_t seed;           /* --stats-seed */
+    int32_t reserved;
+} mdx_stats_config;
+int mdx_stats_loglik(int32_t device, const mdx_stats_config *cfg, int32_t n_tables, const double *tables, const double *lnfact,
+                     const double *nu, const double *acgt, int64_t n, const int32_t *table_of, const double *params, double *loglik);
+int mdx_stats_run(int32_t device, const mdx_stats_config *cfg, int32_t n_chains, const double *tables, const double *lnfact,
+                  const double *nu, const double *acgt, const uint32_t *chain_id, double *trace, double *prop_sd, double *acc,
+                  double *corr, double *start);
+int mdx_stats_pmat(int32_t device, int64_t n, const double *theta_rho_acgt, int32_t jukes_cantor, double *out);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,7 @@ EXPORTS = (
     "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
     "mdx_set_strata", "mdx_set_strata_regions", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
+    "mdx_stats_loglik", "mdx_stats_run", "mdx_stats_pmat",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*

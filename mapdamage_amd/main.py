@@ -94,6 +94,14 @@ def build_parser():
                                ("--iter", int, 50000), ("--seq-length", int, 12)):
         g.add_argument(flag, type=typ, default=default)
     g.add_argument("--termini", choices=("5p", "3p", "both"), default="both")
+    g.add_argument("--stats", action="store_true",
+                   help="estimate the damage parameters once the tables are written (mapdamage/r/stats/ on the GPU, one chain per "
+                        "table set in one launch): Stats_out_MCMC_iter.csv, ..._iter_summ_stat.csv and ..._correct_prob.csv; needs "
+                        "one of --fix-nicks, --use-raw-nick-freq and --single-stranded.  With --by-reference / --reference-groups / "
+                        "--regions / --region-groups every group gets a chain of its own and its three files beside its tables")
+    g.add_argument("--stats-seed", type=int, default=0, metavar="N",
+                   help="seed of the estimate's random numbers (Philox4x32-10; a chain is reproducible from it)")
+    g.add_argument("--stats-chain", type=int, default=0, help=argparse.SUPPRESS)     # key word of the run's own chain (group g: g + 1)
     for flag in ("--forward", "--reverse", "--var-disp", "--jukes-cantor", "--diff-hangs", "--fix-nicks",
                  "--use-raw-nick-freq", "--single-stranded", "--theme-bw", "--stats-only", "--no-stats",
                  "--check-R-packages"):
@@ -161,10 +169,34 @@ def build_parser():
 def parse_args(argv):
     parser = build_parser()
     o = parser.parse_args(argv)
-    if o.plot_only or o.stats_only or o.rescale or o.check_R_packages:
-        parser.error("plotting and the Bayesian estimation are not part of this engine; run them with the "
-                     "reference on the emitted tables (--rescale-only works from an existing "
-                     "Stats_out_MCMC_correct_prob.csv)")
+    if o.plot_only or o.check_R_packages:
+        parser.error("plotting is not part of this engine; run it with the reference on the emitted tables")
+    if o.forward:                                                       # config.py:255-266: both set --termini
+        o.termini = "5p"
+    if o.reverse:
+        o.termini = "3p"
+    o.want_stats = o.stats or o.stats_only or o.rescale
+    if o.want_stats:
+        from .stats import StatsError, StatsOptions
+        if o.no_stats:
+            parser.error("--no-stats contradicts --stats / --stats-only / --rescale")
+        if o.rescale_only:
+            parser.error("--rescale-only works from an existing Stats_out_MCMC_correct_prob.csv; it runs no estimate")
+        if o.stats_only and (o.stats or o.rescale):
+            parser.error("--stats-only works from an existing folder; it excludes --stats and --rescale")
+        try:
+            o.stats_options = StatsOptions.from_args(o)
+        except StatsError as error:
+            parser.error(str(error))
+        if o.seq_length > o.length and not o.stats_only:
+            parser.error("--seq-length must not be greater than --length: the tables hold no position beyond it")
+    if o.stats_only:
+        if not o.folder:
+            parser.error("--folder required when using --stats-only")
+        if not o.jukes_cantor and not (o.folder / "dnacomp_genome.csv").is_file() and not o.ref:
+            parser.error("--stats-only needs dnacomp_genome.csv in the folder, or --reference to make it from")
+        o.no_stats = False
+        return o
     if o.by_reference and o.reference_groups:
         parser.error("--by-reference and --reference-groups exclude each other")
     if (o.by_reference or o.reference_groups) and o.rescale_only:
@@ -190,6 +222,8 @@ def parse_args(argv):
         if o.rescale_only:
             parser.error("--rescale-only cannot read its input from stdin or a pipe (it reads the file more than once); "
                          "write it to a file")
+        if o.rescale:
+            parser.error("Cannot build model and rescale in one run when input is a pipe")          # main.py:133-136
     if not o.ref:
         parser.error("--reference FASTA file not specified")
     if o.downsample is not None:
@@ -206,8 +240,8 @@ def parse_args(argv):
     if not o.folder:
         o.folder = Path(o.filename.stem + ".mapDamage")
     o.folder.mkdir(parents=True, exist_ok=True, mode=0o750)
-    o.no_stats = True
-    if not o.rescale_out and o.rescale_only:
+    o.no_stats = not o.want_stats
+    if not o.rescale_out and (o.rescale or o.rescale_only):
         o.rescale_out = o.folder / (o.filename.stem + ".rescaled.bam")
     if o.rescale_length_3p is None:
         o.rescale_length_3p = o.seq_length
@@ -269,6 +303,64 @@ def rescale_qual(options):
     for line in summary.log_lines():                                     # rescale.py:361-362
         logger.info("%s", line)
     logger.debug("Rescaling completed in %f seconds", time.time() - start)
+    return 0
+
+
+def _base_frequencies(options, ref, n_contig, device):
+    """A, C, G, T of ``dnacomp_genome.csv`` (main.py:96-103, 248-250): read when the folder holds the file, otherwise counted
+    on the device from the reference and written.  None with --jukes-cantor (main.r:33-35)."""
+    from . import composition
+    from .stats import read_base_freqs
+    path = options.folder / "dnacomp_genome.csv"
+    if not path.is_file() or ref is not None:
+        if ref is None:
+            # (--stats-only: every sequence of the FASTA, in the order of its index)
+            if not is_plain_gzip(options.ref):
+                ensure_fasta_index(options.ref)
+            names = list(read_fasta_index(str(options.ref) + ".fai"))
+            ref, n_contig = reference_for_bam(options.ref, names), len(names)
+        with DamageEngine([("*", "*")], options.length, options.around, 0, device=device) as engine:
+            engine.set_reference(ref)
+            composition.write_base_comp(engine.genome_composition(n_contig), path)
+    return None if options.stats_options.jukes_cantor else read_base_freqs(path)
+
+
+def _group_has_data(folder):
+    """The part of check_table_and_warn_if_dmg_freq_is_low that refuses a table (statistics.py), without its log lines."""
+    from .statistics import _position_one_totals
+    try:
+        totals = _position_one_totals(folder / "misincorporation.txt")
+    except (OSError, KeyError, ValueError, IndexError):
+        return False
+    return totals is not None and totals[("5p", "C")] != 0 and totals[("3p", "G")] != 0
+
+
+def bayesian_estimates(options, logger, ref=None, n_contig=0, device=0):
+    """The estimate of the folder's tables and of every group directory beside them (by_reference/<index>,
+    by_region/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
+    from .stats import StatsError, estimate_folders
+    start = time.time()
+    try:
+        acgt = _base_frequencies(options, ref, n_contig, device)
+        folders, chains = [options.folder], [options.stats_chain]
+        for sub in ("by_reference", "by_region"):
+            if not (options.folder / sub / "groups.tsv").is_file():
+                continue
+            index = 0
+            while (options.folder / sub / str(index) / "misincorporation.txt").is_file():
+                group = options.folder / sub / str(index)
+                if _group_has_data(group):
+                    folders.append(group)
+                    chains.append(index + 1)
+                else:
+                    logger.info("Group %d of %s: too few reads for the Bayesian estimate (no C at the first 5' position or no "
+                                "G at the first 3' position); skipped", index, sub)
+                index += 1
+        estimate_folders(folders, acgt, options.stats_options, chains, device, logger)
+    except (StatsError, MdxError, OSError, ValueError) as error:
+        logger.error("Bayesian estimate failed: %s", error)
+        return 1
+    logger.debug("Bayesian estimates made in %f seconds", time.time() - start)
     return 0
 
 
@@ -628,6 +720,22 @@ def main(argv):
     except SystemExit as error:
         return int(error.code or 0) and 1
     import os
+    if options.stats_only:
+        # mapdamage/main.py:93-111: from the tables of an existing folder; one process, one GPU
+        if int(os.environ.get("RANK", "0")) != 0:
+            return 0
+        handler = logging.FileHandler(options.folder / "Runtime_log.txt")
+        handler.setFormatter(logging.Formatter(_LOG_FORMAT))
+        logging.getLogger().setLevel(options.log_level)
+        logging.getLogger().addHandler(handler)
+        try:
+            if not check_table_and_warn_if_dmg_freq_is_low(options.folder):
+                logger.error("Cannot use the Bayesian estimation, terminating the program")
+                return 1
+            return bayesian_estimates(options, logger, device=options.device)
+        finally:
+            logging.getLogger().removeHandler(handler)
+            handler.close()
     if options.rescale_only:
         # the rescaling pass rewrites one BAM file in file order (rescale.py:285-365): one process, one GPU — under a launcher
         # that started several ranks the others leave at once instead of waiting in a process group for rank 0's whole pass
@@ -776,7 +884,20 @@ def main(argv):
         if options.freq_files:
             (options.folder / "5pCtoT_freq.txt").write_text(tables.damage_frequency_text("5p", options.readplot))
             (options.folder / "3pGtoA_freq.txt").write_text(tables.damage_frequency_text("3p", options.readplot))
-        check_table_and_warn_if_dmg_freq_is_low(options.folder)
+        usable = check_table_and_warn_if_dmg_freq_is_low(options.folder)
+        if not options.no_stats:
+            # main.py:241-257
+            if not usable:
+                logger.error("Cannot use the Bayesian estimation, terminating the program")
+                return 1
+            if bayesian_estimates(options, logger, ref, len(reader.handle.header.references), ranks.device):
+                return 1
+            stages.mark("estimates")
+            if options.rescale:
+                reader.close()
+                reader = None
+                if rescale_qual(options):
+                    return 1
         logger.info("Successful run")
         logger.debug("Run completed in %f seconds", time.time() - start_time)
         stages.mark("files written")
