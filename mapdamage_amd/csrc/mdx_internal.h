@@ -1,5 +1,5 @@
 // Internal interface between the C-ABI layer (mdx_capi.cpp) and the gfx950 kernels
-// (mdx_kernels.hip).  Not installed; the public boundary is include/mdx.h.
+// (mdx_kernels.hip, mdx_rescale.hip).  Not installed; the public boundary is include/mdx.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -447,6 +447,7 @@ struct MdxRescaleArgs {
     int row_base;               // first row of subs_part the walk kernel's blocks write (set by mdx_k_rescale)
     int copy_qual;              // set by mdx_k_rescale: rescale_kernel copies qual to qual_out tile by tile
 };
+// (mdx_rescale.hip) the launches of the rescale kernels
 void mdx_k_rescale(const MdxRescaleArgs &a, int n_cu, hipStream_t s);
 // qual_out = qual with the n_patch entries of a patch list applied (qual_out may be qual: in place)
 void mdx_k_rescale_expand(const uint8_t *qual, uint8_t *qual_out, int64_t n_bases, const unsigned long long *patch,

@@ -37,70 +37,18 @@
 // strand step of main.py:200-205 (reverse-complement + flank swap) becomes a fixed permutation
 // applied once by finalize_kernel.  The oracle (oracle/mdx_oracle.c) builds and reverses the
 // strings literally instead, so the two share no derivation.
-#include "mdx_internal.h"
+// The kernels that rescale qualities on their own (rescale_kernel and those behind it) are in mdx_rescale.hip; the types and
+// the few helpers both units use, in mdx_device.h.
+#include "mdx_device.h"
 
 #include <type_traits>
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "gfx950 only: the s_waitcnt immediates (0xC07F = lgkmcnt(0), 0x0F70 = vmcnt(0)) and the inline assembly below are gfx9 encodings"
-#endif
-
-typedef uint8_t u8;
-typedef int8_t i8;
-typedef uint16_t u16;
-typedef uint32_t u32;
-typedef u32 u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x2 __attribute__((aligned(1))) u32x2_u;
-typedef u32x2 __attribute__((aligned(4))) u32x2_a4;
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 __attribute__((aligned(1))) u32x4_u;
-typedef u32 __attribute__((aligned(1))) u32_u;
-typedef u16 __attribute__((aligned(1))) u16_u;
-struct __attribute__((packed, aligned(4))) u32x3 { u32 x, y, z; };   // global_load_dwordx3
-typedef u32 u32v3 __attribute__((ext_vector_type(3)));
-typedef u32v3 __attribute__((aligned(4))) u32v3_u;
-// MDX_NT=1: the operands streamed once (SEQ, qualities, the per-record columns) loaded non-temporal, so that their lines
-// are the first to leave the XCD's L2 in favour of the reference (two random windows per record: 58 % of what crosses
-// the fabric for the survey's genome).  Measured (r03c): L2 misses -2 %, kernel time unchanged on the 10 Mb genome and
-// 7 % worse on a 3 Gb one (the loads skip the vector L1) — off.
-#ifndef MDX_NT
-#define MDX_NT 0
-#endif
-
-// The quality copy of the fused kernel (16-byte units at 16-byte-aligned addresses): the copy is written once and not
-// read again by this kernel: MDX_CP_NT & 1 stores it non-temporal, so that it does not take the reference's place in the
-// L2, MDX_CP_NT & 2 loads the source likewise — measured: 3.43 ms either way against 3.44 (off).
-#ifndef MDX_CP_NT
-#define MDX_CP_NT 0
-#endif
+// the quality copy of the fused kernel: 16-byte units at 16-byte-aligned addresses
 typedef u32x4 __attribute__((aligned(16))) u32x4_a;
-__device__ __forceinline__ void cp_store(u8 *p, const u32x4 v) {
-#if MDX_CP_NT & 1
-    __builtin_nontemporal_store(v, (u32x4_a *)p);
-#else
-    *(u32x4_a *)p = v;
-#endif
-}
-__device__ __forceinline__ u32x4 cp_load(const u8 *p) {
-#if MDX_CP_NT & 2
-    return __builtin_nontemporal_load((const u32x4_a *)p);
-#else
-    return *(const u32x4_a *)p;
-#endif
-}
-__device__ __forceinline__ u32x3 ld12_stream(const u8 *p) {
-    u32x3 r;
-#if MDX_NT
-    const u32v3 t = __builtin_nontemporal_load((const u32v3_u *)p);
-    r.x = t.x; r.y = t.y; r.z = t.z;
-#else
-    r = *(const u32x3 *)p;
-#endif
-    return r;
-}
-typedef unsigned long long u64;
-typedef u64 __attribute__((aligned(1))) u64_u;
-typedef long long i64;
+__device__ __forceinline__ void cp_store(u8 *p, const u32x4 v) { *(u32x4_a *)p = v; }
+__device__ __forceinline__ u32x4 cp_load(const u8 *p) { return *(const u32x4_a *)p; }
+// the dword-aligned twelve bytes a window of a streamed column (SEQ, qualities) is funnelled out of
+__device__ __forceinline__ u32x3 ld12_stream(const u8 *p) { return *(const u32x3 *)p; }
 
 #ifndef MDX_BLOCK
 #define MDX_BLOCK 768                   // 12 wavefronts; two blocks per CU share the 160 KiB LDS
@@ -111,42 +59,17 @@ typedef long long i64;
 #ifndef PIPE_DEPTH
 #define PIPE_DEPTH 4                    // wavefront steps in flight of the complete runs (register sets of the load pipeline)
 #endif
-#ifndef MDX_ENT_AHEAD
-#define MDX_ENT_AHEAD 0                 // staging entries read one fill ahead
-#endif
-#ifndef MDX_PK_ENT_AHEAD
-#define MDX_PK_ENT_AHEAD 0              // ... in the packed kernels (measured: +-1 % on every workload — the other wavefronts cover that wait)
-#endif
 #ifndef MDX_PD_G
 #define MDX_PD_G 2                      // steps in flight of the single-indel runs
 #endif
 #ifndef MDX_PD_P
 #define MDX_PD_P 3                      // ... and of the runs of partial entries
 #endif
-#ifndef MDX_QPREFETCH
-#define MDX_QPREFETCH 1                 // MASK: the quality windows requested with the other two, PIPE_DEPTH steps ahead
-#endif
-#ifndef MDX_PK_FASTP
-#define MDX_PK_FASTP 1                  // the partial steps of the plain packed kernels: see FIDP
-#endif
-#ifndef MDX_PK_SIP
-#define MDX_PK_SIP 1                    // the packed kernels' phase 1 makes the entries of single-indel records itself (see SIP)
-#endif
-#ifndef MDX_PK_FASTIDX
-#define MDX_PK_FASTIDX 1                // the packed kernels' complete steps: the staging entry's LDS address as add + min (a slot past its strand's
-#endif                                  // last entry reads that last entry and is masked out), the event's place from two shift-adds
 #ifndef MDX_PK_PD
 #define MDX_PK_PD 4                     // ... and of the packed kernel's complete runs
 #endif
 #ifndef MDX_PK_PD_P
 #define MDX_PK_PD_P 4                   // ... and of its runs of partial entries (four: its groups are added in pairs)
-#endif
-#ifndef MDX_PK_PTILE
-#define MDX_PK_PTILE 1                  // the packed kernels count a tile's partial records in the tile loop (0: through the wavefront's list behind it; the fused one always does)
-#endif
-#ifndef MDX_PKF_PTILE
-#define MDX_PKF_PTILE 0                 // ... and the packed fused kernel: no — through its list, rescaled by the list's passes (the run in the
-                                        // tile loop cost the kernel's registers 3 % on config 5, which has no such record)
 #endif
 #ifndef MDX_PKM_PD
 #define MDX_PKM_PD 3                    // ... and with --min-basequal
@@ -167,9 +90,6 @@ typedef long long i64;
 #ifndef MDX_PD_G_ML
 #define MDX_PD_G_ML 1                   // ... and of single-indel entries
 #endif
-#ifndef MDX_PREFIX
-#define MDX_PREFIX 1                    // plain prefixes of gapped records through the fast step
-#endif
 #define EVQ_CAP 64                      // rare-event queue capacity per wavefront
 #define EVQ_BYTES (EVQ_CAP * 20)        // per wavefront: S[64] u32x2 | R[64] u32x2 | W[64] u32
 // The fused kernel (one 1024-thread block per CU: the LDS has the room) holds the events of a whole run, as a rule: it never
@@ -179,7 +99,6 @@ typedef long long i64;
 #define MDX_PK_EVQ_BYTES (MDX_PK_QCAP * 20)   // the packed kernel's: {read 8 B, reference 8 B}[QCAP] | W[QCAP]
 #define MDX_PK_TAB_BYTES 1024                 // ... and per block: the lanes' read-column masks (64 x 8 B), the symbol-pair table (256 x 2 B)
 #define COL_S 24
-#define ERR_BAD_READ 6
 // symbol classes on the device: 0..3 = A,C,T,G ((ascii >> 1) & 3), 4 = '-', 5 = anything else
 #define SYM_GAP 4
 #define SYM_OTHER 5
@@ -225,9 +144,7 @@ int mdx_k_lgd_lds(int L, int A, int lgd_max) { return mdx_c_lgd_lds(L, A, lgd_ma
 // The fused tabulate + rescale kernel (tabulate_kernel<.., RS>): one block of 1024 threads per CU — 16 wavefronts with
 // 128 registers each instead of 24 with 80 (measured with the plain kernel: +3 % on config 3) — because its image does
 // not fit twice: behind the plain image [second TC table, 256-byte aligned][4 words][lookup table][terms]
-#ifndef MDX_FUSE_BLOCK
-#define MDX_FUSE_BLOCK 1024
-#endif
+// (MDX_FUSE_BLOCK, its block: mdx_device.h)
 #ifndef MDX_FUSE_WPS
 #define MDX_FUSE_WPS 4
 #endif
@@ -240,9 +157,6 @@ int mdx_k_lgd_lds(int L, int A, int lgd_max) { return mdx_c_lgd_lds(L, A, lgd_ma
 #ifndef MDX_FUSE_PD
 #define MDX_FUSE_PD 4                   // steps in flight of the complete runs in the fused kernel
 #endif
-#ifndef MDX_FUSE_CP2
-#define MDX_FUSE_CP2 1                  // the passes of the quality copy behind the first: two units per lane and round trip
-#endif
 #define MDX_FUSE_RSQ 192                // per wavefront: transitions of fused records waiting for their qualities (8 bytes each)
 #define MDX_FUSE_MRM 72                 // per wavefront: one 64-bit word per staging entry (the MR terms of its record)
 int mdx_k_fuse_block_threads() { return MDX_FUSE_BLOCK; }
@@ -252,14 +166,8 @@ int mdx_k_fuse_block_threads() { return MDX_FUSE_BLOCK; }
 #ifndef MDX_PK_BLOCK
 #define MDX_PK_BLOCK 1024               // the largest block of the packed kernels (their launch bound): see MdxPkConfig
 #endif
-#ifndef MDX_PK_DEFER
-#define MDX_PK_DEFER 1                  // the plain packed kernel adds its groups of four steps in pairs (tabulate_kernel: HS)
-#endif
 #ifndef MDX_PK_STEAL
 #define MDX_PK_STEAL 2                    // pools a wavefront of the packed kernels asks for tiles once its own is empty (0: none)
-#endif
-#ifndef MDX_PK_DEFER_ML
-#define MDX_PK_DEFER_ML 1               // ... the kernel of the launches over several libraries too (round 6: it has the registers)
 #endif
 #ifndef MDX_PK_WPS
 #define MDX_PK_WPS 4
@@ -411,18 +319,6 @@ __device__ __forceinline__ void bump_n(u32 *lds, u64 *raw, int idx, u32 n) {
     else atomicAdd(&raw[idx], (u64)n);
 }
 
-__device__ __forceinline__ void flag_error(u64 *err, i64 read, int code) {
-    atomicMin(err, ((u64)read << 8) | (u64)code);
-}
-
-__device__ __forceinline__ int rl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-__device__ __forceinline__ int mbcnt64(u64 m, int base) {
-    return (int)__builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, (u32)base));
-}
-// Rescaling in patch mode (MdxFuse::patch / MdxRescaleArgs::patch): a quality byte that changes (rescale.py:228-246) becomes
-// an entry of the launch's list — index of the byte in the column | new Phred << 32 — instead of a store into a copy of the
-// column.  The lanes that have one at the same time append together: one atomic for all of them (called under divergence it
-// covers the active lanes — the ballot's).
 // the kernel arguments where they lie — in the constant address space: what is read through such a pointer comes by a scalar
 // load at the point of use (through a generic pointer it would be a vector load and a round trip)
 typedef const __attribute__((address_space(4))) MdxTabArgs *karg_p;
@@ -490,31 +386,6 @@ __device__ __forceinline__ void pfl_store_b128(const void *base, const u32 off, 
     asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_nop 1" :: "v"(off), "v"(v), "s"(base) : "memory");
 }
 
-__device__ __forceinline__ void patch_put(unsigned long long *__restrict__ patch0, unsigned long long *__restrict__ n_patch0, long long cap,
-                                          int parts, bool on, u32 idx, u32 newq) {
-    const u64 m = __ballot(on);
-    if (m == 0) return;
-    // (the block's part of the list: a counter per part — one list for the whole launch is one address all wavefronts queue at)
-    const u32 part = blockIdx.x & (u32)(parts - 1);
-    unsigned long long *__restrict__ patch = patch0 + (size_t)part * (size_t)cap, *__restrict__ n_patch = n_patch0 + part;
-    const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)m) - 1);
-    u64 base = 0;
-    if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(n_patch, (unsigned long long)__popcll(m));
-    const u64 b = (u64)(u32)rl((int)(u32)base, leader) | ((u64)(u32)rl((int)(u32)(base >> 32), leader) << 32);
-    if (on) {
-        const u64 at = b + (u64)mbcnt64(m, 0);
-        if ((long long)at < cap) patch[at] = (u64)idx | ((u64)newq << 32);
-    }
-}
-
-// bytes [lo, hi) of a 64-bit word, the range clamped to [0, 8)
-__device__ __forceinline__ u64 byte_range(int lo, int hi) {
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > 8 ? 8 : hi;
-    if (hi <= lo) return 0ull;
-    const u64 upto = hi >= 8 ? ~0ull : ((1ull << (8 * hi)) - 1ull);
-    return upto & ~((1ull << (8 * lo)) - 1ull);
-}
 // static byte masks of the lane (side, 8 m) of a record (MdxDims): vm = the byte is a task of a complete
 // record, em = the byte is a read column (its read byte is compared; a flank byte is only classified)
 __device__ __forceinline__ void lane_masks(const MdxDims &d, int side, int m8, u64 &vm, u64 &em) {
@@ -597,11 +468,7 @@ __device__ __forceinline__ void direct8(u32 *lds, u32 r_lo, u32 r_hi, u32 base_b
 // element idx of a column, the byte offset computed in 32 bits (batches hold fewer than 2^30 records)
 template <class T>
 __device__ __forceinline__ T ld32(const T *base, u32 idx) {
-#if MDX_NT
-    return __builtin_nontemporal_load((const T *)((const char *)base + (size_t)(idx * (u32)sizeof(T))));
-#else
     return *(const T *)((const char *)base + (size_t)(idx * (u32)sizeof(T)));
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1001,7 +868,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     // Paired groups (the kernels with the registers for them): a group of four steps leaves one word of weight 4 per dword;
     // rippled through planes 2..7 that is twelve instructions.  Two groups one after the other hand their two words to one
     // adder into plane 2, and its carry ripples from plane 3: fourteen for both.
-    constexpr bool HS = PK && MDX_PK_DEFER && !MASK && !RS && (!ML || MDX_PK_DEFER_ML);
+    constexpr bool HS = PK && !MASK && !RS;
     // fold the planes into the block's TC table, PK layout: word [base k][64 j + lane]; per bit position s of the bytes of
     // a plane, the four counters of bits s, s + 8, s + 16, s + 24 are gathered as the bytes of one word
     // (inlined at every call site: a call would take the planes through memory)
@@ -1072,9 +939,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         const MdxTabArgs *kp = (const MdxTabArgs *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(kp));
         const u32 idx = t.y & 0x7FFFu;
-#ifndef MDX_RSABL_NOATOM
         atomicAdd(&kp->rs.subs_part[(size_t)blockIdx.x * rs_ncnt + idx + q], 1u);
-#endif
         if (t.y & 0x8000u) {
             const u32 newq = l_lut[idx - 752u + q];
             if (kp->rs.patch) patch_put(kp->rs.patch, kp->rs.n_patch, kp->rs.patch_cap, kp->rs.patch_parts, newq != q, t.x, newq);
@@ -1095,11 +960,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         for (int k = 0; k < MDX_FUSE_RSQ / 64; k++) {
             const u32 i = (u32)lane + 64u * k;
             q[k] = 0xFFu;
-#ifdef MDX_RSABL_NOQLD
-            if (i < n) { t[k] = rsq[i]; q[k] = 30u + (t[k].x & 7u); }
-#else
             if (i < n) { t[k] = rsq[i]; q[k] = qin[t[k].x]; }
-#endif
         }
         // (every vector-memory operation of the wavefront so far is complete — the qualities just requested, and the stores
         // of the tile's quality copy, which the new qualities must not overtake)
@@ -1249,9 +1110,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                         // what the column really is (rare_column): the read base, and a substitution / indel
                         if (sc < 4) atomicAdd(&lds[b_cmp + spc * 4 + sc], 1u);
                         if (col != 31) atomicAdd(&lds[b_mis + __mul24(sp, 25) + col], 1u);
-#ifndef MDX_RSABL_NOEV
                         if (RS && rsev) rs_event4(rent, (int)((w >> 21) & 0x7Fu), rev, side, p, pc, g, (u32)(s64 >> sh) & 15u, (u32)(r64 >> sh) & 15u);
-#endif
                     }
                     };
                     if (__ballot(del)) nibbles(std::true_type{});
@@ -1309,9 +1168,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 }
                 if ((em >> sh) & 1ull) {
                     rare_column<USE_LDS>(lds, raw, b_mis, b_cmp, L, side, p, pc, sb, (int)(i8)rb, MASK && ((w >> jb) & 1u));
-#ifndef MDX_RSABL_NOEV
                     if (RS && rsev) rs_event(rent, (int)(w & 0x7Fu), rev, side, p, sb, rb);
-#endif
                 }
             }
         }
@@ -1409,18 +1266,8 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
             }
         };
         if (QM) {
-#if MDX_QPREFETCH
             // (requested by fill(), with the other two windows)
             q12_ = st.q12; qo_ = st.so - c_so + c_qo;
-#else
-            // the quality window is requested here, at the start of the step that uses it, not a step or two ahead like
-            // the other two: three more registers per step in flight are more than the kernel has (the hot loop
-            // spilled), and what a step does before it needs the qualities covers part of the latency.  Records that
-            // cannot be masked — no qualities, or the caller's hint — read one fixed line instead of their window.
-            const u32 qo = st.so - c_so + c_qo;
-            const u32x3 q12 = *(const u32x3 *)(qualW + ((st.pk & 0x40000000u) ? (qo & ~3u) : 0u));
-            q12_ = q12; qo_ = qo;       // (funnelled out where the qualities are first needed: the wait sits there)
-#endif
         }
         // event word of this lane (without lane and quality bits; RS: with the staging index)
         u32 evw = st.pk & (RS ? 0xBF03FF7Fu : 0xBF03FF00u);
@@ -1598,12 +1445,12 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 // entry's LDS address is min(first + 16 H k, last entry of the lane's strand) — the dynamic LDS starts at address 0.
                 // A slot past its strand's last entry reads that entry, or the run's first when the strand has none, and is
                 // masked out by the step (actm))
-                constexpr bool FIDX = MDX_PK_FASTIDX && KIND == STEP_C && !RS;
+                constexpr bool FIDX = KIND == STEP_C && !RS;
                 // (FIDP — the partial steps of the kernels with the registers for it: the same addressing, the slot's being
                 // past its strand's last entry from one compare of the address; and the lane's nibble mask, a table lookup by a
                 // value of the entry, requested by the fill — four steps ahead of the step that wants it — instead of by the step,
                 // which waited for it)
-                constexpr bool FIDP = MDX_PK_FASTIDX && MDX_PK_FASTP && KIND == STEP_P && !RS && !MASK;
+                constexpr bool FIDP = KIND == STEP_P && !RS && !MASK;
                 const u32 stg_a = (u32)(size_t)(lds_u4 *)stg;
                 const int last_l = e0 + (p_strand ? nP_ : 0) + (p_strand ? nM_ : nP_) - 1;
                 const u32 ent_a0 = stg_a + 16u * (u32)base_l, ent_cap = stg_a + 16u * (u32)(last_l > e0 ? last_l : e0);
@@ -1612,9 +1459,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 // (one <3 x i32> load per operand: a struct of three words is taken apart and put together again as the
                 // vectorizer likes — two overlapping dwordx2 loads at times)
                 struct St16 { u32v3 s, r; u32 sa, ra, pk, aux, aux2; int k; bool valid; u64 mk; };
-                // (MDX_PK_ENT_AHEAD: the staging entry of a step is read from the LDS one fill ahead — LDS operations return in
-                // order, so a fill that reads its own entry waits, in front of its window loads, for that read and for the
-                // event writes of the step just counted)
                 auto ent_index = [&](const int kk, bool &act) -> int {
                     const int k = kk < nsteps4 ? kk : nsteps4 - 1;
                     act = true;
@@ -1625,9 +1469,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     }
                     return idx;
                 };
-#if MDX_PK_ENT_AHEAD
-                uint4 ent_next = make_uint4(0u, 0u, 0u, 0u);
-#endif
                 auto fill16 = [&](St16 &st) {
                     st.valid = kf < nsteps4;
                     const int k = st.valid ? kf : nsteps4 - 1;
@@ -1635,12 +1476,9 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     bool act = true;
                     int idx = 0;
                     u32 ref_copy = 0u;
-                    if (!(FIDX || FIDP) || MDX_PK_ENT_AHEAD) idx = ent_index(kf, act);
+                    if (!(FIDX || FIDP)) idx = ent_index(kf, act);
                     kf++;
                     st.k = k;
-#if MDX_PK_ENT_AHEAD
-                    const uint4 ent = ent_next;
-#else
                     uint4 ent;
                     if constexpr (FIDP) {
                         const u32 ad = ent_a0 + (u32)(H16 * k);
@@ -1659,7 +1497,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                         // 0, or 2 GiB: MdxTabArgs::ref2)
                         ref_copy = e_.w;
                     } else ent = stg[idx];
-#endif
                     const u32 t = ent.z & c_cm;
                     u32 ro = ent.x + c_ro + t;
                     u32 so = ro + ent.y;
@@ -1728,9 +1565,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     st.r = *(const u32v3_u *)(refW + (((ro >> 1) & 0x7FFFFFFCu) | ref_copy));
                     st.s = *(const u32v3_u *)(seqW + ((so >> 1) & ~3u));
                     st.pk = KIND == STEP_C ? 0u : ent.w;
-#if MDX_PK_ENT_AHEAD
-                    { bool a_; ent_next = stg[ent_index(kf, a_)]; }
-#endif
                 };
                 // one step: X = the nibbles this step counts (one-hot codes: the increments themselves).  A step whose events do
                 // not fit the queue does nothing and reports itself (ovf, kredo): the run stops behind the group, drains and
@@ -1849,7 +1683,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                             return;
                         }
                         if (ev) {
-#if MDX_PK_FASTIDX
                             // (the event's place among this step's events, the queue's fill in the scalar part of both addresses)
                             const u32 slot = (u32)mbcnt64(mm, 0);
                             // (kept apart: the sum of slot and fill would be a vector add)
@@ -1857,15 +1690,9 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                                       ea_s = (u32)__builtin_amdgcn_readfirstlane((int)(qE_a + 4u * (u32)qcount));
                             *(lds_u4 *)(size_t)((slot << 4) + qa_s) = u32x4{s_lo, s_hi, r_lo, r_hi};
                             *(lds_u1 *)(size_t)((slot << 2) + ea_s) = evw;
-#else
-                            const int slot = mbcnt64(mm, qcount);
-                            qQ[slot] = make_uint4(s_lo, s_hi, r_lo, r_hi);
-                            qE[slot] = evw;
-#endif
                         }
                         qcount += n;
                     }
-#ifndef MDX_RSABL_NOBC
                     if (RS) {
                         // the reference bases of a fused record's columns, by class (a code is one-hot: four population counts
                         // per dword), in this lane's own counters — its slot fixes the strand
@@ -1878,7 +1705,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                         bcT += __builtin_popcount(y_lo & 0x44444444u) + __builtin_popcount(y_hi & 0x44444444u);
                         bcG += __builtin_popcount(y_lo & 0x88888888u) + __builtin_popcount(y_hi & 0x88888888u);
                     }
-#endif
                     if (MASK && KIND == STEP_GD && __ballot(ymk != 0ull)) {
                         // (the masked read bases behind the deletion: CMP[column - g][base], like the pass below)
                         const int g = (int)(st.aux2 & 7u);
@@ -1972,9 +1798,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 for (int kstart = 0;;) {
                     kf = kstart;
                     ovf = false;
-#if MDX_PK_ENT_AHEAD
-                    { bool a_; ent_next = stg[ent_index(kf, a_)]; }
-#endif
 #pragma unroll
                     for (int dd = 0; dd < PD4; dd++) fill16(st[dd]);
                     if (pfl && pfl_due != 0xFFFFFFFEu) {
@@ -2013,11 +1836,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 else if (qcount >= 64) drain_all(qcount & 63);
                 return;
             }
-#if MDX_ENT_AHEAD
-            // (the staging entry of a step is read from the LDS one fill ahead: its latency — behind the eight table
-            // updates of the step just counted — is off the path to the window loads)
-            uint4 ent_next = stg[e0 + c_slot];
-#endif
             // fill() always issues its loads (past the last step it re-reads it), so the number of
             // loads in flight is static and the waits before count() are counted ones
             auto fill = [&](Stage &st) {
@@ -2028,15 +1846,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 nv = nv > R ? R : nv;
                 st.lim = nv * G;
                 st.k = k;
-#if MDX_ENT_AHEAD
-                const uint4 ent = ent_next;
-                {
-                    const int kn = kf < nsteps ? kf : nsteps - 1;
-                    ent_next = stg[e0 + kn * R + c_slot];
-                }
-#else
                 const uint4 ent = stg[e0 + k * R + c_slot];
-#endif
                 const u32 t = ent.z & c_cm;
                 u32 ro = ent.x + c_ro + t;
                 u32 so = ent.y + c_so + t;
@@ -2086,13 +1896,11 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 // (RS: the low byte — n0 - nq of a gapped entry, read above — makes room for the entry's place in the
                 // staging area, which an event of a fused record hands to drain_all)
                 st.pk = RS ? ((ent.w & 0xFFFFFF00u) | (u32)(e0 + k * R + c_slot)) : ent.w;
-#if MDX_QPREFETCH
                 if (QM) {
                     // records that cannot be masked — no qualities, or the caller's hint — read one fixed line instead
                     const u32 qo = so - c_so + c_qo;
                     st.q12 = ld12_stream(qualW + ((ent.w & 0x40000000u) ? (qo & ~3u) : 0u));
                 }
-#endif
             };
             // software pipeline: PIPE_DEPTH steps in flight, each in its own register set (no register
             // rotation: a copy of an in-flight destination would wait for its load).  Every point of
@@ -2128,9 +1936,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 kstart = rs_kredo;
             }
             // (RS: the events of fused records look their staging entries up: drained before those are overwritten)
-#ifndef MDX_RSABL_NOFD
             if (RS && qcount > 0) drain_all();
-#endif
         };
 
     // Without the fast path, tiles of 64 records are dealt round-robin to the wavefronts (a run of expensive records —
@@ -2142,7 +1948,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     // records ends on a full step.
     // (ML: the records of the pool's library, places [rec_lo, rec_lo + n_rec) of the bucketed columns; ml_lib = that library,
     // counted from the launch's first one)
-    u32 ml_k = 0u, ml_m = 1u, ml_first = 0u;     // ML: the pool's place among the ml_m pools of its library, the first of which is pool ml_first
+    u32 ml_m = 1u, ml_first = 0u;     // ML: the pool is one of the ml_m pools of its library, the first of which is pool ml_first
     const u32 rounds = (n_rec / T) / nwaves;
     const u32 rem_lo = rounds * nwaves * T, rem = n_rec - rem_lo;
     const u32 t_lo = rem_lo + (u32)((u64)rem * gwave / nwaves), t_hi = rem_lo + (u32)((u64)rem * (gwave + 1) / nwaves);
@@ -2459,7 +2265,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
             ent.w = ((u32)(libid * d.w_lib + d.off_tc() + rev * 4 * 512) << 2) | ((u32)libid << 24) |
                     ((w1 & D_HASQ) ? 0x40000000u : 0u) | ((u32)rev << 31);
             bool gpre = false, isS = false, covered = false;
-            if (MDX_PREFIX && __ballot(kept && !(w1 & D_SIMPLE))) {   // (wave-uniform: tiles of plain records skip this)
+            if (__ballot(kept && !(w1 & D_SIMPLE))) {   // (wave-uniform: tiles of plain records skip this)
                 // gapped records with complete flanks: the columns of their first / last match run ride the
                 // partial-plain list (and the CIGAR walk starts behind them)
                 const int dnq = n0 - nq;
@@ -2733,8 +2539,8 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
     };   // general
 
     // (ML: a pool counts ONE library of the launch — MdxTabArgs::ml_plan, made on the device from the libraries' sizes: pool p
-    // is the ml_k-th of the ml_m pools of library ml_lib, which share that library's tiles among themselves as the pools of a
-    // one-library launch share the batch's; see the template's comment)
+    // is one of the ml_m pools of library ml_lib (the plan's y, its place among them, goes unused), which share that library's
+    // tiles among themselves as the pools of a one-library launch share the batch's; see the template's comment)
     {
     if (ML) {
         karg_p kp = ka;
@@ -2747,7 +2553,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         }
         const uint4 pl = kp->ml_plan[blockIdx.x % mdx_n_pools(gridDim.x)];
         ml_lib = (int)__builtin_amdgcn_readfirstlane((int)pl.x);
-        ml_k = (u32)__builtin_amdgcn_readfirstlane((int)pl.y);
         ml_m = (u32)__builtin_amdgcn_readfirstlane((int)pl.z);
         ml_first = (u32)__builtin_amdgcn_readfirstlane((int)pl.w);
         rec_lo = kp->lib_start[k_lib_lo + ml_lib];
@@ -2837,7 +2642,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
         u32 cur = tile_of(grab());
         u32 nxt = (RS || pfl) && cur != 0xFFFFFFFFu ? tile_of(grab()) : 0xFFFFFFFFu;
         // (pfl: the first tile's columns and second round trip, one after the other — every later tile's come under the tile
-        // in front of it.  Rounds 4-6 had the same prefetch into registers behind MDX_PK_PREFETCH: 26 of them, spilled — DESIGN 4)
+        // in front of it)
         if (pfl && cur != 0xFFFFFFFFu) {
             pfl_cols(cur);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3028,7 +2833,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                             hi |= cpv[k].x | cpv[k].y | cpv[k].z | cpv[k].w;
                         }
                     }
-#if MDX_FUSE_CP2
                     // (two units per lane and round trip)
                     for (u32 u = 64u * FCPU + (u32)lane; u < cp_nu; u += 128u) {
                         const u32x4 v = cp_load(qin + (cp_a0 + 16u * u));
@@ -3039,22 +2843,11 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                         if (two) cp_store(qout + (cp_a0 + 16u * (u + 64u)), v2);
                         hi |= v.x | v.y | v.z | v.w | v2.x | v2.y | v2.z | v2.w;
                     }
-#else
-                    for (u32 u = 64u * FCPU + (u32)lane; u < cp_nu; u += 64u) {
-                        const u32x4 v = cp_load(qin + (cp_a0 + 16u * u));
-                        cp_store(qout + (cp_a0 + 16u * u), v);
-                        hi |= v.x | v.y | v.z | v.w;
-                    }
-#endif
                     if (cp_b0 + (u32)lane < cp_a0) { const u8 b = qin[cp_b0 + (u32)lane]; qout[cp_b0 + (u32)lane] = b; hi |= b; }
                     const u32 t0 = cp_a0 + 16u * cp_nu + (u32)lane;
                     if (t0 < cp_b1) { const u8 b = qin[t0]; qout[t0] = b; hi |= b; }
                     // (patch mode: no pass over the tile's qualities has been made — every record looks at its first one)
-#ifdef MDX_RSABL_NOQF
-                    rs_anyhi = __ballot((hi & 0x80808080u) != 0u) != 0ull;
-#else
                     rs_anyhi = p.rs.patch != nullptr || __ballot((hi & 0x80808080u) != 0u) != 0ull;
-#endif
                     MDX_PH(1);
                 }
                 bool kept = (fl & 0xF04u) == 0;  // reader.py:121-132
@@ -3129,7 +2922,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 // cost): the conditions are the general pass's for such an entry (complete flanks, the window loads inside the
                 // SEQ column with the sixteen nibbles of slack of a gapped step, a CIGAR that agrees with SEQ), the entry is the
                 // one it would have made, and anything it would have refused or reported is left to it.
-                constexpr bool SIP = PK && !RS && MDX_PK_SIP;
+                constexpr bool SIP = PK && !RS;
                 bool sone = false, s_del = false;
                 u32 s_nq = 0u, s_n0 = 0u, s_vlr = 0u;
                 // (a tile without such a record — any tile of ungapped data — skips all of it)
@@ -3179,16 +2972,10 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     // status of the records this kernel is done with (rescale.py:300-342): the fused ones and those written
                     // back unchanged (mr_raw is preset to NaN by the launch: such a record keeps it); the others go to the
                     // wavefront's list
-#ifndef MDX_RSABL_NOST
                     if (valid && (rs_fused || !want)) p.rs.status[ri] = (u8)rs_st;
-#endif
                     // (PK: the general pass lists its own records)
                     const bool lst = want && !rs_fused && !(PK && kept && !triv);
-#ifdef MDX_RSABL_NOLIST
-                    const u64 mW = 0;
-#else
                     const u64 mW = __ballot(lst);
-#endif
                     if (mW) {
                         if (lst) (p.rs.gen_list + (size_t)gwave * (size_t)p.list_cap)[n_rs + (u32)mbcnt64(mW, 0)] = ri;
                         n_rs += (u32)__popcll(mW);
@@ -3308,7 +3095,7 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                 // (a tile of a coordinate-sorted batch — its first and last record within 64 KB of one another — reads the
                 // first copy only: its records share their lines with their neighbours, and two copies are twice the lines;
                 // 25 M sorted records over 3 Gb: 1.09 ms with one copy, 1.16 with both)
-                constexpr bool REF2P = PK && !RS && !MASK && MDX_PK_FASTIDX && MDX_PK_FASTP;     // (... the partial steps that look at w: FIDP)
+                constexpr bool REF2P = PK && !RS && !MASK;     // (... the partial steps that look at w: FIDP)
                 bool copy_b = false;
                 if (PK && !RS && a.ref2 && mT) {
                     const u32 xa = (u32)rl((int)ent.x, __ffsll((long long)mT) - 1), xb = (u32)rl((int)ent.x, 63 - __clzll((long long)mT));
@@ -3339,9 +3126,10 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                         if (lane < d.R - 1) stg[nF + lane] = pad;
                     }
                 }
-                // (PTILE — the packed fused kernel: the partial records of the tile are staged behind its complete ones, by strand,
-                // and counted by a run of their own in the tile loop: their MR words are the tile's)
-                constexpr bool PTILE = PK && (RS ? MDX_PKF_PTILE : MDX_PK_PTILE);
+                // (PTILE — the packed kernels but the fused one: the partial records of the tile are staged behind its complete ones,
+                // by strand, and counted by a run of their own in the tile loop; the fused one's go through its list, rescaled by
+                // the list's passes)
+                constexpr bool PTILE = PK && !RS;
                 int nPt = 0, nPtp = 0;
                 const u64 mPm = PTILE ? __ballot(triv && !isF && rev) : 0ull;
                 if (PTILE && mP) {
@@ -3412,17 +3200,12 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
                     // windows do not hold, [L, nq) — subs[nt_ref], rescale.py:142-143 (the first 32 of them requested
                     // here; a record shorter than L leaves L - nq zeroed bytes in plane A of its left columns).
                     const u8 *__restrict__ g_ref = p.ref + (size_t)(c0 + (u32)c_pos);
-#ifdef MDX_RSABL_NOE
-                    const bool resting = false;
-#else
-                    const bool resting = rs_fused;
-#endif
                     u32x4 rv2[2];
                     rv2[0] = rv2[1] = u32x4{0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u};
-                    if (resting && nq > L) rv2[0] = *(const u32x4_u *)(g_ref + L);
-                    if (resting && nq > L + 16) rv2[1] = *(const u32x4_u *)(g_ref + L + 16);
+                    if (rs_fused && nq > L) rv2[0] = *(const u32x4_u *)(g_ref + L);
+                    if (rs_fused && nq > L + 16) rv2[1] = *(const u32x4_u *)(g_ref + L + 16);
                     rsq_flush();
-                    if (resting) {
+                    if (rs_fused) {
                         int nA = 0, nC = 0, nG = 0, nT = 0;
                         auto count16 = [&](const u32x4 rv, const int qi) {
                             const u64 r64[2] = {(u64)rv.x | ((u64)rv.y << 32), (u64)rv.z | ((u64)rv.w << 32)};
@@ -3451,12 +3234,6 @@ __global__ __launch_bounds__(RS ? MDX_FUSE_BLOCK : (PK ? MDX_PK_BLOCK : MDX_BLOC
             if (pend >= 64 || (over && pend > 0)) {
                 const int m = pend < 64 ? pend : 64;
                 MDX_PH(6);
-                // (PK: the general pass is where the kernel wants the most registers: the bit-sliced counters are folded
-                // into TC in front of it — every dozen tiles, about as often as their eight planes ask for anyway — and
-                // are not live across it)
-#ifdef MDX_PK_FLUSH_GENERAL
-                if (PK) bs_flush();
-#endif
                 // (the wavefront's own stores: complete before they are read back)
                 if (pfl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -4017,918 +3794,4 @@ __global__ void genome_comp_kernel(const u8 *__restrict__ ref, const i64 *__rest
 void mdx_k_genome_comp(const uint8_t *ref, const int64_t *contig_off, int n_contig, unsigned long long *out,
                        hipStream_t s) {
     hipLaunchKernelGGL(genome_comp_kernel, dim3(2048), dim3(256), 0, s, ref, (const i64 *)contig_off, n_contig, out);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Quality rescaling (mapdamage/rescale.py:195-365; BASELINE config[4]).  The new quality is a byte lookup
-// LUT[sub][position key][old quality] prepared on the host with the reference's floating-point expressions
-// (mapdamage_amd/rescale.py); MR is the fp64 sum of term[sub][key] over the rescaled columns in the read's own
-// 5'->3' order (bit-exact).  Only columns within len5p of the 5' end or len3p of the 3' end have a key other than 0,
-// and key 0 leaves the quality as it is and adds 0.0 (checked on the host: MdxRescaleArgs::lds_tables), so a record
-// whose CIGAR is [S] M [S] is rescaled by ONE lane walking its two end windows (phase E); the whole read is streamed
-// only for the substitution summary of rescale.py:108-192 (phase S, eight bytes per lane).  Any other record is
-// walked column by column by a whole wavefront (`generic`).
-// 512-thread blocks, three per CU (their LDS tables: ~35 KB each), six wavefronts per SIMD (80 VGPRs): measured
-// against 256 x 5 (93 VGPRs, LDS-limited) -8 %; eight per SIMD spill (43 VGPRs) and lose 30 %
-#ifndef RS_BLOCK
-#define RS_BLOCK 512
-#endif
-#ifndef RS_WPS
-#define RS_WPS 6
-#endif
-#ifndef RS_BPC
-#define RS_BPC 3
-#endif
-#ifndef RS_EG
-#define RS_EG 4           // 8-byte groups of the end windows fetched per round trip of phase E (2: one window; 4: both)
-#endif
-#ifndef RS_WG
-#define RS_WG 2          // 8-column groups the walk kernel fetches per round trip
-#endif
-#define RS_STG 192        // staging entries per wavefront: at most three per record of a tile
-__global__ __launch_bounds__(RS_BLOCK, RS_WPS) void rescale_kernel(MdxRescaleArgs a) {
-    const int lane = threadIdx.x & 63;
-    const i64 gwave = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const i64 nwaves = ((i64)gridDim.x * blockDim.x) >> 6;
-    const int npos = 1 + a.len5p + a.len3p;
-    u32 bc[4] = {0, 0, 0, 0};   // summary (rescale.py:108-143): raw reference-base counts per lane, see phase S
-    // In the LDS (the kernel is launched only when they fit, a.lds_tables): the lookup tables and the summary histograms
-    // (global atomics on a few hot words serialise in the L2): [lut 2 npos 94 B, padded][term 2 npos f64]
-    // [counters u32: 4 x 2 x 94 transitions | 2 x npos x 94 rescaled-column kinds, padded to 16 B], flushed at block
-    // end, [staging: RS_STG entries of 16 B per wavefront].
-    extern __shared__ __attribute__((aligned(16))) u8 rs_lds[];
-    const int lut_bytes = (2 * npos * 94 + 15) & ~15, n_cnt = 752 + 2 * npos * 94;
-    const u8 *const l_lut = rs_lds;
-    const double *const l_term = (const double *)(rs_lds + lut_bytes);
-    u32 *const l_cnt = (u32 *)(rs_lds + lut_bytes + 2 * npos * 8);
-    uint4 *const stg = (uint4 *)(rs_lds + lut_bytes + 2 * npos * 8 + ((n_cnt * 4 + 15) & ~15)) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * RS_STG;
-    {
-        for (int i = threadIdx.x; i < 2 * npos * 94; i += blockDim.x) rs_lds[i] = a.lut[i];
-        for (int i = threadIdx.x; i < 2 * npos; i += blockDim.x) ((double *)(rs_lds + lut_bytes))[i] = a.term[i];
-        for (int i = threadIdx.x; i < n_cnt; i += blockDim.x) l_cnt[i] = 0;
-        __syncthreads();
-    }
-    // ---- tiles of 64 records.  Phase 1, lane per record: routing (rescale.py:300-342) and the records the fast
-    // path can take: unchanged ones (qual_out already holds their qualities) and rescaled ones whose CIGAR is
-    // [S] M [S].  Phase E, still lane per record: the two end windows of a fast record — candidate columns by a
-    // byte-parallel test, LUT, MR.  Phase S (summary only): the aligned part of four fast records per step, eight
-    // bytes per lane.
-    const i64 ntiles = (a.n_reads + 63) / 64;
-    u32 *__restrict__ my_list = a.gen_list + gwave * a.gen_cap;
-    u32 n_list = 0;
-    const int slot = lane >> 3, sl = lane & 7;     // phase S: eight runs per step, sixteen bytes per lane
-    auto load8 = [](const u8 *ptr) -> u64 {
-        const u32x2 v = *(const u32x2_u *)ptr;
-        return (u64)v.x | ((u64)v.y << 32);
-    };
-    auto do_tile = [&](const i64 tile, const i64 ri, const bool valid) __attribute__((always_inline)) {
-        if (a.copy_qual) {
-            // qual_out starts as a copy of qual: the tile's own stretch of the column, 16 bytes per lane, before any
-            // lane of this wavefront stores a rescaled byte into it (the stretch belongs to this tile alone: its first
-            // and last partial 16 bytes are moved byte by byte, never a neighbour's).  The lines it reads are the ones
-            // phase 1 needs the first quality of every record from.
-            const i64 r1 = tile * 64 + 64 < a.n_reads ? tile * 64 + 64 : a.n_reads;
-            const u32 b0 = a.seq_off[tile * 64], b1 = a.seq_off[r1];
-            const u32 nu = (b1 - b0) >> 4;                           // whole 16-byte units, then up to 15 single bytes
-            for (u32 u = (u32)lane; u < nu; u += 128u) {
-                const u32 o0 = b0 + 16u * u, o1 = o0 + 1024u;
-                const bool two = u + 64u < nu;
-                const u32x4 v0 = *(const u32x4_u *)(a.qual + o0);
-                u32x4 v1 = v0;
-                if (two) v1 = *(const u32x4_u *)(a.qual + o1);
-                *(u32x4_u *)(a.qual_out + o0) = v0;
-                if (two) *(u32x4_u *)(a.qual_out + o1) = v1;
-            }
-            const u32 t0 = b0 + 16u * nu + (u32)lane;
-            if (t0 < b1) a.qual_out[t0] = a.qual[t0];
-        }
-        u32 so = 0;
-        int lseq = 0, qs = 0, nq = 0, st = 0, fwd_only = 0, rev = 0;
-        int m1 = 0, gi = 0, gd = 0;   // a fast record is M(m1) [I(gi) | D(gd)] M(nq - m1 - gi) between its soft clips
-        i64 rbase = 0;
-        bool fast = false, handled = false;
-        if (valid) {
-            // first round trip: the record's columns; second: what they point at
-            const u32 fl = a.flag[ri];
-            so = a.seq_off[ri];
-            lseq = (int)(a.seq_off[ri + 1] - so);
-            const u32 co = a.cigar_off[ri];
-            const int cn = (int)(a.cigar_off[ri + 1] - co);
-            const int c_tid = a.tid[ri], c_pos = a.pos[ri], c_mtid = a.mtid[ri], c_mpos = a.mpos[ri];
-            const u32 q_first = lseq > 0 ? ((fl & 0x4000u) ? 0u : (u32)a.qual[so]) : 0xFFu;      // (MDX_FLAG_HAS_QUAL)
-            const u32 c0 = cn > 0 ? a.cigar[co] : 0u, c1 = cn > 1 ? a.cigar[co + 1] : 0u, c2 = cn > 2 ? a.cigar[co + 2] : 0u;
-            const u32 c3 = cn > 3 ? a.cigar[co + 3] : 0u, c4 = cn > 4 ? a.cigar[co + 4] : 0u;
-            const bool tid_ok = c_tid >= 0 && c_tid < a.n_contig;
-            const i64 c_off0 = tid_ok ? a.contig_off[c_tid] : 0, c_off1 = tid_ok ? a.contig_off[c_tid + 1] : 0;
-            rev = (fl >> 4) & 1;
-            const int mate_rev = (fl >> 5) & 1;
-            if (fl & 0x4) st = 0;
-            else if (lseq == 0 || q_first == 0xFF) st = 1;
-            else if (fl & 0x1) {
-                const int pos = c_pos, mp = c_mpos;
-                const bool same = c_tid == c_mtid;
-                if ((!rev && mate_rev && mp > pos && same) || (rev && !mate_rev && mp < pos && same)) { st = 3; fwd_only = 1; }
-                else st = 4;
-            } else st = 2;
-            const bool room = (i64)so + lseq + 16 <= a.n_bases;  // the 8- and 16-byte loads stay inside the columns
-            if (st < 2 || st == 4) {
-                // written back unchanged: qual_out already holds the record's qualities (mdx_rescale_device copies the
-                // column before the launch), only the status and the MR marker are left to set
-                a.status[ri] = (u8)st;
-                a.mr_raw[ri] = __builtin_nan("");
-                handled = true;
-            } else if (room && cn >= 1 && cn <= 5) {
-                // [S] M [S] or [S] M (I | D) M [S], both runs of the second form at least as long as the end windows
-                auto is_m = [](u32 c) { const u32 o = c & 0xF; return o == 0 || o == 7 || o == 8; };
-                const int lead = (c0 & 0xF) == 4 ? 1 : 0;
-                const u32 cl = cn == 1 ? c0 : (cn == 2 ? c1 : (cn == 3 ? c2 : (cn == 4 ? c3 : c4)));
-                const int trail = (cn > 1 && (cl & 0xF) == 4) ? 1 : 0;
-                const int core = cn - lead - trail;
-                const u32 k0 = lead ? c1 : c0, k1 = lead ? c2 : c1, k2 = lead ? c3 : c2;
-                qs = lead ? (int)(c0 >> 4) : 0;
-                const int clipr = trail ? (int)(cl >> 4) : 0;
-                bool ok = (core == 1 || core == 3) && is_m(k0);
-                m1 = (int)(k0 >> 4);
-                int m2 = 0;
-                if (core == 3) {
-                    const int ox = k1 & 0xF, g = (int)(k1 >> 4);
-                    const int wreq = a.len5p > a.len3p ? a.len5p : a.len3p;
-                    m2 = (int)(k2 >> 4);
-                    ok = ok && is_m(k2) && (ox == 1 || ox == 2) && g >= 1 && m1 >= 1 && m2 >= 1 && m1 >= wreq && m2 >= wreq;
-                    gi = ox == 1 ? g : 0;
-                    gd = ox == 2 ? g : 0;
-                }
-                nq = m1 + gi + m2;
-                const i64 pos = c_pos;
-                // (so + qs >= 8: a reverse-strand window is loaded as the eight bytes that end at its last column;
-                //  nq, and with it every run, fits 16 bits of a staging entry)
-                ok = ok && nq >= 1 && nq <= 0xFFFF && gd <= 0xFFFF && qs + nq + clipr == lseq && tid_ok && pos >= 0 &&
-                     pos + m1 + gd + m2 <= c_off1 - c_off0 && so + (u32)qs >= 8u;
-                if (ok) rbase = c_off0 + pos;
-                fast = ok;
-                if (!ok) { qs = 0; nq = 0; m1 = 0; gi = 0; gd = 0; }
-            }
-        }
-        // (the tile's quality copy has long been written back — two round trips ago — but nothing orders the stores of
-        //  different lanes to one address, so the rescaled bytes wait for it explicitly)
-        if (a.copy_qual) __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0)
-        const u64 m_fast = __ballot(fast);
-        const bool walk = valid && !fast && !handled;   // left to rescale_walk_kernel
-        const u64 m_gen = __ballot(walk);
-
-        // ---- phase E: lane per fast record.  Columns [0, n5) and [s3, nq) in read orientation are the only ones
-        // that can carry a key (_corr_this_base, rescale.py:49-79); every other column keeps its quality and adds 0.
-        if (fast) {
-            const u32 sb = so + (u32)qs;          // 32-bit offsets into the read / quality columns (scalar base pointers)
-            // reference byte under query base qi: at rbase + qi in the left run, rbase + gd - gi + qi in the right one
-            // (the same when there is no gap); the 5' window lies in the left run of a forward read, the right run of a
-            // reverse one
-            const int rshift = gd - gi;
-            const int n5 = a.len5p < nq ? a.len5p : nq;
-            const int s3 = nq - a.len3p > n5 ? nq - a.len3p : n5;
-            const int n3 = fwd_only ? 0 : nq - s3;
-            // stored pair (read byte | reference byte << 8) of a C>T / G>A column of the read's own strand
-            const u32 pair0 = rev ? ('A' | 'G' << 8) : ('T' | 'C' << 8), pair1 = rev ? ('T' | 'C' << 8) : ('A' | 'G' << 8);
-            double mr = 0.0;
-            // A round takes up to 16 columns of the 5' window and 16 of the 3' window as four groups of eight bytes,
-            // all fetched (read, reference, quality) before any is looked at — one round trip.  Byte j of a group is
-            // column oq0 + j (a reverse-strand group is loaded from its far end and byte-swapped), so the candidates
-            // come out in the reference's order: 5' window first, then the 3' window.  Windows longer than 16 take
-            // their own rounds, all of the 5' window before the 3' one.
-            const int ra = (a.len5p + 15) >> 4, rb = (a.len3p + 15) >> 4;
-            const bool one = RS_EG == 4 && ra <= 1 && rb <= 1;
-            const int rounds = one ? 1 : ra + rb;
-            for (int r = 0; r < rounds; r++) {
-                int w[2] = {0, 0}, c[2] = {0, 0};
-                if (one) { c[0] = n5; w[1] = s3; c[1] = n3; }
-                else if (r < ra) { w[0] = 16 * r; c[0] = n5 - 16 * r; }
-                else { w[1] = s3 + 16 * (r - ra); c[1] = n3 - 16 * (r - ra); }
-                u64 sg[4], rg[4], qg[4];
-                int qi0[4];
-#if RS_EG == 2
-                const int hw = r < ra ? 0 : 1;         // a round is one window: two groups
-#define RS_H(h) (hw * 2 + (h))
-#else
-#define RS_H(h) (h)
-#endif
-#pragma unroll
-                for (int h0 = 0; h0 < RS_EG; h0++) {
-                    const int h = RS_H(h0);
-                    const int oq0 = w[h >> 1] + 8 * (h & 1), cnt = c[h >> 1] - 8 * (h & 1);
-                    qi0[h0] = rev ? nq - 8 - oq0 : oq0;
-                    sg[h0] = 0; rg[h0] = 0; qg[h0] = 0;
-                    if (cnt > 0) {
-                        sg[h0] = load8(a.seq + (u32)(sb + qi0[h0]));
-                        rg[h0] = load8(a.ref + (rbase + (((h >> 1) ^ rev) ? rshift : 0) + qi0[h0]));
-                        qg[h0] = load8(a.qual + (u32)(sb + qi0[h0]));
-                    }
-                }
-#pragma unroll
-                for (int h0 = 0; h0 < RS_EG; h0++) {
-                    const int h = RS_H(h0);
-                    const int oq0 = w[h >> 1] + 8 * (h & 1), cnt = c[h >> 1] - 8 * (h & 1);
-                    if (cnt <= 0) continue;
-                    u64 s8 = sg[h0], r8 = rg[h0], q8 = qg[h0];
-                    if (rev) { s8 = __builtin_bswap64(s8); r8 = __builtin_bswap64(r8); q8 = __builtin_bswap64(q8); }
-                    // a transition differs in bits 1 and 2 of the byte ('A'^'G' = 0x06, 'C'^'T' = 0x17), no other
-                    // pair of bases does: the exact test is left to the few candidates
-                    const u64 x = s8 ^ r8;
-                    u64 cd = x & (x >> 1) & 0x0202020202020202ull & byte_range(0, cnt);
-                    while (cd) {
-                        const int sh = (__ffsll((long long)cd) - 1) & ~7;
-                        cd &= cd - 1;
-                        const u32 pr = ((u32)(s8 >> sh) & 0xFFu) | (((u32)(r8 >> sh) & 0xFFu) << 8);
-                        const int sub = pr == pair0 ? 0 : (pr == pair1 ? 1 : -1);
-                        if (sub < 0) continue;
-                        const int oq = oq0 + (sh >> 3);
-                        int pp = oq + 1;                                 // _corr_this_base, rescale.py:49-79
-                        const int back = pp - nq - 1;
-                        if (!fwd_only && pp >= -back) pp = back;
-                        const int key = pp > 0 ? (pp <= a.len5p ? pp : 0) : (-pp <= a.len3p ? a.len5p - pp : 0);
-                        const int ti = sub * npos + key;
-                        mr += l_term[ti];                                // (x + 0.0 == x: a zero term changes nothing)
-                        const u32 q = (u32)(q8 >> sh) & 0xFFu;
-                        if (q <= 93) {
-                            const u32 newq = l_lut[ti * 94 + q];
-                            if (a.patch) patch_put(a.patch, a.n_patch, a.patch_cap, a.patch_parts, newq != q, (u32)(sb + (rev ? nq - 1 - oq : oq)), newq);
-                            else if (newq != q) a.qual_out[(u32)(sb + (rev ? nq - 1 - oq : oq))] = (u8)newq;
-                        }
-                    }
-                }
-            }
-            a.status[ri] = (u8)st;
-            a.mr_raw[ri] = mr;
-        }
-
-        // ---- phase S: the substitution summary of the fast records (rescale.py:108-143), four records per step; the
-        // first 128 columns of the next four are fetched before the current ones are counted
-        if (a.subs && m_fast) {
-            // staging entries (16 B): a run of columns [seq/qual byte offset, reference offset lo, reference offset hi (8)
-            // | rev << 8 | 5'-only << 9 | deletion << 10 | first query base of the run << 16, columns | nq << 16]; a
-            // deleted stretch is an entry of its own whose "read" is the reference itself (base counts, no transition)
-            const int ne = fast ? (m1 + gi == nq ? 1 : (gd ? 3 : 2)) : 0;
-            const int e0 = mbcnt64(__ballot(ne & 1), 0) + 2 * mbcnt64(__ballot(ne & 2), 0);
-            if (fast) {
-                const u32 fl2 = ((u32)rev << 8) | ((u32)fwd_only << 9), nqh = (u32)nq << 16;
-                const u32 sb = so + (u32)qs;
-                auto entry = [&](const u32 soff, const i64 roff, const u32 flags, const int qoff, const int len) {
-                    return make_uint4(soff, (u32)(roff & 0xFFFFFFFFll), (u32)(roff >> 32) | flags | ((u32)qoff << 16), (u32)len | nqh);
-                };
-                stg[e0] = entry(sb, rbase, fl2, 0, m1 + gi == nq ? nq : m1);
-                if (ne >= 2) stg[e0 + ne - 1] = entry(sb + m1 + gi, rbase + m1 + gd, fl2, m1 + gi, nq - m1 - gi);
-                if (ne == 3) stg[e0 + 1] = entry(sb, rbase + m1, fl2 | (1u << 10), 0, gd);
-            }
-            const int nfast = rl(e0 + ne, 63);     // entries of the tile
-            for (int i0 = 0; i0 < nfast; i0 += 8) {
-                const bool sact = i0 + slot < nfast;
-                const uint4 e = stg[sact ? i0 + slot : 0];
-                const int s_nq = sact ? (int)(e.w & 0xFFFFu) : 0;        // columns of the run
-                const int s_rev = (e.z >> 8) & 1, s_fwd = (e.z >> 9) & 1, s_del = (e.z >> 10) & 1;
-                const int s_qoff = (int)(e.z >> 16), s_tot = (int)(e.w >> 16);
-                const i64 rb = ((i64)(e.z & 0xFFu) << 32) | e.y;
-                const u32 fx = s_rev ? 0x04040404u : 0u;    // A <-> T, C <-> G in the two class bits: counts in read orientation
-                // passes of 128 columns per run (one, unless a run is longer)
-                for (int off = 16 * sl; __ballot(off < s_nq); off += 128) {
-                    const int nb = s_nq - off;                           // columns from this lane's first byte on
-                    if (nb <= 0) continue;
-                    // both loads in one round trip (the entry of a deleted stretch points at its record's first base;
-                    // the columns hold 16 readable bytes behind every record the fast path takes, see `room`)
-                    const u32x4 rv = *(const u32x4_u *)(a.ref + rb + off);
-                    const u32x4 sl16 = *(const u32x4_u *)(a.seq + (e.x + (s_del ? 0u : (u32)off)));
-                    const u32x4 sv = s_del ? rv : sl16;
-                    const int n_lo = nb < 8 ? nb : 8, n_hi = nb < 16 ? nb - 8 : 8;
-                    const u64 am0 = ~0ull >> (64 - 8 * n_lo), am1 = n_hi > 0 ? ~0ull >> (64 - 8 * n_hi) : 0ull;
-                    const u32 am[4] = {(u32)am0, (u32)(am0 >> 32), (u32)am1, (u32)(am1 >> 32)};
-                    u32 cany = 0, cd[4];
-#pragma unroll
-                    for (int w = 0; w < 4; w++) {
-                        // subs[nt_ref] += 1 for every column (rescale.py:142-143).  Raw per-lane counts: valid bytes
-                        // (bit 7 clear: A,C,G,T), class bit 1 set (C,G), class bit 2 set (T,G), both (G) — in read
-                        // orientation; A,C,G,T follow at the end of the kernel
-                        const u32 ok = ~rv[w] & 0x80808080u & am[w];
-                        const u32 b1 = (rv[w] << 6) & ok, b2 = ((rv[w] ^ fx) << 5) & ok;
-                        bc[0] += __popc(ok); bc[1] += __popc(b1); bc[2] += __popc(b2); bc[3] += __popc(b1 & b2);
-                        // transitions (and junk bytes that look like one): bits 1 and 2 of the byte differ
-                        const u32 x = sv[w] ^ rv[w];
-                        cd[w] = x & (x >> 1) & 0x02020202u & am[w];
-                        cany |= cd[w];
-                    }
-                    if (!cany) continue;
-                    const u32x4 qv = *(const u32x4_u *)(a.qual + (e.x + (u32)off));
-                    // one bit per candidate byte
-                    u32 m16 = (((cd[0] >> 1) * 0x00204081u >> 21) & 0xFu) | (((cd[1] >> 1) * 0x00204081u >> 17) & 0xF0u) |
-                              (((cd[2] >> 1) * 0x00204081u >> 13) & 0xF00u) | (((cd[3] >> 1) * 0x00204081u >> 9) & 0xF000u);
-                    // read-orientation position of byte 0, and the step to byte j
-                    const int oq0 = s_rev ? s_tot - 1 - s_qoff - off : s_qoff + off, dq = s_rev ? -1 : 1;
-                    while (m16) {
-                        const int j = __ffs((int)m16) - 1;
-                        m16 &= m16 - 1;
-                        const u32 bo = (u32)(j & 3) * 8u;
-                        const int w = j >> 2;
-                        const u32 qw = w == 0 ? qv[0] : (w == 1 ? qv[1] : (w == 2 ? qv[2] : qv[3]));
-                        const u32 sw = w == 0 ? sv[0] : (w == 1 ? sv[1] : (w == 2 ? sv[2] : sv[3]));
-                        const u32 rw = w == 0 ? rv[0] : (w == 1 ? rv[1] : (w == 2 ? rv[2] : rv[3]));
-                        const u32 q = __builtin_amdgcn_ubfe(qw, bo, 8u);
-                        const u32 pr = __builtin_amdgcn_ubfe(sw, bo, 8u) | (__builtin_amdgcn_ubfe(rw, bo, 8u) << 8);
-                        // stored pair -> transition of the read's own strand: 0 C>T, 1 G>A (rescaled), 2 T>C, 3 A>G;
-                        // -1: not a transition of two bases (sums of 0/1 terms: no branches)
-                        const int kind = (int)(pr == ('T' | 'C' << 8)) * (1 + s_rev) + (int)(pr == ('A' | 'G' << 8)) * (2 - s_rev) +
-                                         (int)(pr == ('C' | 'T' << 8)) * (3 + s_rev) + (int)(pr == ('G' | 'A' << 8)) * (4 - s_rev) - 1;
-                        int pp = oq0 + dq * j + 1;                           // _corr_this_base, rescale.py:49-79
-                        const int back = pp - s_tot - 1;
-                        pp = (!s_fwd && pp >= -back) ? back : pp;
-                        const int k5 = pp <= a.len5p ? pp : 0, k3 = -pp <= a.len3p ? a.len5p - pp : 0;
-                        const int key = pp > 0 ? k5 : k3;
-                        // "before" words of T>C / A>G, or the occurrences of (substitution, key, old quality)
-                        const int idx = kind >= 2 ? (kind == 2 ? 2 : 6) * 94 : 752 + (kind * npos + key) * 94;
-                        if (kind >= 0 && q <= 93) atomicAdd(&l_cnt[idx + (int)q], 1u);
-                    }
-                }
-            }
-        }
-        if (m_gen) {
-            if (walk) my_list[n_list + (u32)mbcnt64(m_gen, 0)] = (u32)ri;
-            n_list += (u32)__popcll(m_gen);
-        }
-    };
-    if (a.in_list) {
-        // behind the fused kernel: the records its wavefronts listed, 64 at a time (qual_out is complete: no copy).
-        // (Measured against a scan of all tiles for records marked in their status: 0.51 against 0.71 ms per 25 M records
-        // of config 5 — a tile costs its round trips however few of its lanes are busy.)
-        for (i64 l = gwave; l < a.n_in; l += nwaves) {
-            const u32 *__restrict__ in = a.in_list + l * a.in_cap;
-            const u32 n = a.in_count[l];
-            for (u32 k0 = 0; k0 < n; k0 += 64) do_tile(0, k0 + lane < n ? (i64)in[k0 + lane] : 0, k0 + lane < n);
-        }
-    } else {
-        for (i64 tile = gwave; tile < ntiles; tile += nwaves) do_tile(tile, tile * 64 + lane, tile * 64 + lane < a.n_reads);
-    }
-    if (lane == 0) a.gen_count[gwave] = n_list;
-    if (a.subs) {
-        // The block's counters go to its own row of subs_part (plain stores; rescale_reduce_kernel adds the rows up):
-        // atomics of every block on the same few thousand words cost 0.3 ms per launch whatever its size.
-        // The four reference-base counts of the block are collected in the first counter words no transition uses
-        // ("before" of C>T).
-        __syncthreads();
-        {
-            u32 v[4];
-            for (int b = 0; b < 4; b++) {
-                v[b] = bc[b];
-                for (int o = 32; o; o >>= 1) v[b] += __shfl_xor(v[b], o);
-            }
-            // valid, bit 1 (C,G), bit 2 (T,G), both (G) -> A, C, G, T
-            if (lane == 0) {
-                atomicAdd(&l_cnt[0], v[0] - v[1] - v[2] + v[3]);
-                atomicAdd(&l_cnt[1], v[1] - v[3]);
-                atomicAdd(&l_cnt[2], v[3]);
-                atomicAdd(&l_cnt[3], v[2] - v[3]);
-            }
-        }
-        __syncthreads();
-        u32 *__restrict__ row = a.subs_part + (size_t)blockIdx.x * n_cnt;
-        for (int i = threadIdx.x; i < n_cnt; i += blockDim.x) row[i] = l_cnt[i];
-    }
-}
-
-// The records rescale_kernel leaves out — any CIGAR — one lane per record: the lane walks the record's CIGAR in the
-// read's own 5'->3' order (operations and bytes backwards on the reverse strand), eight columns of a match run at a
-// time, so that MR is summed in the reference's order (rescale.py:226-262).  Wavefront w takes the list
-// rescale_kernel's wavefront w wrote (a.gen_list), 64 records at a time, or — without that kernel (tables too large
-// for its LDS image, or key 0 not the identity) — every (number of wavefronts)-th tile of the batch.
-__global__ __launch_bounds__(RS_BLOCK) void rescale_walk_kernel(MdxRescaleArgs a) {
-    const int lane = threadIdx.x & 63;
-    const i64 gwave = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const i64 nwaves = ((i64)gridDim.x * blockDim.x) >> 6;
-    const int npos = 1 + a.len5p + a.len3p;
-    u32 bc[4] = {0, 0, 0, 0};   // summary (rescale.py:108-143): reference bases A,C,G,T in read orientation, per lane
-    // In the LDS when they fit (a.lds_tables): [lut 2 npos 94 B, padded][term 2 npos f64][counters u32: 4 x 2 x 94
-    // transitions | 2 x npos x 94 rescaled-column kinds], the counters flushed at block end.
-    extern __shared__ __attribute__((aligned(16))) u8 rs_lds[];
-    const int lut_bytes = (2 * npos * 94 + 15) & ~15, n_cnt = 752 + 2 * npos * 94;
-    u32 *const l_cnt = (u32 *)(rs_lds + lut_bytes + 2 * npos * 8);
-    if (a.lds_tables) {
-        for (int i = threadIdx.x; i < 2 * npos * 94; i += blockDim.x) rs_lds[i] = a.lut[i];
-        for (int i = threadIdx.x; i < 2 * npos; i += blockDim.x) ((double *)(rs_lds + lut_bytes))[i] = a.term[i];
-        for (int i = threadIdx.x; i < n_cnt; i += blockDim.x) l_cnt[i] = 0;
-        __syncthreads();
-    }
-    const u8 *const t_lut = a.lds_tables ? (const u8 *)rs_lds : a.lut;
-    const double *const t_term = a.lds_tables ? (const double *)(rs_lds + lut_bytes) : a.term;
-    // summary word `idx` (>= 4) of include/mdx.h += 1
-    auto sub_bump = [&](const int idx) {
-        if (a.lds_tables) atomicAdd(&l_cnt[idx - 4], 1u);
-        else atomicAdd(&a.subs[idx], 1ull);
-    };
-
-    // ---- one record by the whole wavefront, any CIGAR: one lane per query base, CIGAR walked per base, column by
-    // column as the reference does it.  Only for what the lane walk below cannot follow: a reverse-strand read with a
-    // reference skip (see there).
-    auto generic = [&](const i64 ri) __attribute__((always_inline)) {
-        const u32 fl = a.flag[ri];
-        const u32 so = a.seq_off[ri];
-        const int lseq = (int)(a.seq_off[ri + 1] - so);
-        const u32 co = a.cigar_off[ri];
-        const int cn = (int)(a.cigar_off[ri + 1] - co);
-        const u8 *__restrict__ qin = a.qual + so;
-        // (patch mode: no second column — what is written back unchanged is not written at all)
-        const bool to_list = a.patch != nullptr;
-        u8 *__restrict__ qout = to_list ? nullptr : a.qual_out + so;
-        const int rev = (fl >> 4) & 1, mate_rev = (fl >> 5) & 1;
-        // record routing, rescale.py:300-342
-        int st, forward_only = 0;
-        if (fl & 0x4) st = 0;
-        else if (lseq == 0 || qin[0] == 0xFF) st = 1;
-        else if (fl & 0x1) {
-            const int pos = a.pos[ri], mp = a.mpos[ri];
-            const bool same = a.tid[ri] == a.mtid[ri];
-            if ((!rev && mate_rev && mp > pos && same) || (rev && !mate_rev && mp < pos && same)) { st = 3; forward_only = 1; }
-            else st = 4;
-        } else st = 2;
-        if (lane == 0) { a.status[ri] = (u8)st; a.mr_raw[ri] = __builtin_nan(""); }
-        if (st < 2 || st == 4) {
-            if (!to_list) for (int b = lane; b < lseq; b += 64) qout[b] = qin[b];
-            return;
-        }
-        // CIGAR: one op per lane; scan by lane 0's view via readlane
-        const u32 op_lane = lane < cn ? a.cigar[co + lane] : 0u;
-        auto op_at = [&](int k) -> u32 { return cn <= 64 ? (u32)rl((int)op_lane, k) : a.cigar[co + k]; };
-        int qs = 0, clipr = 0, rlen = 0, ncols = 0, nI = 0, qcons = 0;
-        bool leading = true;
-        for (int k = 0; k < cn; k++) {
-            const u32 c = op_at(k);
-            const int op = c & 0xF, len = (int)(c >> 4);
-            if (leading) { if (op == 4) qs += len; else if (op != 5) leading = false; }
-            if (op == 0 || op == 7 || op == 8) { ncols += len; rlen += len; qcons += len; }
-            else if (op == 1) { ncols += len; nI += len; qcons += len; }
-            else if (op == 2) { ncols += len; rlen += len; }
-            else if (op == 3) rlen += len;
-        }
-        for (int k = cn - 1; k >= 1; k--) {
-            const u32 c = op_at(k);
-            const int op = c & 0xF;
-            if (op == 5) continue;
-            if (op == 4) clipr += (int)(c >> 4); else break;
-        }
-        const int nq = lseq - qs - clipr > 0 ? lseq - qs - clipr : 0;
-        const int n0 = rlen ? rlen : 1;
-        const int nrg = n0 + nI;
-        const int tid = a.tid[ri];
-        const i64 pos = a.pos[ri];
-        bool bad = cn == 0 || tid < 0 || tid >= a.n_contig || pos < 0 || nq != qcons;
-        i64 rbase = 0;
-        if (!bad) {
-            const i64 c0 = a.contig_off[tid];
-            bad = pos + n0 > a.contig_off[tid + 1] - c0;
-            rbase = c0 + pos;
-        }
-        // rescale.py:266-271 re-attaches clips only when the first / last op is S: any other clip
-        // layout (H before S) leaves a quality string of the wrong length, which pysam rejects
-        if (!bad) {
-            const u32 f = op_at(0), l = op_at(cn - 1);
-            const int pre = (f & 0xF) == 4 ? (int)(f >> 4) : 0, suf = (l & 0xF) == 4 ? (int)(l >> 4) : 0;
-            bad = pre != qs || suf != clipr || (cn == 1 && (f & 0xF) == 4);
-        }
-        if (bad) {
-            if (lane == 0) flag_error(a.err, ri, ERR_BAD_READ);
-            if (!to_list) for (int b = lane; b < lseq; b += 64) qout[b] = qin[b];
-            return;
-        }
-        // soft-clipped qualities are kept
-        if (!to_list) {
-            for (int b = lane; b < qs; b += 64) qout[b] = qin[b];
-            for (int b = qs + nq + lane; b < lseq; b += 64) qout[b] = qin[b];
-        }
-
-        const i8 *__restrict__ rp = (const i8 *)a.ref + rbase;
-        const u8 *__restrict__ sp = a.seq + so + qs;
-        // reference byte under gapped-reference column jr (-1: an insertion gap)
-        auto ref_at = [&](const int jr) -> int {
-            int c2 = 0, shift = 0, rix = -2;
-            for (int k = 0; k < cn && rix == -2; k++) {
-                const u32 c = op_at(k);
-                const int op = c & 0xF, len = (int)(c >> 4);
-                if (op == 1) {
-                    if (jr < c2) rix = jr - shift;
-                    else if (jr < c2 + len) rix = -1;
-                    shift += len; c2 += len;
-                } else if (op == 0 || op == 7 || op == 8 || op == 2) c2 += len;
-            }
-            if (rix == -2) rix = jr - shift;
-            return rix < 0 ? -1 : (int)rp[rix];
-        };
-        // subs[nt_ref] += 1 (rescale.py:142-143): valid reference bytes are 'A','C','G','T'
-        auto count_ref = [&](const int rch) {
-            if (rch >= 0) {
-                const int k = (rch >> 1) & 3;       // A,C,T,G
-                int b = k ^ (k >> 1);               // A,C,G,T
-                if (rev) b = 3 - b;                 // complemented on the reverse strand
-                bc[0] += b == 0; bc[1] += b == 1; bc[2] += b == 2; bc[3] += b == 3;
-            }
-        };
-        double mr = 0.0;
-        for (int base = 0; base < nq; base += 64) {
-            const int oq = base + lane;                 // query base in read orientation (0 = 5' end)
-            double term = 0.0;
-            if (oq < nq) {
-                const int qi = rev ? nq - 1 - oq : oq;  // forward query index
-                // gapped-read column of query base qi, then the gapped-reference column facing it
-                // (each string is reversed from its own end on the reverse strand, rescale.py:221-224)
-                int col = 0, qoff = 0, js = -1;
-                for (int k = 0; k < cn && js < 0; k++) {
-                    const u32 c = op_at(k);
-                    const int op = c & 0xF, len = (int)(c >> 4);
-                    if (op == 0 || op == 7 || op == 8 || op == 1) {
-                        if (qi < qoff + len) js = col + (qi - qoff);
-                        col += len; qoff += len;
-                    } else if (op == 2) col += len;
-                }
-                const int rch = ref_at(rev ? nrg - ncols + js : js);
-                const u32 ch = sp[qi];
-                const u32 q = qin[qs + qi];
-                // read-orientation pair (T,C) -> C>T ; (A,G) -> G>A; complemented on the reverse strand
-                int sub = -1;
-                if (!rev) { if (ch == 'T' && rch == 'C') sub = 0; else if (ch == 'A' && rch == 'G') sub = 1; }
-                else { if (ch == 'A' && rch == 'G') sub = 0; else if (ch == 'T' && rch == 'C') sub = 1; }
-                u32 newq = q;
-                int skey = 0;
-                if (sub >= 0) {
-                    // _corr_this_base, rescale.py:49-79
-                    int p = oq + 1;
-                    const int back = p - nq - 1;
-                    if (!forward_only && p >= -back) p = back;
-                    const int key = p > 0 ? (p <= a.len5p ? p : 0) : (-p <= a.len3p ? a.len5p - p : 0);
-                    skey = key;
-                    term = a.term[sub * npos + key];
-                    if (q <= 93) newq = a.lut[(sub * npos + key) * 94 + q];
-                }
-                if (to_list) patch_put(a.patch, a.n_patch, a.patch_cap, a.patch_parts, newq != q, so + (u32)(qs + qi), newq);
-                else qout[qs + qi] = (u8)newq;
-                if (a.subs) {
-                    // _record_subs (rescale.py:108-143): transitions by old/new quality, reference bases
-                    count_ref(rch);
-                    int st = sub == 0 ? 0 : (sub == 1 ? 2 : -1);   // 0 CT, 1 TC, 2 GA, 3 AG
-                    if (st < 0) {
-                        const bool cg = rev ? (ch == 'G' && rch == 'A') : (ch == 'C' && rch == 'T');
-                        const bool ga = rev ? (ch == 'C' && rch == 'T') : (ch == 'G' && rch == 'A');
-                        st = cg ? 1 : (ga ? 3 : -1);
-                    }
-                    // (one counter per column, as in the lane walk)
-                    if (st >= 0 && q <= 93) {
-                        if (sub >= 0) sub_bump(756 + (sub * npos + skey) * 94 + q);
-                        else sub_bump(4 + (st * 2 + 0) * 94 + q);
-                    }
-                }
-            }
-            // ordered fp64 accumulation of the non-zero terms (x + 0.0 == x exactly)
-            u64 nz = __ballot(term != 0.0);
-            while (nz) {
-                const int l = __ffsll((long long)nz) - 1;
-                nz &= nz - 1;
-                const int lo = rl(__double2loint(term), l), hi = rl(__double2hiint(term), l);
-                mr += __hiloint2double(hi, lo);
-            }
-        }
-        if (lane == 0) a.mr_raw[ri] = mr;
-        if (a.subs) {
-            // deletion columns pair '-' with a reference base (counted while read bases remain in the
-            // iteration order: `if pos_on_read < length_read`, rescale.py:252)
-            int col = 0, qoff = 0;
-            for (int k = 0; k < cn; k++) {
-                const u32 c = op_at(k);
-                const int op = c & 0xF, len = (int)(c >> 4);
-                if (op == 0 || op == 7 || op == 8 || op == 1) { col += len; qoff += len; }
-                else if (op == 2) {
-                    if (rev ? qoff > 0 : qoff < nq)
-                        for (int t = lane; t < len; t += 64) count_ref(ref_at(rev ? nrg - ncols + col + t : col + t));
-                    col += len;
-                }
-            }
-        }
-    };
-
-    // ---- one record by one lane; true: left to the whole wavefront
-    auto walk = [&](const i64 ri) __attribute__((always_inline)) -> bool {
-        const u32 fl = a.flag[ri];
-        const u32 so = a.seq_off[ri];
-        const int lseq = (int)(a.seq_off[ri + 1] - so);
-        const u32 co = a.cigar_off[ri];
-        const int cn = (int)(a.cigar_off[ri + 1] - co);
-        const int rev = (fl >> 4) & 1, mate_rev = (fl >> 5) & 1;
-        const int tid = a.tid[ri];
-        const i64 pos = a.pos[ri];
-        // record routing, rescale.py:300-342
-        int st, fwd_only = 0;
-        if (fl & 0x4) st = 0;
-        else if (lseq == 0 || a.qual[so] == 0xFF) st = 1;
-        else if (fl & 0x1) {
-            const int mp = a.mpos[ri];
-            const bool same = tid == a.mtid[ri];
-            if ((!rev && mate_rev && mp > pos && same) || (rev && !mate_rev && mp < pos && same)) { st = 3; fwd_only = 1; }
-            else st = 4;
-        } else st = 2;
-        a.status[ri] = (u8)st;
-        a.mr_raw[ri] = __builtin_nan("");
-        if (st < 2 || st == 4) return false;     // written back unchanged: qual_out starts as a copy of qual
-        // CIGAR: clips, spans
-        auto opk = [&](const int k) -> u32 { return a.cigar[co + k]; };
-        int qs = 0, clipr = 0, rlen = 0, qcons = 0, n_skip = 0;
-        u32 c_first = 0, c_last = 0;
-        bool leading = true;
-        for (int k = 0; k < cn; k++) {
-            const u32 c = opk(k);
-            const int op = c & 0xF, len = (int)(c >> 4);
-            if (k == 0) c_first = c;
-            c_last = c;
-            if (leading) { if (op == 4) qs += len; else if (op != 5) leading = false; }
-            if (op == 0 || op == 7 || op == 8) { rlen += len; qcons += len; }
-            else if (op == 1) qcons += len;
-            else if (op == 2) rlen += len;
-            else if (op == 3) { rlen += len; n_skip += len; }
-            // soft clips behind the last operation that is not a clip (the first operation never counts)
-            if (k >= 1) { if (op == 4) clipr += len; else if (op != 5) clipr = 0; }
-        }
-        const int nq = lseq - qs - clipr > 0 ? lseq - qs - clipr : 0;
-        const int n0 = rlen ? rlen : 1;
-        bool bad = cn == 0 || tid < 0 || tid >= a.n_contig || pos < 0 || nq != qcons;
-        i64 rbase = 0;
-        if (!bad) {
-            const i64 c0 = a.contig_off[tid];
-            bad = pos + n0 > a.contig_off[tid + 1] - c0;
-            rbase = c0 + pos;
-        }
-        // rescale.py:266-271 re-attaches clips only when the first / last op is S: any other clip
-        // layout (H before S) leaves a quality string of the wrong length, which pysam rejects
-        if (!bad) {
-            const int pre = (c_first & 0xF) == 4 ? (int)(c_first >> 4) : 0, suf = (c_last & 0xF) == 4 ? (int)(c_last >> 4) : 0;
-            bad = pre != qs || suf != clipr || (cn == 1 && (c_first & 0xF) == 4);
-        }
-        if (bad) { flag_error(a.err, ri, ERR_BAD_READ); return false; }
-
-        const u32 sb = so + (u32)qs;
-        const bool room = (i64)so + lseq + 8 <= a.n_bases;      // eight bytes can be loaded from any byte of the record
-        auto col8 = [&](const u8 *__restrict__ colp, const u32 off, const int cnt) -> u64 {
-            if (room) { const u32x2 v = *(const u32x2_u *)(colp + off); return (u64)v.x | ((u64)v.y << 32); }
-            u64 v = 0;
-            for (int j = 0; j < cnt; j++) v |= (u64)colp[off + j] << (8 * j);
-            return v;
-        };
-        auto count_bases = [&](const u64 r64, const u64 am) {
-            // subs[nt_ref] += 1 (rescale.py:142-143): A,C,G,T of the reference, complemented on the reverse strand
-            const u64 ok7 = ~r64 & 0x8080808080808080ull & am;   // bit 7 clear: a base
-            const u64 b1 = (r64 << 6) & ok7, b2 = (r64 << 5) & ok7;      // bit 1, bit 2 of the byte
-            const int nA = __popcll(ok7 & ~b1 & ~b2), nC = __popcll(b1 & ~b2), nT = __popcll(~b1 & b2), nG = __popcll(b1 & b2);
-            if (rev) { bc[0] += nT; bc[1] += nG; bc[2] += nC; bc[3] += nA; }
-            else { bc[0] += nA; bc[1] += nC; bc[2] += nG; bc[3] += nT; }
-        };
-        double mr = 0.0;
-        // A reverse-strand read with a reference skip: the reference's alignment strings hold gaps for insertions and
-        // deletions only (align.py:53-73), the fetched reference still holds the skipped stretch, and both strings
-        // are reversed from their own ends (rescale.py:221-224) — read column js then faces column js + (skipped
-        // bases) of the gapped reference, whose insertion gaps stay where the forward walk put them.  No runs to
-        // follow: left to `generic`.
-        if (rev && n_skip > 0) return true;
-        int q = rev ? nq : 0, r = rev ? rlen : 0;     // query bases / reference bases in front of the next operation
-        for (int t = 0; t < cn; t++) {
-            const u32 c = opk(rev ? cn - 1 - t : t);
-            const int op = c & 0xF, len = (int)(c >> 4);
-            const int step = rev ? -len : len;
-            if (op == 0 || op == 7 || op == 8) {
-                // RS_WG groups of eight columns at a time, all fetched before any is looked at: a lane waits for every
-                // round trip to memory, and little else runs beside it in this kernel
-                for (int done = 0; done < len; done += 8 * RS_WG) {
-                    u64 sg[RS_WG], rg[RS_WG], cdg[RS_WG];
-                    int q0g[RS_WG];
-#pragma unroll
-                    for (int g = 0; g < RS_WG; g++) {
-                        const int d = done + 8 * g, cnt = len - d < 8 ? len - d : 8;
-                        q0g[g] = rev ? q - d - cnt : q + d;
-                        sg[g] = 0; rg[g] = 0;
-                        if (cnt > 0) {
-                            sg[g] = col8(a.seq, sb + (u32)q0g[g], cnt);
-                            const u32x2 rv = *(const u32x2_u *)(a.ref + rbase + (rev ? r - d - cnt : r + d));   // (guard band)
-                            rg[g] = (u64)rv.x | ((u64)rv.y << 32);
-                        }
-                    }
-                    u64 any = 0;
-#pragma unroll
-                    for (int g = 0; g < RS_WG; g++) {
-                        const int d = done + 8 * g, cnt = len - d < 8 ? len - d : 8;
-                        const u64 am = cnt > 0 ? byte_range(0, cnt) : 0ull;
-                        if (a.subs) count_bases(rg[g], am);
-                        const u64 x = sg[g] ^ rg[g];
-                        cdg[g] = x & (x >> 1) & 0x0202020202020202ull & am;   // transitions (and junk bytes that look like one)
-                        any |= cdg[g];
-                    }
-                    if (!any) continue;
-                    u64 qg[RS_WG];
-#pragma unroll
-                    for (int g = 0; g < RS_WG; g++) {
-                        const int d = done + 8 * g, cnt = len - d < 8 ? len - d : 8;
-                        qg[g] = cdg[g] ? col8(a.qual, sb + (u32)q0g[g], cnt) : 0ull;
-                    }
-#pragma unroll
-                    for (int g = 0; g < RS_WG; g++) {
-                        u64 cd = cdg[g];
-                        const u64 s64 = sg[g], r64 = rg[g], q64 = qg[g];
-                        const int q0 = q0g[g];
-                        while (cd) {
-                            // the next candidate in read order
-                            const int sh = (rev ? 63 - __builtin_clzll(cd) : __ffsll((long long)cd) - 1) & ~7;
-                            cd &= ~(0xFFull << sh);
-                            const u32 pr = ((u32)(s64 >> sh) & 0xFFu) | (((u32)(r64 >> sh) & 0xFFu) << 8);
-                            // stored pair -> transition of the read's own strand: 0 C>T, 1 G>A (rescaled), 2 T>C, 3 A>G
-                            int kind = -1;
-                            if (pr == ('T' | 'C' << 8)) kind = rev;
-                            else if (pr == ('A' | 'G' << 8)) kind = 1 - rev;
-                            else if (pr == ('C' | 'T' << 8)) kind = 2 + rev;
-                            else if (pr == ('G' | 'A' << 8)) kind = 3 - rev;
-                            if (kind < 0) continue;
-                            const u32 qv = (u32)(q64 >> sh) & 0xFFu;
-                            if (kind < 2) {
-                                const int qi = q0 + (sh >> 3);
-                                int pp = (rev ? nq - 1 - qi : qi) + 1;          // _corr_this_base, rescale.py:49-79
-                                const int back = pp - nq - 1;
-                                if (!fwd_only && pp >= -back) pp = back;
-                                const int key = pp > 0 ? (pp <= a.len5p ? pp : 0) : (-pp <= a.len3p ? a.len5p - pp : 0);
-                                const int ti = kind * npos + key;
-                                mr += t_term[ti];                                // (x + 0.0 == x: a zero term changes nothing)
-                                if (qv <= 93) {
-                                    const u32 newq = t_lut[ti * 94 + qv];
-                                    if (a.patch) patch_put(a.patch, a.n_patch, a.patch_cap, a.patch_parts, newq != qv, sb + (u32)qi, newq);
-                                    else if (newq != qv) a.qual_out[sb + (u32)qi] = (u8)newq;
-                                    if (a.subs) sub_bump(756 + ti * 94 + qv);
-                                }
-                            } else if (qv <= 93 && a.subs) {
-                                sub_bump(4 + (kind == 2 ? 2 : 6) * 94 + qv);    // "before" words of T>C / A>G
-                            }
-                        }
-                    }
-                }
-                q += step; r += step;
-            } else if (op == 1) {
-                q += step;
-            } else if (op == 2) {
-                // deletion columns pair '-' with a reference base, counted while read bases remain in the
-                // iteration order (`if pos_on_read < length_read`, rescale.py:252)
-                if (a.subs && (rev ? q > 0 : q < nq)) {
-                    const int r0 = rev ? r - len : r;
-                    for (int done = 0; done < len; done += 8) {
-                        const u32x2 rv = *(const u32x2_u *)(a.ref + rbase + r0 + done);
-                        count_bases((u64)rv.x | ((u64)rv.y << 32), byte_range(0, len - done < 8 ? len - done : 8));
-                    }
-                }
-                r += step;
-            }
-            // (a reference skip, N, moves nothing: the reference's alignment strings know insertions and deletions
-            //  only — align.py:53-73 — so the bases behind a skip face the skipped stretch itself)
-        }
-        a.mr_raw[ri] = mr;
-        return false;
-    };
-
-    // 64 records at a time, then one by one those the lanes handed back
-    auto pass = [&](const bool have, const i64 ri) __attribute__((always_inline)) {
-        const bool hand = have && walk(ri);
-        u64 m = __ballot(hand);
-        while (m) {
-            const int j = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            generic(((i64)rl((int)(ri >> 32), j) << 32) | (u32)rl((int)(ri & 0xFFFFFFFFll), j));
-        }
-    };
-    if (a.gen_list) {
-        const u32 *__restrict__ mine = a.gen_list + gwave * a.gen_cap;
-        const u32 n = a.gen_count[gwave];
-        for (u32 k0 = 0; k0 < n; k0 += 64) pass(k0 + lane < n, k0 + lane < n ? (i64)mine[k0 + lane] : 0);
-    } else {
-        const i64 ntiles = (a.n_reads + 63) / 64;
-        for (i64 tile = gwave; tile < ntiles; tile += nwaves) pass(tile * 64 + lane < a.n_reads, tile * 64 + lane);
-    }
-    if (a.subs && a.lds_tables) {
-        // the block's own row of subs_part, as in rescale_kernel (rows a.row_base ..)
-        __syncthreads();
-        for (int b = 0; b < 4; b++) {
-            u32 v = bc[b];
-            for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0 && v) atomicAdd(&l_cnt[b], v);
-        }
-        __syncthreads();
-        u32 *__restrict__ row = a.subs_part + (size_t)(a.row_base + blockIdx.x) * n_cnt;
-        for (int i = threadIdx.x; i < n_cnt; i += blockDim.x) row[i] = l_cnt[i];
-    } else if (a.subs) {
-        for (int b = 0; b < 4; b++) {
-            u32 v = bc[b];
-            for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0 && v) atomicAdd(&a.subs[b], (u64)v);
-        }
-    }
-}
-
-// subs[4 + i] += sum over the blocks' rows of word i; words 0..3 of a row are the block's reference-base counts.
-// blockIdx.y picks every RS_RED_Y-th row (one thread walking all rows of a word took 0.18 ms on its own).
-#define RS_RED_Y 32
-__global__ void rescale_reduce_kernel(const u32 *__restrict__ part, int rows, int n_cnt, u64 *__restrict__ subs) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_cnt) return;
-    u64 v = 0;
-#pragma unroll 4
-    for (int r = blockIdx.y; r < rows; r += RS_RED_Y) v += part[(size_t)r * n_cnt + i];
-    if (v) atomicAdd(&subs[i < 4 ? i : 4 + i], v);
-}
-
-static size_t rs_lds_bytes(int npos, bool staging) {
-    return (size_t)((2 * npos * 94 + 15) & ~15) + (size_t)2 * npos * 8 + (((size_t)(752 + 2 * npos * 94) * 4 + 15) & ~(size_t)15) +
-           (staging ? (size_t)(RS_BLOCK / 64) * RS_STG * 16 : 0);
-}
-
-void mdx_k_rescale(const MdxRescaleArgs &a0, int n_cu, hipStream_t s) {
-    if (a0.n_reads <= 0) return;
-    MdxRescaleArgs a = a0;
-    const int npos = 1 + a.len5p + a.len3p;
-    const size_t need = rs_lds_bytes(npos, true);
-    a.lds_tables = (a.key0_plain && 2 * npos < 255 && need <= 60 * 1024 && a.gen_list && a.gen_count && a.subs_part) ? 1 : 0;
-    // one launch-sized grid (RS_BPC blocks per CU); the tiles are dealt round-robin to the wavefronts
-    const int64_t want = (a.n_reads + RS_BLOCK - 1) / RS_BLOCK;
-    const int grid = (int)(want < (int64_t)n_cu * RS_BPC ? want : (int64_t)n_cu * RS_BPC);
-    const int n_cnt = 752 + 2 * npos * 94;
-    if (a.lds_tables) {
-        a.copy_qual = (a.qual_out != a.qual && !a.patch) ? 1 : 0;      // the fast kernel copies the quality column as it goes
-        if (need > 48 * 1024)
-            (void)hipFuncSetAttribute((const void *)rescale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-        hipLaunchKernelGGL(rescale_kernel, dim3(grid), dim3(RS_BLOCK), need, s, a);
-        // what it left out (same grid: wavefront w reads the list wavefront w wrote), then the summary rows of both
-        a.row_base = grid;
-        hipLaunchKernelGGL(rescale_walk_kernel, dim3(grid), dim3(RS_BLOCK), rs_lds_bytes(npos, false), s, a);
-        if (a.subs)
-            hipLaunchKernelGGL(rescale_reduce_kernel, dim3((n_cnt + 255) / 256, RS_RED_Y), dim3(256), 0, s, a.subs_part, 2 * grid, n_cnt, a.subs);
-    } else {
-        // no fast path: every record by the walk; summary counters in the LDS when those alone fit
-        const size_t walk_lds = rs_lds_bytes(npos, false);
-        if (a.qual_out != a.qual && !a.patch)
-            (void)hipMemcpyAsync(a.qual_out, a.qual, (size_t)a.n_bases, hipMemcpyDeviceToDevice, s);
-        a.gen_list = nullptr;
-        a.row_base = 0;
-        a.lds_tables = (2 * npos < 255 && walk_lds <= 60 * 1024 && a.subs_part) ? 1 : 0;
-        if (a.lds_tables && walk_lds > 48 * 1024)
-            (void)hipFuncSetAttribute((const void *)rescale_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds);
-        hipLaunchKernelGGL(rescale_walk_kernel, dim3(grid), dim3(RS_BLOCK), a.lds_tables ? walk_lds : 0, s, a);
-        if (a.subs && a.lds_tables)
-            hipLaunchKernelGGL(rescale_reduce_kernel, dim3((n_cnt + 255) / 256, RS_RED_Y), dim3(256), 0, s, a.subs_part, grid, n_cnt, a.subs);
-    }
-}
-
-void mdx_k_rescale_lists_pass(const MdxRescaleArgs &a0, int fused_rows, int n_cu, hipStream_t s) {
-    MdxRescaleArgs a = a0;
-    const int npos = 1 + a.len5p + a.len3p, n_cnt = 752 + 2 * npos * 94;
-    const size_t need = rs_lds_bytes(npos, true);
-    static_assert(RS_BPC * RS_BLOCK >= MDX_FUSE_BLOCK, "a wavefront of rescale_kernel per list of the fused kernel");
-    a.lds_tables = 1;
-    a.copy_qual = 0;
-    // every wavefront of the fused kernel has a list: as many wavefronts here, at least (a wavefront takes the lists
-    // l = its index, + the number of wavefronts, ...; its own list for the walk kernel holds what it leaves out)
-    int64_t want = ((int64_t)a.n_in * 64 + RS_BLOCK - 1) / RS_BLOCK;
-    if (want < 1) want = 1;
-    const int grid = (int)(want < (int64_t)n_cu * RS_BPC ? want : (int64_t)n_cu * RS_BPC);
-    if (need > 48 * 1024)
-        (void)hipFuncSetAttribute((const void *)rescale_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need);
-    a.subs_part = a0.subs_part + (size_t)fused_rows * n_cnt;
-    hipLaunchKernelGGL(rescale_kernel, dim3(grid), dim3(RS_BLOCK), need, s, a);
-    a.in_list = nullptr; a.in_count = nullptr; a.n_in = 0;
-    a.row_base = grid;
-    hipLaunchKernelGGL(rescale_walk_kernel, dim3(grid), dim3(RS_BLOCK), rs_lds_bytes(npos, false), s, a);
-    if (a.subs)
-        hipLaunchKernelGGL(rescale_reduce_kernel, dim3((n_cnt + 255) / 256, RS_RED_Y), dim3(256), 0, s, a0.subs_part,
-                           fused_rows + 2 * grid, n_cnt, a.subs);
-}
-
-// wavefronts of a launch over n_reads records, and the list entries each may need (its tiles x 64)
-void mdx_k_rescale_lists(int64_t n_reads, int n_cu, int64_t *n_waves, int64_t *cap) {
-    const int64_t want = (n_reads + RS_BLOCK - 1) / RS_BLOCK;
-    const int64_t grid = want < (int64_t)n_cu * RS_BPC ? want : (int64_t)n_cu * RS_BPC;
-    const int64_t nw = grid * (RS_BLOCK / 64), ntiles = (n_reads + 63) / 64;
-    *n_waves = nw > 0 ? nw : 1;
-    *cap = ((ntiles + *n_waves - 1) / *n_waves) * 64;
-}
-
-// a patch list applied: qual_out (a copy of the quality column, or the column itself) takes the new Phred of every entry;
-// blockIdx.y = the part of the list
-__global__ void rescale_expand_kernel(u8 *__restrict__ qual_out, const u64 *__restrict__ patch, const u64 *__restrict__ n_patch, long long cap,
-                                      i64 n_bases) {
-    const u64 n = n_patch[blockIdx.y] < (u64)cap ? n_patch[blockIdx.y] : (u64)cap;
-    const u64 *__restrict__ mine = patch + (size_t)blockIdx.y * (size_t)cap;
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-        const u64 e = mine[i];
-        const u32 idx = (u32)e;
-        if ((i64)idx < n_bases) qual_out[idx] = (u8)(e >> 32);
-    }
-}
-void mdx_k_rescale_expand(const uint8_t *qual, uint8_t *qual_out, int64_t n_bases, const unsigned long long *patch,
-                          const unsigned long long *n_patch, long long patch_cap, int patch_parts, hipStream_t s) {
-    if (n_bases <= 0 || patch_parts <= 0) return;
-    if (qual_out != qual) (void)hipMemcpyAsync(qual_out, qual, (size_t)n_bases, hipMemcpyDeviceToDevice, s);
-    hipLaunchKernelGGL(rescale_expand_kernel, dim3(16, patch_parts), dim3(256), 0, s, qual_out, (const u64 *)patch, (const u64 *)n_patch, patch_cap, (i64)n_bases);
-}
-
-size_t mdx_k_rescale_part_bytes(int len5p, int len3p, int n_cu) {
-    return (size_t)2 * n_cu * RS_BPC * (size_t)(752 + 2 * (1 + len5p + len3p) * 94) * 4;   // rows of both kernels
 }
