@@ -462,6 +462,25 @@ int64_t mdx_bam_ref_length(const mdx_bam *bam, int32_t i);
 int mdx_bam_batch(const mdx_bam *bam, mdx_batch *view, const int32_t **mtid, const int32_t **mpos,
                   const int32_t **rg_index, const uint8_t **has_mr);
 const uint8_t *mdx_bam_qmin(const mdx_bam *bam);     /* lowest quality per record (0xFF: none) */
+
+/* Record filters (--min-mapq, --require-flags, --exclude-flags, --min-read-length, --max-read-length; none is a reference
+ * option).  A record is dropped when (FLAG & require_flags) != require_flags, when (FLAG & exclude_flags) != 0, when
+ * MAPQ < min_mapq (numeric: 255 passes any threshold), when l_seq < min_length, or when max_length > 0 and l_seq > max_length
+ * — evaluated in that order, on the 16 flag bits as the file carries them; l_seq is the length of the SEQ field (0 for a
+ * SAM '*'), not the CIGAR's query length.  A dropped record keeps its place in the batch and gets 0x200 OR-ed into its
+ * entry of the flag column by the decoder, which the flag filter of every kernel (0xF04) drops: nothing downstream takes a
+ * filter argument.  counts[6] = records read, then the records dropped by each of the five reasons (a record counts under
+ * the first that drops it; every record of the input is evaluated, also those the flag filter drops anyway).
+ * mdx_bam_apply_record_filter marks the flag column of a decoded mdx_bam (mdx_bam_read, every chunk of mdx_bam_next) and
+ * ADDS to counts (may be NULL); NULL or all-zero filter: nothing is marked, counts[0] += the records.  It tests the flag
+ * bits the decoder read from the file, not the column — marks made since (its own, --downsample's 0x200) are not looked at —;
+ * every call counts the batch again, so one call per decoded batch. */
+typedef struct mdx_record_filter {
+    int32_t min_mapq;
+    uint32_t require_flags, exclude_flags;
+    int32_t min_length, max_length;
+} mdx_record_filter;
+int mdx_bam_apply_record_filter(mdx_bam *bam, const mdx_record_filter *filter, uint64_t counts[6]);
 int32_t mdx_bam_n_rg(const mdx_bam *bam);
 const char *mdx_bam_rg_name(const mdx_bam *bam, int32_t i);
 const char *mdx_bam_qnames(const mdx_bam *bam, const uint32_t **offsets);
@@ -569,6 +588,15 @@ int mdx_gbam_set_min_basequal(mdx_gbam *g, int32_t minqual);
  * the views of mdx_gbam_next then carry seq_format = MDX_SEQ_4BIT.  Default MDX_SEQ_ASCII. */
 int mdx_gbam_set_seq_format(mdx_gbam *g, int32_t seq_format);
 int mdx_gbam_missing_qualities(const mdx_gbam *g);
+/* The record filter of the device path (mdx_record_filter above): set any time before the first mdx_gbam_next (MDX_ERR_STATE
+ * behind it; NULL or all zero: off).  The unpack kernel evaluates it on the record's fixed fields and ORs 0x200 into the flag
+ * column and sums the reasons on the device: no copy and no wait per slab.  mdx_gbam_filter_counts: the six counts,
+ * cumulative over the slabs decoded so far (skipped slabs are not read); it waits for the context's stream.  The records
+ * read count the slabs handed out; a slab whose mdx_gbam_next FAILED behind its unpack launch (a block that fails its CRC32,
+ * a HIP error) may have added to the five reasons already — such a file ends in the host decoder's error for the same
+ * block, and a caller that goes on regardless should take the counts before the call, not after. */
+int mdx_gbam_set_record_filter(mdx_gbam *g, const mdx_record_filter *filter);
+int mdx_gbam_filter_counts(const mdx_gbam *g, uint64_t out[6]);
 int mdx_gbam_at_end(const mdx_gbam *g);
 /* Steps over the slab mdx_gbam_next would decode next (same chunk_bytes, same borders) without touching the device: in a
  * run over several GPUs (one process and one mdx_gbam per GPU) rank r decodes the slabs r, r + N, ... and skips
@@ -672,6 +700,11 @@ int mdx_gsam_view_flags(mdx_gsam *g, uint16_t *flags, int64_t n);
 int mdx_gsam_view_set_flags(mdx_gsam *g, const uint16_t *flags, int64_t n);
 /* a record the kernel counts has come by without qualities so far (under mdx_gsam_set_min_basequal; main.py:185-192) */
 int mdx_gsam_missing_qualities(const mdx_gsam *g);
+/* The record filter, as mdx_gbam_set_record_filter / mdx_gbam_filter_counts.  With a MAPQ threshold the field pass parses
+ * field 5: anything but 1 to 3 digits with a value of 255 or less gives the slab up to the host parser (MDX_ERR_UNSUPPORTED).
+ * A slab that is given up adds nothing to the counts. */
+int mdx_gsam_set_record_filter(mdx_gsam *g, const mdx_record_filter *filter);
+int mdx_gsam_filter_counts(const mdx_gsam *g, uint64_t out[6]);
 void mdx_gsam_close(mdx_gsam *g);
 
 /* ---- The Bayesian estimate of the damage parameters on the device (additions of ABI 6): mapdamage/r/stats/ — the model of

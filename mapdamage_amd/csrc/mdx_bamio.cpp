@@ -6,6 +6,7 @@
 #ifndef MDX_HOST_ONLY      // (tools/sanitize/run_bamio.sh builds the host decoder alone, without the HIP runtime)
 #include "mdx_internal.h"
 #endif
+#include "mdx_filter.h"
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
@@ -127,6 +128,8 @@ struct mdx_bam {
     std::vector<std::string> rg_names;
     std::vector<uint8_t> has_mr;
     std::vector<uint8_t> qmin;       // lowest quality of each record (0xFF: no bases)
+    std::vector<uint8_t> mapq;       // MAPQ, and the file's own 16 flag bits (the column has 14 and 15 cleared and takes marks):
+    std::vector<uint16_t> flag_file; // what mdx_bam_apply_record_filter tests
     // the chunk's encoded records as they stood in the file (mdx_bam_stream_keep_raw): rewriting a BAM preserves every
     // byte it does not change.  rec_off[i] = offset of record i's block_size field, rec_off[n] = end
     raw_bytes raw;
@@ -733,6 +736,7 @@ int unpack_records(mdx_bam *b, const uint8_t *data, size_t off, size_t total, in
     lap(scanned ? "scan (par.)" : "record scan");
     b->flag.resize(n); b->lib.assign(n, 0); b->tid.resize(n); b->pos.resize(n); b->tlen.resize(n);
     b->mtid.resize(n); b->mpos.resize(n); b->rg_index.assign(n, -1); b->has_mr.assign(n, 0); b->qmin.resize(n);
+    b->mapq.resize(n); b->flag_file.resize(n);
     b->cigar_off = coff; b->seq_off = soff; b->qname_off = noff;
     b->cigar.resize(coff.back()); b->seq.resize((size_t)soff.back() + 64); b->qual.resize((size_t)soff.back() + 64);
     b->qnames.resize(noff.back());
@@ -750,6 +754,7 @@ int unpack_records(mdx_bam *b, const uint8_t *data, size_t off, size_t total, in
         const int32_t l_seq = rdi32(r + 16);
         b->tid[i] = rdi32(r); b->pos[i] = rdi32(r + 4); b->flag[i] = (uint16_t)(rd16(r + 14) & 0x3FFFu);   // bits 14, 15: MDX_FLAG_HAS_QUAL / _QUAL_ABOVE_MIN, hints, never the file's
         b->mtid[i] = rdi32(r + 20); b->mpos[i] = rdi32(r + 24); b->tlen[i] = rdi32(r + 28);
+        b->mapq[i] = r[9]; b->flag_file[i] = (uint16_t)rd16(r + 14);
         const uint8_t *p = r + 32;
         if (l_name) std::memcpy(&b->qnames[noff[i]], p, l_name - 1);
         p += l_name;
@@ -884,6 +889,23 @@ static int bam_read(mdx_source *file, bool owned, int threads, mdx_bam *b) {
     b->reaper = std::thread([](raw_bytes d) { raw_bytes().swap(d); }, std::move(data));
     lap("release");
     return rc;
+}
+
+// ---- the checks of a caller's mdx_record_filter, for every decoder (mdx_internal.h)
+bool mdx_record_filter_valid(const mdx_record_filter *f) {
+    return !f || (f->min_mapq >= 0 && f->min_mapq <= 255 && f->require_flags <= 0xFFFFu && f->exclude_flags <= 0xFFFFu && f->min_length >= 0 &&
+                  f->max_length >= 0 && (f->max_length == 0 || f->min_length <= f->max_length));
+}
+bool mdx_record_filter_active(const mdx_record_filter *f) {
+    return f && (f->min_mapq || f->require_flags || f->exclude_flags || f->min_length || f->max_length);
+}
+MdxFilterArgs mdx_record_filter_args(const mdx_record_filter *f, unsigned long long *counts) {
+    MdxFilterArgs a{};
+    if (mdx_record_filter_active(f)) {
+        a.on = 1; a.min_mapq = f->min_mapq; a.require = f->require_flags; a.exclude = f->exclude_flags;
+        a.min_len = f->min_length; a.max_len = f->max_length; a.counts = counts;
+    }
+    return a;
 }
 
 extern "C" {
@@ -1038,6 +1060,23 @@ int mdx_bam_batch(const mdx_bam *b, mdx_batch *view, const int32_t **mtid, const
 }
 
 const uint8_t *mdx_bam_qmin(const mdx_bam *b) { return b ? b->qmin.data() : nullptr; }
+
+int mdx_bam_apply_record_filter(mdx_bam *b, const mdx_record_filter *filter, uint64_t counts[6]) {
+    if (!b || !mdx_record_filter_valid(filter)) return MDX_ERR_ARG;
+    const size_t n = b->flag.size();
+    if (counts) counts[0] += n;
+    if (!mdx_record_filter_active(filter)) return MDX_OK;
+    if (b->mapq.size() != n || b->flag_file.size() != n) return MDX_ERR_STATE;
+    const MdxFilterArgs f = mdx_record_filter_args(filter, nullptr);
+    uint64_t dropped[5] = {0, 0, 0, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+        // (the 16 bits as the file carries them: whatever has been OR-ed into the column since does not count)
+        const int why = mdx_filter_reason(f, b->flag_file[i], b->mapq[i], b->seq_off[i + 1] - b->seq_off[i]);
+        if (why >= 0) { b->flag[i] |= 0x200u; dropped[why]++; }
+    }
+    if (counts) for (int k = 0; k < 5; k++) counts[1 + k] += dropped[k];
+    return MDX_OK;
+}
 
 int32_t mdx_bam_n_rg(const mdx_bam *b) { return b ? (int32_t)b->rg_names.size() : 0; }
 
@@ -1470,6 +1509,13 @@ struct mdx_gbam {
     int minqual = 0;                     // --min-basequal on the device path (mdx_gbam_set_min_basequal)
     int seq_format = MDX_SEQ_ASCII;      // form of the seq column handed out (mdx_gbam_set_seq_format)
     bool no_qual_seen = false;           // a counted record without qualities has come by
+    // the record filter (mdx_gbam_set_record_filter) and its counts: records read, dropped by each of the five reasons
+    // (the five reasons are summed on the device, in 64-bit words of the handle's own that the unpack kernels of all slabs add
+    // to — nothing is copied or waited for per slab; mdx_gbam_filter_counts reads them behind the context's stream)
+    mdx_record_filter filter{};
+    bool filter_on = false;
+    uint64_t records_read = 0;
+    unsigned long long *d_filter_counts = nullptr;
     // read groups
     std::vector<uint8_t> rg_names;
     std::vector<uint32_t> rg_off;
@@ -2140,6 +2186,7 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
     if (c.seq_packed && hipMemsetAsync(c.seq, 0, (size_t)(tot[2] + 1) / 2 + 8, st) != hipSuccess) return MDX_ERR_HIP;
     // (--min-basequal: the mask goes into the nibbles — MDX_SEQ_4BITQ, the packed masked kernel's input)
     c.fold = (c.minqual > 0 && c.seq_packed) ? 1 : 0;
+    c.filter = mdx_record_filter_args(g->filter_on ? &g->filter : nullptr, g->d_filter_counts);
     mdx_k_gbam_unpack((const uint8_t *)s.unc.p, (const uint4 *)s.pre.p, (const uint4 *)s.cnt.p, (int)nb,
                       (uint32_t)tot[0], (uint32_t)tot[1], (uint32_t)tot[2], (uint32_t *)s.rec_off.p, c, st);
     if (hipGetLastError() != hipSuccess) { g->error = "GPU unpack launch failed"; return MDX_ERR_HIP; }
@@ -2157,6 +2204,7 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
         // nothing in this slab can be masked: the unmasked kernel (no nibble of the column is a complement)
         if (counters[1] == 0) { view->qual = nullptr; view->seq_format = g->seq_format; }
     }
+    g->records_read += tot[0];
     if (d_mtid) *d_mtid = c.mtid;
     if (d_mpos) *d_mpos = c.mpos;
     g->last_view = *view; g->last_mtid = c.mtid; g->last_mpos = c.mpos;
@@ -2383,6 +2431,36 @@ int mdx_gbam_set_seq_format(mdx_gbam *g, int32_t seq_format) {
 
 int mdx_gbam_missing_qualities(const mdx_gbam *g) { return (g && g->no_qual_seen) ? 1 : 0; }
 
+int mdx_gbam_set_record_filter(mdx_gbam *g, const mdx_record_filter *filter) {
+    if (!g) return MDX_ERR_ARG;
+    if (!mdx_record_filter_valid(filter)) { g->error = "mdx_gbam_set_record_filter: a value out of range (MAPQ 0..255, flags 0..65535, lengths >= 0, min <= max)"; return MDX_ERR_ARG; }
+    if (g->slabs_done > 0 || g->records_read > 0) { g->error = "mdx_gbam_set_record_filter: behind the first mdx_gbam_next"; return MDX_ERR_STATE; }
+    const bool on = mdx_record_filter_active(filter);
+    if (on && !g->d_filter_counts) {
+        if (hipSetDevice(g->device) != hipSuccess || hipMalloc((void **)&g->d_filter_counts, 5 * sizeof(unsigned long long)) != hipSuccess ||
+            hipMemset(g->d_filter_counts, 0, 5 * sizeof(unsigned long long)) != hipSuccess) {
+            g->error = "mdx_gbam_set_record_filter: no device memory for the counts";
+            return MDX_ERR_HIP;
+        }
+    }
+    g->filter_on = on;
+    g->filter = on ? *filter : mdx_record_filter{};
+    return MDX_OK;
+}
+
+int mdx_gbam_filter_counts(const mdx_gbam *g, uint64_t out[6]) {
+    if (!g || !out) return MDX_ERR_ARG;
+    unsigned long long dropped[5] = {0, 0, 0, 0, 0};
+    if (g->d_filter_counts) {
+        // (behind the unpack kernels of every slab handed out so far)
+        if (hipSetDevice(g->device) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess ||
+            hipMemcpy(dropped, g->d_filter_counts, sizeof(dropped), hipMemcpyDeviceToHost) != hipSuccess) return MDX_ERR_HIP;
+    }
+    out[0] = g->records_read;
+    for (int k = 0; k < 5; k++) out[1 + k] = dropped[k];
+    return MDX_OK;
+}
+
 int mdx_gbam_at_end(const mdx_gbam *g) { return (!g || (g->next_block >= g->blocks.size() && g->whole_file_scanned())) ? 1 : 0; }
 
 void mdx_gbam_close(mdx_gbam *g) {
@@ -2416,6 +2494,7 @@ void mdx_gbam_close(mdx_gbam *g) {
     }
     g->copy_stream = nullptr;
     rg_buffer_give(g->device, g->d_rg, g->d_rg_cap);
+    if (g->d_filter_counts) (void)hipFree(g->d_filter_counts);
     for (int k = 0; k < 3; k++) pf_buffer_give(g->device, g->pf_buf[k], g->pf_cap[k]);
     lap("device");
     // (unmapping the file — a few hundred thousand touched pages — is 3-4 ms of an 8 M-record file's 63; done behind the
@@ -2701,3 +2780,4 @@ int mdx_warm(int32_t device, int64_t pinned_bytes) {
 #endif  // MDX_HOST_ONLY
 
 }  // extern "C"
+

@@ -176,13 +176,31 @@ __global__ void gbam_offsets_kernel(const u8 *__restrict__ unc, const uint4 *__r
 __global__ void gbam_unpack_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off, u32 n_rec, MdxGbamCols c) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 r = t >> 3, j = t & 7u;
+    // The record filter (include/mdx.h mdx_record_filter), by the lane that writes the record's flag, from bytes it reads
+    // anyway: MAPQ, the file's 16 flag bits, l_seq.  A dropped record keeps its place and gets 0x200, which every flag filter
+    // downstream drops.  The counts per reason are summed in the LDS and leave the block as one atomic per reason that has any
+    // (thirty-two records: per-record atomics on five words of one line would queue at the L2, see --min-basequal below).
+    // In front of the first return: every lane of the block reaches the barriers.  Off: one uniform branch.
+    u32 fdrop = 0;
+    if (c.filter.on) {
+        __shared__ u32 f_cnt[5];
+        if (threadIdx.x < 5u) f_cnt[threadIdx.x] = 0;
+        __syncthreads();
+        if (r < n_rec && j == 0) {
+            const u8 *__restrict__ f = unc + rec_off[r];
+            const int why = mdx_filter_reason(c.filter, g16(f + 14), f[9], g32(f + 16));
+            if (why >= 0) { fdrop = 0x200u; atomicAdd(&f_cnt[why], 1u); }
+        }
+        __syncthreads();
+        if (threadIdx.x < 5u && f_cnt[threadIdx.x]) atomicAdd(c.filter.counts + threadIdx.x, (unsigned long long)f_cnt[threadIdx.x]);
+    }
     if (r >= n_rec) return;
     typedef u32 u32u __attribute__((aligned(1)));
     const u8 *__restrict__ p = unc + rec_off[r];
     const u32 bs = g32(p - 4);
     const u32 l_name = p[8], n_cig = g16(p + 12), l_seq = g32(p + 16);
     if (j == 0) {
-        c.flag[r] = (uint16_t)(g16(p + 14) & 0x3FFFu);     // bits 14 and 15 are the hints MDX_FLAG_HAS_QUAL / _QUAL_ABOVE_MIN, never the file's
+        c.flag[r] = (uint16_t)((g16(p + 14) & 0x3FFFu) | fdrop);     // bits 14 and 15 are the hints MDX_FLAG_HAS_QUAL / _QUAL_ABOVE_MIN, never the file's
         c.tid[r] = (int32_t)g32(p); c.pos[r] = (int32_t)g32(p + 4);
         c.tlen[r] = (int32_t)g32(p + 28);
         if (c.mtid) { c.mtid[r] = (int32_t)g32(p + 20); c.mpos[r] = (int32_t)g32(p + 24); }
@@ -271,12 +289,12 @@ __global__ void gbam_unpack_kernel(const u8 *__restrict__ unc, const u32 *__rest
     if (j != 0) return;
     // (MDX_FLAG_HAS_QUAL: the rescaling kernels need not look at the record's first quality to route it, rescale.py:306)
     const u32 hasq = (c.qual && l_seq > 0u && q[0] != 0xFFu) ? 0x4000u : 0u;
-    if (hasq) c.flag[r] = (uint16_t)((g16(p + 14) & 0x3FFFu) | hasq);
+    if (hasq) c.flag[r] = (uint16_t)((g16(p + 14) & 0x3FFFu) | fdrop | hasq);
     if (c.qual && c.minqual > 0) {
         // --min-basequal: a record none of whose qualities is below the threshold cannot be masked (flag bit
         // MDX_FLAG_QUAL_ABOVE_MIN: the tabulation kernel skips its quality windows); a counted record without
         // qualities is what main.py:185-192 warns about
-        const u32 fl = (g16(p + 14) & 0x3FFFu) | hasq;
+        const u32 fl = (g16(p + 14) & 0x3FFFu) | fdrop | hasq;      // (a record the filter drops is not a counted one: no warning)
         if (qmin >= (u32)c.minqual) c.flag[r] = (uint16_t)(fl | 0x8000u);
         // (only whether there is one matters: a store where the word is still clear — eight million atomics on one address
         // were 10 ms of the 11.6 ms this kernel took on a file with qualities)

@@ -235,8 +235,9 @@ __device__ __forceinline__ int cigar_code(u32 c) {
 // otherwise than this parser — or raise on — sets its reason in status[0] and the lowest such line in status[1].
 __global__ __launch_bounds__(kBlock) void gsam_fields_kernel(const u8 *__restrict__ txt, const u32 *__restrict__ tab_bits,
                                                               const u32 *__restrict__ line_end, u32 n_lines, MdxGsamNames refs,
-                                                              MdxGsamNames rgs, int lib_default, uint4 *__restrict__ cnt,
-                                                              MdxGsamLine *__restrict__ ldata, u32 *__restrict__ status) {
+                                                              MdxGsamNames rgs, int lib_default, MdxFilterArgs filter,
+                                                              uint4 *__restrict__ cnt, MdxGsamLine *__restrict__ ldata,
+                                                              u32 *__restrict__ status) {
     const u32 t = blockIdx.x * kBlock + threadIdx.x;
     const u32 line = t >> 3, j = t & 7u;
     if (line >= n_lines) return;
@@ -292,6 +293,20 @@ __global__ __launch_bounds__(kBlock) void gsam_fields_kernel(const u8 *__restric
                 flag = flag * 10u + d;
             }
             if (flag > 65535u) give_up(MDX_GSAM_BAD_FLAG);
+        }
+    }
+    // MAPQ, under a threshold only (read_sam reads it only then): 1-3 digits, at most 255
+    u32 mapq = 0;
+    if (filter.min_mapq > 0) {
+        const u32 a = fa(4), b = fb(4);
+        if (b - a < 1u || b - a > 3u) give_up(MDX_GSAM_BAD_MAPQ);
+        else {
+            for (u32 i = a; i < b; i++) {
+                const u32 d = txt[i] - '0';
+                if (d >= 10u) { give_up(MDX_GSAM_BAD_MAPQ); break; }
+                mapq = mapq * 10u + d;
+            }
+            if (mapq > 255u) give_up(MDX_GSAM_BAD_MAPQ);
         }
     }
     long long pos = 0, tlen = 0;
@@ -368,8 +383,21 @@ __global__ __launch_bounds__(kBlock) void gsam_fields_kernel(const u8 *__restric
     if (why) { atomicOr(status, why); atomicMin(status + 1, line); }
     out = make_uint4(1u, n_ops, nb, 0u);
     cnt[line] = out;
+    // the record filter (include/mdx.h mdx_record_filter) on the file's 16 flag bits, MAPQ and the length of SEQ: a dropped
+    // record gets 0x200; the counts leave the wavefront as one atomic per reason (its eight records' lanes are the active ones)
+    u32 fdrop = 0;
+    if (filter.on) {
+        const int reason = why ? -1 : mdx_filter_reason(filter, flag, mapq, nb);       // (a slab given up counts nothing)
+        if (reason >= 0) fdrop = 0x200u;
+        const unsigned long long here = __ballot(1);
+        const u32 leader = (u32)__ffsll(here) - 1u;
+        for (int k = 0; k < 5; k++) {
+            const unsigned long long m = __ballot(reason == k);
+            if (m && (threadIdx.x & 63u) == leader) atomicAdd(filter.counts + k, (unsigned long long)__popcll(m));
+        }
+    }
     MdxGsamLine d;
-    d.flag_lib = (flag & 0x3FFFu) | ((u32)(lib < 0 ? 0xFFFF : lib) << 16);
+    d.flag_lib = (flag & 0x3FFFu) | fdrop | ((u32)(lib < 0 ? 0xFFFF : lib) << 16);
     d.tid = tid; d.pos = (int32_t)(pos - 1); d.tlen = (int32_t)tlen;
     d.cigar_a = ca; d.cigar_b = no_cigar ? ca : cb; d.seq_a = sa; d.qual_a = no_qual ? kNone : qa;
     ldata[line] = d;
@@ -490,10 +518,11 @@ void mdx_k_gsam_line_ends(const uint32_t *nl_bits, uint32_t n, const uint4 *blk_
 }
 
 void mdx_k_gsam_fields(const uint8_t *txt, const uint32_t *tab_bits, const uint32_t *line_end, uint32_t n_lines, const MdxGsamNames &refs,
-                       const MdxGsamNames &rgs, int lib_default, uint4 *cnt, MdxGsamLine *ldata, uint4 *part, uint32_t *status, hipStream_t s) {
+                       const MdxGsamNames &rgs, int lib_default, const MdxFilterArgs &filter, uint4 *cnt, MdxGsamLine *ldata, uint4 *part,
+                       uint32_t *status, hipStream_t s) {
     if (n_lines > 0)
         hipLaunchKernelGGL(gsam_fields_kernel, dim3((n_lines + 31u) / 32u), dim3(kBlock), 0, s, txt, tab_bits, line_end, n_lines, refs, rgs,
-                           lib_default, cnt, ldata, status);
+                           lib_default, filter, cnt, ldata, status);
     scan3(cnt, n_lines, part, s);
 }
 

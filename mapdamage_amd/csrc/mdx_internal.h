@@ -464,6 +464,9 @@ extern "C" int mdx_ctx_minqual(const mdx_ctx *c);        // the context's --min-
 extern "C" void mdx_ctx_scratch_give(mdx_ctx *c, void *arena, size_t cap, void *tables, void *stream, void *event);
 extern "C" void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, void **stream, void **event);
 
+// ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
+#include "mdx_filter.h"
+
 // ---- GPU-side BAM decode (mdx_gbam.hip; host side: mdx_gbam_* in mdx_bamio.cpp)
 struct MdxGbamCols {
     uint16_t *flag, *lib;
@@ -484,6 +487,7 @@ struct MdxGbamCols {
     // ... and a 4-bit SEQ column takes the mask into its nibbles (MDX_SEQ_4BITQ: a base whose quality is below the threshold
     // is stored as the complement of its code)
     int fold;
+    MdxFilterArgs filter;           // the record filter (on 0: the kernel's work is what it is without)
 };
 size_t mdx_k_gbam_inflate_lds();
 hipError_t mdx_k_gbam_prepare();
@@ -534,7 +538,9 @@ enum {
     MDX_GSAM_BAD_INT = 8,           // POS or TLEN not -?[0-9]+ or outside int32
     MDX_GSAM_BAD_CIGAR = 16,        // a byte outside [0-9MIDNSHP=X], a length of 2^28 or more, digits without an operation
     MDX_GSAM_BAD_QUAL = 32,         // QUAL not '*' and not as long as SEQ (SEQ '*' too), or a byte below 33
+    MDX_GSAM_BAD_MAPQ = 64,         // (under a MAPQ threshold only) MAPQ not 1-3 digits, or above 255
 };
+
 // an open-addressing hash of names (FNV-1a, linear probing): names concatenated, off[n + 1], table[mask + 1] (-1: empty),
 // value[n] (the library of a read group; unused for references)
 struct MdxGsamNames {
@@ -547,7 +553,7 @@ struct MdxGsamNames {
 };
 // what the field pass leaves for the fill pass, per line (32 bytes)
 struct MdxGsamLine {
-    uint32_t flag_lib;              // FLAG & 0x3FFF | library << 16
+    uint32_t flag_lib;              // FLAG & 0x3FFF (| 0x200: dropped by the record filter) | library << 16
     int32_t tid, pos, tlen;
     uint32_t cigar_a, cigar_b;      // the CIGAR field's bytes (empty for '*')
     uint32_t seq_a, qual_a;         // where SEQ and QUAL start (qual_a 0xFFFFFFFF: '*')
@@ -574,7 +580,8 @@ void mdx_k_gsam_last_newline(const uint32_t *nl_bits, uint32_t n, uint32_t *last
 void mdx_k_gsam_line_ends(const uint32_t *nl_bits, uint32_t n, const uint4 *blk_nl, uint32_t *line_end, hipStream_t s);
 // the field pass and the scan of its counts: cnt[line] = (records, operations, bases in front of it), cnt[n_lines] = totals
 void mdx_k_gsam_fields(const uint8_t *txt, const uint32_t *tab_bits, const uint32_t *line_end, uint32_t n_lines, const MdxGsamNames &refs,
-                       const MdxGsamNames &rgs, int lib_default, uint4 *cnt, MdxGsamLine *ldata, uint4 *part, uint32_t *status, hipStream_t s);
+                       const MdxGsamNames &rgs, int lib_default, const MdxFilterArgs &filter, uint4 *cnt, MdxGsamLine *ldata, uint4 *part,
+                       uint32_t *status, hipStream_t s);
 void mdx_k_gsam_fill(const uint8_t *txt, const uint4 *cnt, uint32_t n_lines, const MdxGsamLine *ldata, const MdxGsamCols &c, hipStream_t s);
 
 // (mdx_bamio.cpp) what the SAM decoder needs of a source and of a header-only mdx_bam

@@ -138,6 +138,7 @@ const char *why_text(uint32_t why) {
     if (why & MDX_GSAM_BAD_INT) return "POS or TLEN is not a 32-bit decimal integer";
     if (why & MDX_GSAM_BAD_CIGAR) return "a CIGAR the host parser words (unknown operation, 2^28 bases or more, digits without an operation)";
     if (why & MDX_GSAM_BAD_QUAL) return "QUAL is not '*' and does not fit SEQ (length, bytes below 33)";
+    if (why & MDX_GSAM_BAD_MAPQ) return "MAPQ is not 1-3 digits of at most 255";
     return "unknown";
 }
 
@@ -155,6 +156,10 @@ struct mdx_gsam {
     bool want_qual = false;
     int lib_default = -1, minqual = 0, seq_format = MDX_SEQ_ASCII;
     bool no_qual_seen = false;
+    // the record filter (mdx_gsam_set_record_filter) and its counts: records read, dropped by each of the five reasons
+    mdx_record_filter filter{};
+    bool filter_on = false, began = false;
+    uint64_t filter_counts[6] = {0, 0, 0, 0, 0, 0};
     int64_t view_reads = 0;
     DBuf d_refs, d_rgs;
     MdxGsamNames refs{}, rgs{};
@@ -445,11 +450,12 @@ int mdx_gsam::parse(Slot &s, mdx_batch *view) {
     const uint8_t *txt = (const uint8_t *)s.txt.p + begin;
     auto fail = [&](const char *what) { error = std::string("GPU SAM decode: ") + what; return MDX_ERR_HIP; };
     if (!reserve(nl, (size_t)nw * 4 + 64) || !reserve(tab, (size_t)nw * 4 + 64) || !reserve(blk, ((size_t)nblk + 1) * 16) ||
-        !reserve(part, mdx_k_gsam_scan_parts(nblk) * 16) || !reserve(status, 64)) return fail("out of device memory");
+        !reserve(part, mdx_k_gsam_scan_parts(nblk) * 16) || !reserve(status, 128)) return fail("out of device memory");
     uint32_t *d_status = (uint32_t *)status.p;
     // (status: [0] the reasons to give up, [1] the lowest line with one, [2, 4) the fill pass's counters)
-    // (... [4] compressed text: the offset behind the slab's last '\n')
-    if (hipStreamWaitEvent(st, s.ev_copied, 0) != hipSuccess || hipMemsetAsync(d_status, 0, 20, st) != hipSuccess ||
+    // (... [4] compressed text: the offset behind the slab's last '\n'; bytes [32, 72) the record filter's five 64-bit counts)
+    began = true;
+    if (hipStreamWaitEvent(st, s.ev_copied, 0) != hipSuccess || hipMemsetAsync(d_status, 0, 72, st) != hipSuccess ||
         hipMemsetAsync(d_status + 1, 0xFF, 4, st) != hipSuccess) return fail("enqueue failed");
     if (bgzf) {
         // (the input's last line gets its '\n' — behind one that has it, one more empty line)
@@ -485,11 +491,16 @@ int mdx_gsam::parse(Slot &s, mdx_batch *view) {
         !reserve(ldata, (size_t)n_lines * sizeof(MdxGsamLine) + 64) || !reserve(part, mdx_k_gsam_scan_parts(std::max(n_lines, nblk)) * 16))
         return fail("out of device memory");
     mdx_k_gsam_line_ends((const uint32_t *)nl.p, n, (const uint4 *)blk.p, (uint32_t *)line_end.p, st);
-    mdx_k_gsam_fields(txt, (const uint32_t *)tab.p, (const uint32_t *)line_end.p, n_lines, refs, rgs, lib_default, (uint4 *)cnt.p,
+    // (the counts come back with the field pass's verdict: one wait per slab, as without a filter)
+    const MdxFilterArgs fc = mdx_record_filter_args(filter_on ? &filter : nullptr, (unsigned long long *)(d_status + 8));
+    mdx_k_gsam_fields(txt, (const uint32_t *)tab.p, (const uint32_t *)line_end.p, n_lines, refs, rgs, lib_default, fc, (uint4 *)cnt.p,
                       (MdxGsamLine *)ldata.p, (uint4 *)part.p, d_status, st);
     uint32_t tot[4] = {0, 0, 0, 0}, why[2] = {0, 0};
+    unsigned long long dropped[5] = {0, 0, 0, 0, 0};
     if (hipMemcpyAsync(tot, (const uint4 *)cnt.p + n_lines, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(why, d_status, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        hipMemcpyAsync(why, d_status, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (filter_on && hipMemcpyAsync(dropped, d_status + 8, 40, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
         return fail("field pass failed");
     if (why[0]) {
         // (a byte the classify pass refuses has no line yet — compressed text: it may lie behind the slab's last '\n', in the next slab's line)
@@ -498,6 +509,9 @@ int mdx_gsam::parse(Slot &s, mdx_batch *view) {
         return MDX_ERR_UNSUPPORTED;
     }
     const size_t n_rec = tot[0], n_cig = tot[1], n_seq = tot[2];
+    // (a slab the host parser takes over has added nothing: its records are the host's to count)
+    filter_counts[0] += n_rec;
+    for (int k = 0; k < 5; k++) filter_counts[1 + k] += dropped[k];
     const bool packed = seq_format == MDX_SEQ_4BIT;
     if (!reserve(flag, n_rec * 2 + 64) || !reserve(lib, n_rec * 2 + 64) || !reserve(tid, n_rec * 4 + 64) || !reserve(pos_c, n_rec * 4 + 64) ||
         !reserve(tlen, n_rec * 4 + 64) || !reserve(cigar_off, n_rec * 4 + 68) || !reserve(seq_off, n_rec * 4 + 68) ||
@@ -791,6 +805,24 @@ int mdx_gsam_view_set_flags(mdx_gsam *g, const uint16_t *flags, int64_t n) {
 }
 
 int mdx_gsam_missing_qualities(const mdx_gsam *g) { return (g && g->no_qual_seen) ? 1 : 0; }
+
+int mdx_gsam_set_record_filter(mdx_gsam *g, const mdx_record_filter *f) {
+    if (!g) return MDX_ERR_ARG;
+    if (!mdx_record_filter_valid(f)) {
+        g->error = "mdx_gsam_set_record_filter: a value out of range (MAPQ 0..255, flags 0..65535, lengths >= 0, min <= max)";
+        return MDX_ERR_ARG;
+    }
+    if (g->began) { g->error = "mdx_gsam_set_record_filter: behind the first mdx_gsam_next"; return MDX_ERR_STATE; }
+    g->filter_on = mdx_record_filter_active(f);
+    g->filter = g->filter_on ? *f : mdx_record_filter{};
+    return MDX_OK;
+}
+
+int mdx_gsam_filter_counts(const mdx_gsam *g, uint64_t out[6]) {
+    if (!g || !out) return MDX_ERR_ARG;
+    for (int k = 0; k < 6; k++) out[k] = g->filter_counts[k];
+    return MDX_OK;
+}
 
 void mdx_gsam_close(mdx_gsam *g) {
     if (!g) return;

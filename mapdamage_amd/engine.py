@@ -49,6 +49,8 @@ EXPORTS = (
     "mdx_last_launch_geometry",
     "mdx_set_strata", "mdx_set_strata_regions", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
     "mdx_stats_loglik", "mdx_stats_run", "mdx_stats_pmat",
+    "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
+    "mdx_gsam_filter_counts",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -164,6 +166,9 @@ def load_library(path=None):
     lib.mdx_pack_seq.restype = ctypes.c_int
     lib.mdx_pack_seq.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32]
     lib.mdx_gbam_missing_qualities.argtypes = [ctypes.c_void_p]
+    for name in ("mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter", "mdx_gsam_filter_counts"):
+        getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_bam_apply_record_filter.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_gbam_close.restype = None
     lib.mdx_gbam_close.argtypes = [ctypes.c_void_p]
     lib.mdx_fasta_index.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32]

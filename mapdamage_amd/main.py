@@ -66,6 +66,17 @@ def _ranged(cls, lo=float("-inf"), hi=float("inf")):
     return parse
 
 
+def _flag_mask(value):
+    """A flag mask of the command line: decimal or 0x hex, 0..65535."""
+    try:
+        mask = int(value, 16) if value.lower().startswith("0x") else int(value, 10)
+    except ValueError:
+        raise argparse.ArgumentTypeError("must be a decimal or 0x hexadecimal number")
+    if not 0 <= mask <= 65535:
+        raise argparse.ArgumentTypeError("must lie in 0..65535")
+    return mask
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="mapDamage", usage="%(prog)s [options] -i alignment.bam -r reference.fasta")
     p.add_argument("--version", action="version", version="%(prog)s (mapdamage_amd " + __version__ + ")")
@@ -149,6 +160,23 @@ def build_parser():
                    help="with --regions / --region-groups: the usual three files hold the records inside the regions only (the sum "
                         "of the named groups, '*' left out) — what `samtools view -L BED` in front would have produced; by_region/ "
                         "is still complete")
+    g.add_argument("--min-mapq", type=_ranged(int, 0, 255), default=0, metavar="Q",
+                   help="drop the records whose MAPQ is below Q, as `samtools view -q Q` in front would (numeric: 255 passes any Q); "
+                        "evaluated by the decoders, on the device where the file is decoded there.  Not a reference option "
+                        "(mapdamage/config.py has none), like the four below.  The filters apply to every record in front of "
+                        "everything else — the flag filter 0xF04 of the reference still applies on top, --downsample draws once per "
+                        "record that is left; Runtime_log.txt and record_filters.tsv give the records dropped by each.  --rescale "
+                        "tabulates and estimates from the filtered records and still rewrites every record of the input")
+    g.add_argument("--require-flags", type=_flag_mask, default=0, metavar="F",
+                   help="drop the records that lack one of the bits of F (decimal or 0x hex, 0..65535; `samtools view -f F`), on the 16 "
+                        "bits the file carries")
+    g.add_argument("--exclude-flags", type=_flag_mask, default=0, metavar="F",
+                   help="drop the records that have one of the bits of F (`samtools view -F F`)")
+    g.add_argument("--min-read-length", type=_ranged(int, 0, 2**31 - 1), default=0, metavar="L",
+                   help="drop the records whose SEQ field is shorter than L bases (BAM's l_seq; a SAM '*' is 0) — the length of the "
+                        "stored sequence, not the query length of the CIGAR")
+    g.add_argument("--max-read-length", type=_ranged(int, 0, 2**31 - 1), default=0, metavar="L",
+                   help="drop the records whose SEQ field is longer than L bases (0: no upper bound)")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -190,6 +218,13 @@ def parse_args(argv):
             parser.error(str(error))
         if o.seq_length > o.length and not o.stats_only:
             parser.error("--seq-length must not be greater than --length: the tables hold no position beyond it")
+    from .sam import RecordFilter
+    if o.min_read_length and o.max_read_length and o.min_read_length > o.max_read_length:
+        parser.error("--min-read-length must not be greater than --max-read-length")
+    o.record_filter = RecordFilter(o.min_mapq, o.require_flags, o.exclude_flags, o.min_read_length, o.max_read_length)
+    if o.record_filter.active and (o.rescale_only or o.stats_only):
+        parser.error("--min-mapq / --require-flags / --exclude-flags / --min-read-length / --max-read-length belong to the "
+                     "tabulation pass; neither --rescale-only nor --stats-only counts records")
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -427,6 +462,18 @@ class _Ranks:
         kept = allreduce_words(kept).cpu().numpy().view(np.uint64)
         return StratifiedTables.from_block(block, engine.base_libraries, engine.groups, kept)
 
+    def sum_counts(self, counts):
+        """The record filters' counts (uint64[6]) summed over the ranks, as the kept reads per stratum are."""
+        counts = np.ascontiguousarray(counts, np.uint64)
+        if self.world == 1:
+            return counts
+        import torch
+        from .distributed import allreduce_words
+        words = torch.from_numpy(counts.view(np.int64).copy())
+        if self.backend == "nccl":
+            words = words.to(torch.device("cuda", self.device))
+        return allreduce_words(words).cpu().numpy().view(np.uint64)
+
     def close(self):
         if self.world > 1:
             import torch.distributed as dist
@@ -480,6 +527,22 @@ def _make_engine(options, libraries, device):
     return engine
 
 
+def _report_record_filters(options, counts, logger, first):
+    """The INFO line and record_filters.tsv of a run with record filters (rank 0; ``counts``: summed over the ranks)."""
+    if not first:
+        return
+    f = options.record_filter
+    n, a, b, c, d, e = (int(x) for x in counts)
+    logger.info("Record filters: %d records read; dropped: %d require-flags, %d exclude-flags, %d MAPQ < %d, %d shorter than %d, "
+                "%d longer than %d", n, a, b, c, f.min_mapq, d, f.min_length, e, f.max_length)
+    lines = ["filter\tvalue\trecords_dropped",
+             "require-flags\t0x%X\t%d" % (f.require_flags, a), "exclude-flags\t0x%X\t%d" % (f.exclude_flags, b),
+             "min-mapq\t%d\t%d" % (f.min_mapq, c), "min-read-length\t%d\t%d" % (f.min_length, d),
+             "max-read-length\t%d\t%d" % (f.max_length, e), "records-read\t\t%d" % n,
+             "records-passed\t\t%d" % (n - a - b - c - d - e)]
+    (options.folder / "record_filters.tsv").write_text("\n".join(lines) + "\n")
+
+
 def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None):
     """The records decoded on the host (native BGZF/BAM decoder or SAM text), uploaded batch by batch.
     ``carry``: (engine, resume position, records counted so far, --downsample generator or None) of a device decode that
@@ -492,7 +555,7 @@ def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None
             engine.set_reference(ref)
             n_reads, resume, rand = 0, None, None
         else:
-            engine, resume, n_reads, rand = carry
+            engine, resume, n_reads, rand = carry[:4]
             stack.enter_context(engine)
         warned_about_quals = False
         error = None
@@ -530,6 +593,12 @@ def _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry=None
                 error = exc
                 break
             n_reads += batch.n
+        # the record filters' counts: the reader's (where a host decoder took over part of the way, on top of the device
+        # path's); several ranks decode the same chunks, rank 0 speaks for all
+        counts = reader.filter_counts.copy()
+        if carry is not None and len(carry) > 4:
+            counts += carry[4]
+        options.filter_counts = counts if ranks.rank == 0 else np.zeros(6, np.uint64)
         tables = ranks.finish(engine, error)
     return tables
 
@@ -605,7 +674,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         stages.mark("warm-up joined")
         with (GpuSamStream if sam_text else GpuBamStream)(
                 engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
-                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual) as stream:
+                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual,
+                record_filter=options.record_filter) as stream:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
             slab, n_reads, n_kept = 0, 0, 0
             try:
@@ -618,6 +688,7 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                         continue
                     if sam_stream:
                         slab_start, kept_before, rand_state = stream.tell(), n_kept, downsample_rand.getstate()
+                        counts_before = stream.filter_counts()
                     try:
                         view = stream.next_view()
                     except ValueError:
@@ -636,6 +707,11 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                                 carry = (engine, where, n_reads, downsample_rand if options.downsample is not None else None)
                             elif where is not None and sam_stream:
                                 carry = (engine, where, n_kept, downsample_rand if options.downsample is not None else None)
+                            if carry is not None:
+                                # (the counts of the slabs in front.  A SAM slab that is given up has added nothing; a BAM slab
+                                # that failed behind its unpack launch — a block's CRC32 — may have added to the reasons: the
+                                # host decoder ends on that block's error, and the counts are never written)
+                                carry += (stream.filter_counts(),)
                         raise
                     if view is None:
                         break
@@ -661,7 +737,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                             engine.sync()
                         except BadReadError:
                             downsample_rand.setstate(rand_state)
-                            carry = (engine, slab_start, kept_before, downsample_rand if options.downsample is not None else None)
+                            carry = (engine, slab_start, kept_before, downsample_rand if options.downsample is not None else None,
+                                     counts_before)
                             raise
                         # (the records the host decoder would have counted: its record numbers go on from there)
                         kept = stream.view_flags(view) if options.downsample is None else flags
@@ -675,6 +752,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                 if ranks.world == 1:
                     raise
                 error = exc         # (the ranks agree on it in finish(): all of them take the host path then)
+            if error is None:
+                options.filter_counts = stream.filter_counts()
             tables = ranks.finish(engine, error)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
         engine.close()
@@ -799,6 +878,7 @@ def main(argv):
         reader = BAMReader(options.filename, merge_libraries=options.merge_libraries,
                            downsample_to=options.downsample, downsample_seed=options.downsample_seed,
                            chunk_bytes=int(options.chunk_mb * (1 << 20)), source=options.source,
+                           record_filter=options.record_filter,
                            sam_header_only=options.gpu_decode and _device_path_applies(options, ranks.world))
         reflengths = reader.get_references()
         if not is_plain_gzip(options.ref):
@@ -862,6 +942,8 @@ def main(argv):
         logger.debug("Done. %d filtered alignments processed", tables.n_kept)
         logger.debug("BAM read in %f seconds", time.time() - start_time)
 
+        if options.record_filter.active:
+            _report_record_filters(options, ranks.sum_counts(options.filter_counts), logger, first)
         stages.mark("tables")
         if not first:
             return 0

@@ -56,7 +56,7 @@ def downsample_indices(flag, tid, pos, downsample_to, rand):
 
 class BAMReader:
     def __init__(self, filepath, merge_libraries=False, downsample_to=None, downsample_seed=None,
-                 chunk_bytes=None, source=None, sam_header_only=False):
+                 chunk_bytes=None, source=None, sam_header_only=False, record_filter=None):
         """``chunk_bytes``: decode a BAM file in chunks of that many uncompressed bytes (``iter_batches``
         then yields one batch per chunk and ``handle`` holds the header only) instead of all at once.
         Downsampling to a fixed number of reads needs the whole file (reservoir + coordinate sort,
@@ -68,8 +68,14 @@ class BAMReader:
         ``sam_header_only`` (the device path, ``sam.GpuSamStream``): SAM text is not parsed here — ``handle`` holds its header
         only, read without consuming a stream — and ``iter_batches`` parses the records (all of them, or a stream from
         ``resume`` on: a byte offset, or for compressed text ``GpuSamStream.tell``'s pair) when the host has to count them
-        after all."""
+        after all.
+        ``record_filter`` (a ``sam.RecordFilter``): applied by the host decoders in front of the flag filter and the
+        downsampling — a dropped record is one the flag filter drops —, ``filter_counts`` (uint64[6]: records read, dropped by
+        each reason) summed over everything decoded here: a file read in one piece is counted when it is read, a chunk or a
+        SAM body when ``iter_batches`` decodes it."""
         log = logging.getLogger(__name__)
+        self.record_filter = record_filter if record_filter is not None and record_filter.active else None
+        self.filter_counts = np.zeros(6, np.uint64)
         self.filepath = filepath
         self.downsample_to = downsample_to
         self.downsample_seed = downsample_seed
@@ -90,7 +96,8 @@ class BAMReader:
             self._chunks = BamStream(src, chunk_bytes=chunk_bytes)
             self.handle = Alignments(self._chunks.header, self._empty_batch(), [], [])
         else:
-            self.handle: Alignments = read_alignments(src)
+            self.handle: Alignments = read_alignments(src, self.record_filter)
+            self._counted(self.handle)
         self._merge_libraries = merge_libraries
         # read group id -> (sample, library); with --merge-libraries every record, tagged or not, is ("*", "*")
         self._readgroups = {None: ("*", "*")} if merge_libraries else self._collect_readgroups(log, self.handle)
@@ -105,6 +112,20 @@ class BAMReader:
         return ReadBatch(np.zeros(0, np.uint16), np.zeros(0, np.uint16), np.zeros(0, np.int32), np.zeros(0, np.int32),
                          np.zeros(0, np.int32), np.zeros(1, np.uint32), np.zeros(0, np.uint32), np.zeros(1, np.uint32),
                          np.zeros(0, np.uint8), np.zeros(0, np.uint8))
+
+    def _filtered(self, handle):
+        """``handle`` (the native decoder's chunk) with the record filter applied and counted."""
+        if self.record_filter is not None:
+            from .sam import apply_record_filter
+            apply_record_filter(handle, self.record_filter, self.filter_counts)
+        return handle
+
+    def _counted(self, handle):
+        """``handle`` as a parser that took the filter returned it: its counts added."""
+        counts = getattr(handle, "filter_counts", None)
+        if counts is not None:
+            self.filter_counts += counts
+        return handle
 
     def get_references(self):
         return dict(zip(self.handle.header.references, self.handle.header.lengths))
@@ -146,12 +167,13 @@ class BAMReader:
                 # (zlib inflates from the told block on and drops what lies in front of the line; the header's lines, where
                 # they come by again, are skipped)
                 with compressed_text(self.source if self.source is not None else self.filepath, resume or (0, 0)) as text:
-                    handle = read_sam(text, header=self.handle.header)
+                    handle = read_sam(text, header=self.handle.header, record_filter=self.record_filter)
             elif self.source is not None and self.source.is_stream:
                 self.source.seek(self._sam_body if resume is None else resume)
-                handle = read_sam(self.source.text(), header=self.handle.header)
+                handle = read_sam(self.source.text(), header=self.handle.header, record_filter=self.record_filter)
             else:
-                handle = read_alignments(self.source if self.source is not None else self.filepath)
+                handle = read_alignments(self.source if self.source is not None else self.filepath, self.record_filter)
+            self._counted(handle)
             indices = self.kept_indices(handle, rand)
             batch = handle.batch
             if len(indices) != batch.n:
@@ -181,6 +203,7 @@ class BAMReader:
                 if chunk is None:
                     break
                 pending = pool.submit(self._chunks.next_chunk)
+                self._filtered(chunk)
                 indices = self.kept_indices(chunk, rand)
                 batch = chunk.batch
                 if len(indices) != batch.n:

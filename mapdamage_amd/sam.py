@@ -5,8 +5,11 @@ BAM (through the standard library's zlib) are supported for reading and writing;
 host-side "N1" row of SURVEY §8f in its first, pure-Python form.
 """
 
+import ctypes
+import dataclasses
 import gzip
 import io
+import re
 import struct
 import zlib
 
@@ -48,6 +51,80 @@ def usable_cpus():
 
 class BAMError(RuntimeError):
     """Read-group problems (mapdamage/reader.py:16-17)."""
+
+
+FILTER_REASONS = ("require-flags", "exclude-flags", "min-mapq", "min-read-length", "max-read-length")
+
+
+@dataclasses.dataclass(frozen=True)
+class RecordFilter:
+    """The record filters of the command line (--min-mapq, --require-flags, --exclude-flags, --min-read-length,
+    --max-read-length; include/mdx.h ``mdx_record_filter``).  A record is dropped when ``(FLAG & require_flags) !=
+    require_flags``, ``(FLAG & exclude_flags) != 0``, ``MAPQ < min_mapq`` (numeric, as ``samtools view -q``: 255 passes),
+    ``l_seq < min_length`` or — ``max_length`` not 0 — ``l_seq > max_length``; FLAG is the 16 bits of the file, ``l_seq`` the
+    length of the SEQ field (0 for a SAM ``*``), not the CIGAR's query length.  Every decoder marks a dropped record with
+    0x200 in its flag column, which the flag filter (0xF04) drops: nothing downstream knows about filters."""
+    min_mapq: int = 0
+    require_flags: int = 0
+    exclude_flags: int = 0
+    min_length: int = 0
+    max_length: int = 0
+
+    def __post_init__(self):
+        if not 0 <= self.min_mapq <= 255:
+            raise ValueError("min_mapq must lie in 0..255")
+        if not (0 <= self.require_flags <= 0xFFFF and 0 <= self.exclude_flags <= 0xFFFF):
+            raise ValueError("flag masks must lie in 0..65535")
+        if self.min_length < 0 or self.max_length < 0 or self.min_length >= 1 << 31 or self.max_length >= 1 << 31:
+            raise ValueError("read lengths must lie in 0..2^31-1")
+        if self.max_length and self.min_length > self.max_length:
+            raise ValueError("min_length is greater than max_length")
+
+    @property
+    def active(self):
+        return bool(self.min_mapq or self.require_flags or self.exclude_flags or self.min_length or self.max_length)
+
+    def drops(self, flag, mapq, l_seq):
+        """The reason index (``FILTER_REASONS``) of each record that leaves — the first in the order require, exclude, MAPQ,
+        shortest, longest — or -1, over numpy arrays of the file's FLAG (16 bits), MAPQ and SEQ length."""
+        flag = np.asarray(flag).astype(np.int64) & 0xFFFF
+        mapq = np.asarray(mapq).astype(np.int64)
+        l_seq = np.asarray(l_seq).astype(np.int64)
+        out = np.full(flag.shape, -1, np.int64)
+        tests = ((flag & self.require_flags) != self.require_flags, (flag & self.exclude_flags) != 0, mapq < self.min_mapq,
+                 l_seq < self.min_length, (l_seq > self.max_length) if self.max_length else np.zeros(flag.shape, bool))
+        for reason in range(4, -1, -1):
+            out[tests[reason]] = reason
+        return out
+
+    def as_struct(self):
+        """The ctypes mirror of ``mdx_record_filter``."""
+        return MdxRecordFilter(self.min_mapq, self.require_flags, self.exclude_flags, self.min_length, self.max_length)
+
+    @staticmethod
+    def counts_of(why):
+        """(records, dropped by each reason) of the reason indices ``drops`` returned, as the decoders count: uint64[6]."""
+        return np.concatenate([[why.shape[0]], np.bincount(why[why >= 0], minlength=5)]).astype(np.uint64)
+
+    def counts(self, flag, mapq, l_seq):
+        return self.counts_of(self.drops(flag, mapq, l_seq))
+
+
+class MdxRecordFilter(ctypes.Structure):
+    _fields_ = [("min_mapq", ctypes.c_int32), ("require_flags", ctypes.c_uint32), ("exclude_flags", ctypes.c_uint32),
+                ("min_length", ctypes.c_int32), ("max_length", ctypes.c_int32)]
+
+
+_MAPQ = re.compile(r"-?[0-9]+", re.ASCII)
+
+
+def _mark_dropped(al, record_filter, flags16, mapqs):
+    """The Python parsers' share of ``RecordFilter``: 0x200 into the flag column, and ``al.filter_counts``."""
+    lens = np.diff(al.batch.seq_off.astype(np.int64))
+    why = record_filter.drops(flags16, mapqs, lens)
+    al.batch.flag[why >= 0] |= 0x200
+    al.filter_counts = record_filter.counts_of(why)
+    return al
 
 
 class Header:
@@ -121,9 +198,11 @@ def _finish(header, flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs
     return Alignments(header, batch, rgs, qnames)
 
 
-def read_sam(path_or_handle, header=None):
+def read_sam(path_or_handle, header=None, record_filter=None):
     """SAM text -> ``Alignments``.  ``header``: a ``Header`` read already (a host parser that takes a stream up behind the
-    device decoder, ``GpuSamStream.tell``): every line is then a record line, and a line that starts with '@' is skipped."""
+    device decoder, ``GpuSamStream.tell``): every line is then a record line, and a line that starts with '@' is skipped.
+    ``record_filter`` (a ``RecordFilter``): the records it drops get 0x200 in the flag column, ``filter_counts`` on the
+    result; MAPQ is read only under a MAPQ threshold, and one that is not ``-?[0-9]+`` is then a ``BAMError``."""
     handle = open(path_or_handle, "rt") if isinstance(path_or_handle, (str, bytes)) or hasattr(path_or_handle, "__fspath__") else path_or_handle
     head, lines = [], []
     for line in handle:
@@ -132,11 +211,22 @@ def read_sam(path_or_handle, header=None):
         header = Header("".join(head))
     tid_of = {name: i for i, name in enumerate(header.references)}
     flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs, qnames = [], [], [], [], [], [], [], [], [], []
+    filtering = record_filter is not None and record_filter.active
+    want_mapq = filtering and record_filter.min_mapq > 0
+    flags16, mapqs = [], []
     for line in lines:
         f = line.rstrip("\n").split("\t")
         if len(f) < 11:
             continue
         qnames.append(f[0])
+        if filtering:
+            flags16.append(int(f[1]))
+            if want_mapq:
+                # (-?[0-9]+, compared as a number whatever its size; anything else — int() would take "+5", " 7", "1_0" — is a
+                # line htslib, behind the reference's pysam, refuses)
+                if not _MAPQ.fullmatch(f[4]):
+                    raise BAMError("Read %r: MAPQ %r is not a number" % (f[0], f[4]))
+                mapqs.append(int(f[4]))
         flags.append(int(f[1]) & 0x3FFF)       # bits 14 and 15 are the kernels' hint bits (mdx.h MDX_FLAG_HAS_QUAL / _QUAL_ABOVE_MIN), never the file's
         tids.append(tid_of.get(f[2], -1))
         poss.append(int(f[3]) - 1)
@@ -164,10 +254,13 @@ def read_sam(path_or_handle, header=None):
             if tag.startswith("RG:Z:"):
                 rg = tag[5:]
         rgs.append(rg)
-    return _finish(header, flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs, qnames)
+    al = _finish(header, flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs, qnames)
+    if filtering:
+        _mark_dropped(al, record_filter, flags16, mapqs if want_mapq else np.zeros(len(flags16), np.int64))
+    return al
 
 
-def read_bam(path, keep_raw=False):
+def read_bam(path, keep_raw=False, record_filter=None):
     with gzip.open(path, "rb") as handle:   # BGZF is a series of gzip members
         data = handle.read()
     if data[:4] != b"BAM\x01":
@@ -189,13 +282,16 @@ def read_bam(path, keep_raw=False):
         header.references, header.lengths = names, lengths
     flags, tids, poss, tlens, cigs, cig_counts, seqs, quals, rgs, qnames = [], [], [], [], [], [], [], [], [], []
     mtids, mposs, raws, has_mr = [], [], [], []
+    flags16, mapqs = [], []
     raw_header = data[:off]
     n = len(data)
     while off + 4 <= n:
         block_size, = struct.unpack_from("<i", data, off)
         rec = memoryview(data)[off + 4:off + 4 + block_size]
         off += 4 + block_size
-        tid, pos, l_read_name, _mapq, _bin, n_cigar, flag, l_seq, ntid, npos, tlen = struct.unpack_from("<iiBBHHHiiii", rec, 0)
+        tid, pos, l_read_name, mapq, _bin, n_cigar, flag, l_seq, ntid, npos, tlen = struct.unpack_from("<iiBBHHHiiii", rec, 0)
+        flags16.append(flag)
+        mapqs.append(mapq)
         mtids.append(ntid)
         mposs.append(npos)
         if keep_raw:
@@ -254,7 +350,25 @@ def read_bam(path, keep_raw=False):
     al.has_mr = has_mr
     if keep_raw:
         al.raw, al.raw_header = raws, raw_header
+    if record_filter is not None and record_filter.active:
+        _mark_dropped(al, record_filter, flags16, mapqs)
     return al
+
+
+def apply_record_filter(al, record_filter, counts=None):
+    """``RecordFilter`` over the ``Alignments`` of the native host decoder (include/mdx.h ``mdx_bam_apply_record_filter``): 0x200
+    into the flag column of the records it drops; ``counts`` (uint64[6]) += records, dropped by each reason."""
+    import ctypes
+
+    from .engine import load_library
+    if counts is None:
+        counts = np.zeros(6, np.uint64)
+    flt = record_filter.as_struct() if record_filter is not None else None
+    rc = load_library().mdx_bam_apply_record_filter(al.native, ctypes.byref(flt) if flt is not None else None,
+                                                    ctypes.c_void_p(counts.ctypes.data))
+    if rc != 0:
+        raise ValueError("mdx_bam_apply_record_filter failed (%d)" % rc)
+    return counts
 
 
 def write_bam_raw(path, raw_header, records):
@@ -414,6 +528,7 @@ def _native_alignments(lib, handle, owner, header=None):
     al._qblob = col(blob_ptr, int(al._qoff[-1]), np.uint8) if n else np.zeros(0, np.uint8)
     al.has_mr = col(hmr.value, n, np.uint8).view(bool)
     al.qmin = col(lib.mdx_bam_qmin(handle), n, np.uint8)     # lowest quality of each record
+    al.native, al._native_owner = handle, owner              # (apply_record_filter, patch_rescaled)
     return al
 
 
@@ -450,7 +565,7 @@ class GpuBamStream:
     decodes on the host (``BamStream``), from ``tell()`` on if it likes.  ``path``: a file's, or a ``Source``."""
 
     def __init__(self, engine, path, readgroups=(), lib_default=None, chunk_bytes=256 << 20, want_qual=False,
-                 want_mate=False, min_basequal=0, packed=None):
+                 want_mate=False, min_basequal=0, packed=None, record_filter=None):
         import ctypes
         self._lib = engine._lib
         self._engine = engine
@@ -493,6 +608,18 @@ class GpuBamStream:
         self.packed = bool(packed)
         if self.packed:
             self._lib.mdx_gbam_set_seq_format(self._g, 1)
+        if record_filter is not None and record_filter.active:
+            flt = record_filter.as_struct()
+            if self._lib.mdx_gbam_set_record_filter(self._g, ctypes.byref(flt)) != 0:
+                raise ValueError("%r: %s" % (str(path), self._error()))
+
+    def filter_counts(self):
+        """uint64[6]: the records decoded so far, and those among them the record filter dropped, by reason."""
+        import ctypes
+        out = np.zeros(6, np.uint64)
+        if self._lib.mdx_gbam_filter_counts(self._g, ctypes.c_void_p(out.ctypes.data)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        return out
 
     def missing_qualities(self):
         """A record the kernel counts has come by without qualities (main.py:185-192 warns once)."""
@@ -628,7 +755,7 @@ class GpuSamStream:
     file's, or a ``Source``."""
 
     def __init__(self, engine, path, readgroups=(), lib_default=None, chunk_bytes=256 << 20, want_qual=False,
-                 min_basequal=0, packed=None):
+                 min_basequal=0, packed=None, record_filter=None):
         import ctypes
         self._lib = engine._lib
         self._engine = engine
@@ -670,6 +797,18 @@ class GpuSamStream:
         self.packed = bool(packed)
         if self.packed:
             lib.mdx_gsam_set_seq_format(self._g, 1)
+        if record_filter is not None and record_filter.active:
+            flt = record_filter.as_struct()
+            if lib.mdx_gsam_set_record_filter(self._g, ctypes.byref(flt)) != 0:
+                raise ValueError("%r: %s" % (str(path), self._error()))
+
+    def filter_counts(self):
+        """uint64[6]: the records parsed so far (of slabs handed out), and those the record filter dropped, by reason."""
+        import ctypes
+        out = np.zeros(6, np.uint64)
+        if self._lib.mdx_gsam_filter_counts(self._g, ctypes.c_void_p(out.ctypes.data)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        return out
 
     def _error(self):
         return self._lib.mdx_gsam_error(self._g).decode(errors="replace") if self._g else "GPU SAM decode failed"
@@ -1190,23 +1329,27 @@ def compressed_text(path, resume=(0, 0)):
     return io.TextIOWrapper(io.BufferedReader(raw, 1 << 20))
 
 
-def read_alignments(path):
+def read_alignments(path, record_filter=None):
     """SAM or BAM by content (mapdamage/reader.py:38 lets htslib sniff the format, through compression too).  BAM goes through
     the native decoder of libmdx.so; the pure-Python ``read_bam`` remains as its cross-check.  Compressed SAM text — BGZF or
     plain gzip, any number of members — is inflated by zlib on the way into ``read_sam``.  ``path``: a file's, or a
-    ``Source`` (stdin and pipes: SAM text is read through it, the sniffed bytes included)."""
+    ``Source`` (stdin and pipes: SAM text is read through it, the sniffed bytes included).  ``record_filter``: a
+    ``RecordFilter`` — the result then has its dropped records marked and carries ``filter_counts``."""
     if not isinstance(path, Source) and str(path) == "-":
         import sys
-        return read_sam(sys.stdin)
+        return read_sam(sys.stdin, record_filter=record_filter)
     kind = input_format(path)
     if kind == BAM:
-        return read_bam_native(path)
+        al = read_bam_native(path)
+        if record_filter is not None and record_filter.active:
+            al.filter_counts = apply_record_filter(al, record_filter)
+        return al
     if kind != SAM_TEXT:
         with compressed_text(path) as handle:
-            return read_sam(handle)
+            return read_sam(handle, record_filter=record_filter)
     if isinstance(path, Source):
-        return read_sam(path.text())
-    return read_sam(str(path))
+        return read_sam(path.text(), record_filter=record_filter)
+    return read_sam(str(path), record_filter=record_filter)
 
 
 def header_text(ref_names, ref_lengths, read_groups):
@@ -1221,8 +1364,9 @@ def _cigar_string(ops):
     return "".join("%d%s" % (int(c) >> 4, L.CIGAR_CHARS[int(c) & 15]) for c in ops) or "*"
 
 
-def write_sam(path, batch: ReadBatch, ref_names, ref_lengths, read_groups, rg_of_record=None):
-    """``read_groups``: list of dicts (ID, SM, LB ...); ``rg_of_record``: RG id per record or None."""
+def write_sam(path, batch: ReadBatch, ref_names, ref_lengths, read_groups, rg_of_record=None, mapq=None):
+    """``read_groups``: list of dicts (ID, SM, LB ...); ``rg_of_record``: RG id per record or None; ``mapq``: MAPQ per record
+    (30 everywhere without)."""
     with open(path, "wt") as out:
         out.write(header_text(ref_names, ref_lengths, read_groups))
         for i in range(batch.n):
@@ -1234,7 +1378,7 @@ def write_sam(path, batch: ReadBatch, ref_names, ref_lengths, read_groups, rg_of
                 qual = (batch.qual[s0:s1] + 33).astype(np.uint8).tobytes().decode()
             tid = int(batch.tid[i])
             fields = ["r%d" % i, str(int(batch.flag[i])), ref_names[tid] if tid >= 0 else "*",
-                      str(int(batch.pos[i]) + 1), "30", _cigar_string(batch.cigar[c0:c1]), "*", "0",
+                      str(int(batch.pos[i]) + 1), "30" if mapq is None else str(int(mapq[i])), _cigar_string(batch.cigar[c0:c1]), "*", "0",
                       str(int(batch.tlen[i])), seq, qual]
             rg = None if rg_of_record is None else rg_of_record[i]
             if rg is not None:
@@ -1248,13 +1392,15 @@ _WB_JOB = None
 def _wb_slice(span):
     """Worker of write_bam(workers=N): records [lo, hi) of batch k as finished BGZF blocks, each starting at a record."""
     k, lo, hi = span
-    batches, rg_of_record = _WB_JOB
+    batches, rg_of_record, mapq = _WB_JOB
     batch = batches[k]
+    mapq = None if mapq is None else mapq[k]                          # (per batch: write_bam has seen to it)
     out = io.BytesIO()
     room = 0xFF00
     piece = bytearray()
     for i in range(lo, hi):
-        record = _bam_record(batch, i, rg_of_record if rg_of_record is None or isinstance(rg_of_record, str) else rg_of_record[i])
+        record = _bam_record(batch, i, rg_of_record if rg_of_record is None or isinstance(rg_of_record, str) else rg_of_record[i],
+                             mapq=None if mapq is None else (mapq if np.isscalar(mapq) else mapq[i]))
         if piece and len(piece) + len(record) > room:
             out.write(_bgzf_block(bytes(piece)))
             piece = bytearray()
@@ -1267,7 +1413,7 @@ def _wb_slice(span):
     return out.getvalue()
 
 
-def _bam_record(batch, i, rg):
+def _bam_record(batch, i, rg, mapq=None):
     c0, c1 = int(batch.cigar_off[i]), int(batch.cigar_off[i + 1])
     s0, s1 = int(batch.seq_off[i]), int(batch.seq_off[i + 1])
     name = ("r%d" % i).encode() + b"\x00"
@@ -1280,14 +1426,14 @@ def _bam_record(batch, i, rg):
     aux = b"" if rg is None else b"RGZ" + rg.encode() + b"\x00"
     ntid = -1 if batch.mtid is None else int(batch.mtid[i])
     npos = -1 if batch.mpos is None else int(batch.mpos[i])
-    body = struct.pack("<iiBBHHHiiii", int(batch.tid[i]), int(batch.pos[i]), len(name), 30, 4680,
+    body = struct.pack("<iiBBHHHiiii", int(batch.tid[i]), int(batch.pos[i]), len(name), 30 if mapq is None else int(mapq), 4680,
                        c1 - c0, int(batch.flag[i]), l_seq, ntid, npos, int(batch.tlen[i]))
     body += name + batch.cigar[c0:c1].astype("<u4").tobytes() + packed + qual + aux
     return struct.pack("<i", len(body)) + body
 
 
 def write_bam(path, batch, ref_names, ref_lengths, read_groups, rg_of_record=None, htslib_blocks=True,
-              workers=1, block_bytes=0xFF00):
+              workers=1, block_bytes=0xFF00, mapq=None):
     """``htslib_blocks``: lay the BGZF blocks out as htslib does (the header flushed on its own, and a block closed
     early when the next record would not fit, ``bgzf_flush_try`` in ``bam_write1``), so that every block starts
     at a record — what the files mapDamage sees in practice look like, and what the native decoder's parallel
@@ -1296,9 +1442,22 @@ def write_bam(path, batch, ref_names, ref_lengths, read_groups, rg_of_record=Non
     ``workers`` > 1 (htslib layout only): the records are encoded and deflated by forked worker processes, a slice
     each (call it before the process touches the GPU); a slice starts a block of its own, otherwise the same file.
     With workers, ``batch`` may be a list of batches (written one behind the other: a file of more than 4 G bases) and
-    ``rg_of_record`` one read-group id for every record."""
+    ``rg_of_record`` one read-group id for every record.  ``mapq``: one MAPQ for every record, or — ``batch`` a single batch — one per record,
+    or — ``batch`` a list of batches, of whatever length — a list of one array (or value) per batch; 30 everywhere without."""
     text = header_text(ref_names, ref_lengths, read_groups).encode()
     batches = list(batch) if isinstance(batch, (list, tuple)) else [batch]
+    # MAPQ per batch from here on: one value, or an array per record
+    if mapq is not None:
+        if np.isscalar(mapq):
+            mapq = [mapq] * len(batches)
+        elif isinstance(batch, (list, tuple)):
+            mapq = list(mapq)
+            if len(mapq) != len(batches) or any(not np.isscalar(m) and len(m) != b.n for m, b in zip(mapq, batches)):
+                raise ValueError("with a list of batches, mapq is a list of one array (or value) per batch")
+        else:
+            if len(mapq) != batches[0].n:
+                raise ValueError("mapq holds one value per record")
+            mapq = [mapq]
     if htslib_blocks and workers > 1 and sum(b.n for b in batches) > 4 * workers:
         import multiprocessing as mp
         global _WB_JOB
@@ -1310,7 +1469,7 @@ def write_bam(path, batch, ref_names, ref_lengths, read_groups, rg_of_record=Non
         hv = head.getvalue()
         n_jobs = workers * 4
         spans = [(k, b.n * j // n_jobs, b.n * (j + 1) // n_jobs) for k, b in enumerate(batches) for j in range(n_jobs)]
-        _WB_JOB = (batches, rg_of_record)
+        _WB_JOB = (batches, rg_of_record, mapq)
         try:
             with mp.get_context("fork").Pool(workers) as pool, open(path, "wb") as out:
                 for lo in range(0, len(hv), 0xFF00):
@@ -1324,6 +1483,7 @@ def write_bam(path, batch, ref_names, ref_lengths, read_groups, rg_of_record=Non
     if len(batches) != 1:
         raise ValueError("several batches are written by forked workers only (workers > 1, htslib layout)")
     batch = batches[0]
+    mapq = None if mapq is None else mapq[0]
     if isinstance(rg_of_record, str):
         rg_of_record = [rg_of_record] * batch.n
     raw = io.BytesIO()
@@ -1337,7 +1497,8 @@ def write_bam(path, batch, ref_names, ref_lengths, read_groups, rg_of_record=Non
         head = raw.getvalue()
         pieces = [bytearray(head[lo:lo + room]) for lo in range(0, len(head), room)] + [bytearray()]
     for i in range(batch.n):
-        record = _bam_record(batch, i, None if rg_of_record is None else rg_of_record[i])
+        record = _bam_record(batch, i, None if rg_of_record is None else rg_of_record[i],
+                             mapq=None if mapq is None else (mapq if np.isscalar(mapq) else mapq[i]))
         if not htslib_blocks:
             raw.write(record)
             continue

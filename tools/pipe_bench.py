@@ -8,7 +8,13 @@
 and the stage timings of T_run (MDX_STAGE_LOG, as bench.py's cli_wall splits a run).  The aim: T_run <= max(T_pipe, T_file)
 plus the run's fixed costs.  The tables of T_run must be byte-identical to those of T_file.  One JSON line on stdout.
 
-    python tools/pipe_bench.py [--reads N] [--dir DIR] [--timeout S]"""
+--min-mapq Q: the file is written with MAPQ drawn from {0, 1, 24, 25, 29, 30, 37, 60, 255} (30 everywhere without), and the
+command on the file is timed with and without `--min-mapq Q`, behind T_file (which has warmed the file's pages), in the order
+plain, filtered, filtered, plain, ... (--repeats pairs), wall clock and the "decode and tabulate" stage of MDX_STAGE_LOG each:
+`filter_runs`.  The filtered run tabulates fewer records (a third of that MAPQ set lies below 25), so what it can show is that
+the filter adds no time, not what it costs per record.
+
+    python tools/pipe_bench.py [--reads N] [--dir DIR] [--timeout S] [--min-mapq Q]"""
 import argparse
 import json
 import os
@@ -47,6 +53,8 @@ def main():
     ap.add_argument("--reads", type=int, default=50_000_000)
     ap.add_argument("--dir", help="where the BAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed step may take")
+    ap.add_argument("--min-mapq", type=int, default=0, help="write varied MAPQ and time the file run with this --min-mapq as well")
+    ap.add_argument("--repeats", type=int, default=3, help="pairs of runs with and without --min-mapq")
     args = ap.parse_args()
     from mapdamage_amd import fasta, sam, synth
     work = args.dir or tempfile.mkdtemp(prefix="mdx_pipe_bench_")
@@ -59,8 +67,13 @@ def main():
         cap = 25_000_000
         batches = [synth.parallel_batch("config3_batch", ref, min(cap, args.reads - lo), seed=3000 + k, workers=16)
                    for k, lo in enumerate(range(0, args.reads, cap))]
+        mapq = None
+        if args.min_mapq:
+            import numpy as np
+            rng = np.random.default_rng(2525)
+            mapq = [rng.choice(np.array([0, 1, 24, 25, 29, 30, 37, 60, 255], np.uint8), b.n) for b in batches]
         sam.write_bam(bam, batches, ref.names, ref.lengths, [{"ID": "rg1", "SM": "synthetic", "LB": "lib1"}], rg_of_record="rg1",
-                      workers=16)
+                      workers=16, mapq=mapq)
         fasta.write_fasta(fa, ref)
         del batches
         write_s = time.perf_counter() - t0
@@ -80,6 +93,27 @@ def main():
             result["error"] = "T_file: exit %d %s" % (rc, err)
             print(json.dumps(result))
             return 1
+        if args.min_mapq:
+            result["min_mapq"] = args.min_mapq
+            runs = {"plain": [], "filtered": []}
+            order = [("plain", "filtered") if k % 2 == 0 else ("filtered", "plain") for k in range(args.repeats)]
+            for k, which in enumerate(w for pair in order for w in pair):
+                out_k = os.path.join(work, "%s_%d" % (which, k))
+                log_k = os.path.join(work, "stages_%d.json" % k)
+                extra = " --min-mapq %d" % args.min_mapq if which == "filtered" else ""
+                t_spawn = time.time()
+                t_k, rc, err = timed(cli + out_k + extra + " -i " + bam, args.timeout, env=dict(os.environ, MDX_STAGE_LOG=log_k))
+                if rc != 0:
+                    result["error"] = "%s run %d: exit %d %s" % (which, k, rc, err)
+                    print(json.dumps(result))
+                    return 1
+                st = stages(log_k, t_spawn, t_k) or {}
+                log = open(os.path.join(out_k, "Runtime_log.txt")).read()
+                runs[which].append({"wall_s": round(t_k, 3), "decode_and_tabulate_s": st.get("decode and tabulate"),
+                                    "device": "Decode path: device; fallbacks from the device path: 0" in log})
+                if which == "filtered":
+                    result["record_filters_tsv"] = open(os.path.join(out_k, "record_filters.tsv")).read()
+            result["filter_runs"] = runs
         stage_log = os.path.join(work, "stages.json")
         env = dict(os.environ, MDX_STAGE_LOG=stage_log)
         t_spawn = time.time()
