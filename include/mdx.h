@@ -291,6 +291,22 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
  *                      mdx_set_strata.  A context has tid strata or region strata: calling the other kind is
  *                      MDX_ERR_STATE.  The arrays are copied to the device and stay there for the context's life.  The
  *                      flag filter is unchanged: a record it drops gets a key and is not counted in mdx_strata_kept.
+ *   mdx_set_strata_damage  the group from what the record itself shows, for the conditional substitution analysis that tells
+ *                      endogenous molecules from modern contamination (is damage at one end of a molecule associated with
+ *                      damage at its other end?): four groups, 0 none, 1 5p, 2 3p, 3 both.  A record is 5p-damaged if
+ *                      MisincorporationRates.update(read, seq, refseq, "5p", library) (statistics.py:22-35, as called from
+ *                      main.py:185-212) would add to C>T at an index below `positions`, 3p-damaged if the "3p" call would add
+ *                      to G>A there — C>T with single_stranded != 0.  Everything that shapes those calls shapes the rule:
+ *                      terminal soft clips are no part of the query, hard clips are ignored, the gap columns of insertions
+ *                      and deletions are positions, a reverse-strand record is reverse-complemented first, an N operation
+ *                      misaligns the columns behind it as align.py:76-88 does, under --min-basequal a column below the
+ *                      threshold is N / N (a record without qualities is not masked), and only the exact symbols match.  The
+ *                      key kernel reads the record's CIGAR, a few SEQ symbols per end (all three forms of `seq`; qual or lowq
+ *                      only where a column shows the substitution) and the resident reference: mdx_set_reference must have
+ *                      been called before the first tabulation and before mdx_batch_upload (MDX_ERR_STATE).  A tid outside
+ *                      the reference or a window beyond its sequence: group none, reported by the tabulation if kept.
+ *                      cfg.nlib no multiple of 4, positions outside [1, cfg.length]: MDX_ERR_ARG.  State rules, the flag
+ *                      filter, the fused calls and "one kind per context" as above.
  *   mdx_strata_groups  n_groups, 0 for a context without strata
  *   mdx_strata_kept    kept[cfg.nlib] (host): the records the flag filter (reader.py:121-132) kept, per stratum, of this
  *                      context's batches since mdx_create / mdx_reset — the block's n_kept is one word for the whole run.
@@ -311,6 +327,7 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
 int mdx_set_strata(mdx_ctx *ctx, int32_t n_groups, const int32_t *group_of_tid, int32_t n_contig);
 int mdx_set_strata_regions(mdx_ctx *ctx, int32_t n_groups, int32_t n_contig, const int64_t *iv_off /* n_contig+1 */,
                            const int32_t *iv_start, const int32_t *iv_end, const int32_t *iv_group, int32_t rest_group);
+int mdx_set_strata_damage(mdx_ctx *ctx, int32_t positions, int32_t single_stranded);
 int mdx_strata_groups(const mdx_ctx *ctx);
 int mdx_strata_kept(mdx_ctx *ctx, uint64_t *kept);
 int64_t mdx_merged_words(const mdx_ctx *ctx);

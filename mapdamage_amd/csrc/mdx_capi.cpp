@@ -162,6 +162,9 @@ struct mdx_ctx {
     // context's life — [iv_off n_contig + 1][iv_start][iv_end][iv_group]
     void *d_regions = nullptr;
     MdxRegions regions = {};
+    // ... or (mdx_set_strata_damage) from the record's own terminal substitutions: none, 5p, 3p, both
+    int damage_positions = 0;      // > 0: damage strata, the terminal columns looked at
+    int damage_single_stranded = 0;
     DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -551,14 +554,31 @@ static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, i
     for (uint64_t v : {(uint64_t)n, (uint64_t)n_cigar, (uint64_t)n_bases, (uint64_t)nlib | (uint64_t)n_groups << 32}) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; }
     return h | 1ull;
 }
-// A stratified context (mdx_set_strata, mdx_set_strata_regions): *out = the device batch b with the key column — library x
-// groups + group of the record's sequence, or of the first region it overlaps — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
+// A stratified context (mdx_set_strata, mdx_set_strata_regions, mdx_set_strata_damage): *out = the device batch b with the key column — library x
+// groups + group of the record's sequence, of the first region it overlaps, or of the damage its ends show — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
 // stream; valid until the next such call).  count: the kept records are added to the context's counts per stratum.
 static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool count) {
     *out = *b;
     if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
     HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
-    if (c->d_regions)
+    if (c->damage_positions > 0) {
+        // (the key reads the batch as the caller brings it — under --min-basequal the mask from the nibbles of a MDX_SEQ_4BITQ
+        // column, else from the qualities or the caller's bitmap of them, as the launch's own fold would take it)
+        if (!c->d_ref) return fail(c, MDX_ERR_STATE, "damage strata (mdx_set_strata_damage) read the reference: mdx_set_reference has not been called");
+        MdxDamageKey k{};
+        k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
+        k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos;
+        k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off; k.seq = b->seq;
+        k.seq_packed = b->seq_format != MDX_SEQ_ASCII; k.seq_folded = b->seq_format == MDX_SEQ_4BITQ;
+        k.minqual = c->cfg.minqual;
+        k.qual = c->cfg.minqual > 0 ? b->qual : nullptr;
+        k.lowq = c->cfg.minqual > 0 && b->qual && b->seq_format == MDX_SEQ_4BIT ? b->lowq : nullptr;
+        k.ref = c->d_ref + 256;   // (kRefPad)
+        k.contig_off = c->d_contig_off; k.n_contig = c->n_contig;
+        k.n_libraries = c->cfg.nlib / c->n_groups;
+        k.positions = c->damage_positions; k.single_stranded = c->damage_single_stranded;
+        mdx_k_strata_damage_key(k, (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
+    } else if (c->d_regions)
         mdx_k_strata_region_key(b->n_reads, b->flag, b->lib, b->tid, b->pos, b->cigar_off, b->cigar, b->n_cigar, c->regions, c->n_groups,
                                 c->cfg.nlib / c->n_groups, (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
     else
@@ -587,6 +607,9 @@ int mdx_batch_upload(mdx_ctx *c, const mdx_batch *h, mdx_batch *dv) {
     int rc = check_batch(c, h);
     if (rc != MDX_OK) return rc;
     if (!dv) return MDX_ERR_ARG;
+    // (damage strata: the resident batch is bucketed by a key that reads the reference)
+    if (c->damage_positions > 0 && !c->d_ref)
+        return fail(c, MDX_ERR_STATE, "mdx_batch_upload: a context with mdx_set_strata_damage buckets the batch by a key that reads the reference; call mdx_set_reference first");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     std::memset(dv, 0, sizeof(*dv));
     dv->n_reads = h->n_reads; dv->n_cigar = h->n_cigar; dv->n_bases = h->n_bases;
@@ -710,7 +733,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     mdx_batch b_key;
     if (c->n_groups > 0) {
         if (fuse) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
-        if (c->strata_n_contig != c->n_contig)
+        if (c->damage_positions == 0 && c->strata_n_contig != c->n_contig)
             return fail(c, MDX_ERR_ARG, std::string(c->d_regions ? "mdx_set_strata_regions" : "mdx_set_strata") + " named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
                                         std::to_string(c->n_contig));
         if (!(ml && b_in->libsort)) {
@@ -1261,6 +1284,7 @@ int mdx_set_strata(mdx_ctx *c, int32_t n_groups, const int32_t *group_of_tid, in
             return fail(c, MDX_ERR_ARG, "set_strata: the group of sequence " + std::to_string(t) + " is outside [0, n_groups)");
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata: records have been counted already (mdx_reset first)");
     if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata: the context has region strata (mdx_set_strata_regions); a context has one kind");
+    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata: the context has damage strata (mdx_set_strata_damage); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_group_of_tid) { (void)hipFree(c->d_group_of_tid); c->d_group_of_tid = nullptr; }
@@ -1302,6 +1326,7 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
         }
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_regions: records have been counted already (mdx_reset first)");
     if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has tid strata (mdx_set_strata); a context has one kind");
+    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has damage strata (mdx_set_strata_damage); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_regions) { (void)hipFree(c->d_regions); c->d_regions = nullptr; }
@@ -1325,6 +1350,28 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
     }
     c->n_groups = n_groups;
     c->strata_n_contig = n_contig;
+    return MDX_OK;
+}
+
+int mdx_set_strata_damage(mdx_ctx *c, int32_t positions, int32_t single_stranded) {
+    if (!c) return MDX_ERR_ARG;
+    if (c->cfg.nlib % 4 != 0)
+        return fail(c, MDX_ERR_ARG, "set_strata_damage: the context's " + std::to_string(c->cfg.nlib) +
+                                    " tables are no multiple of the 4 groups none, 5p, 3p, both (create it with nlib = libraries x 4)");
+    if (positions < 1 || positions > c->cfg.length)
+        return fail(c, MDX_ERR_ARG, "set_strata_damage: " + std::to_string(positions) + " terminal positions are outside [1, length = " +
+                                    std::to_string(c->cfg.length) + "]");
+    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_damage: records have been counted already (mdx_reset first)");
+    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has tid strata (mdx_set_strata); a context has one kind");
+    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has region strata (mdx_set_strata_regions); a context has one kind");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (!c->d_strata_kept) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
+        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
+    }
+    c->n_groups = 4;
+    c->damage_positions = positions;
+    c->damage_single_stranded = single_stranded ? 1 : 0;
     return MDX_OK;
 }
 

@@ -397,6 +397,13 @@ struct MdxRegions {
 void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *pos,
                              const uint32_t *cigar_off, const uint32_t *cigar, int64_t n_cigar, const MdxRegions &r, int n_groups,
                              int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
+// damage strata (mdx_set_strata_damage): four groups from the record's own alignment against the resident reference —
+// none, 5p, 3p, both: an end is damaged if MisincorporationRates.update (statistics.py:22-35) would add to C>T (5p) or G>A
+// (3p; C>T with single_stranded) at an index below `positions`.  The batch in any of its three SEQ forms; qual / lowq are
+// read under a minqual for the forms that do not carry the mask; a tid or a window outside the reference is group none.
+// (MdxDamageKey and the rule itself: mdx_damage_key.h)
+#include "mdx_damage_key.h"
+void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long long *kept, hipStream_t s);
 void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
 // a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
 // n_libraries tables, the groups of each library summed

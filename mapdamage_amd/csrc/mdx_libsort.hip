@@ -497,6 +497,42 @@ void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *li
                        r.n_contig, n_groups, n_libraries, key, (u64 *)kept);
 }
 
+// The same with the group taken from what the record SHOWS (mdx_set_strata_damage): none, 5p, 3p or both, by the
+// substitutions at its own ends — the rule and its walk are mdx_damage_group (mdx_damage_key.h), one lane per record.  On top
+// of the tid key's 10 bytes: pos, two CIGAR offsets and the words, two SEQ offsets, and per end a line of SEQ and a line of
+// the reference (class per base, MdxTabArgs::ref); a quality byte only where a column shows the substitution.
+__global__ __launch_bounds__(256) void strata_damage_key_kernel(MdxDamageKey a, u16 *__restrict__ key, u64 *__restrict__ kept) {
+    __shared__ u32 h[LS_LDS_LIBS];
+    const int n_strata = a.n_libraries * 4;
+    const bool in_lds = n_strata <= LS_LDS_LIBS;
+    if (in_lds) {
+        for (int l = threadIdx.x; l < n_strata; l += 256) h[l] = 0u;
+        __syncthreads();
+    }
+    const i64 lo = (i64)blockIdx.x * STRATA_KEY_PER, hi = lo + STRATA_KEY_PER < a.n ? lo + STRATA_KEY_PER : a.n;
+    for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
+        const u32 lb = a.lib[i], fl = a.flag[i];
+        u32 k = 0xFFFFu;
+        if (lb < (u32)a.n_libraries) k = lb * 4u + mdx_damage_group(a, i, fl);
+        key[i] = (u16)k;
+        if (kept && k != 0xFFFFu && !(fl & 0xF04u)) {
+            if (in_lds) atomicAdd(&h[k], 1u);
+            else atomicAdd(&kept[k], 1ull);
+        }
+    }
+    if (in_lds && kept) {
+        __syncthreads();
+        for (int l = threadIdx.x; l < n_strata; l += 256)
+            if (h[l]) atomicAdd(&kept[l], (u64)h[l]);
+    }
+}
+
+void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long long *kept, hipStream_t s) {
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL(strata_damage_key_kernel, dim3((unsigned)((a.n + STRATA_KEY_PER - 1) / STRATA_KEY_PER)), dim3(256), 0, s, a, key,
+                       (u64 *)kept);
+}
+
 // ... and for a batch that brings its columns bucketed by stratum (mdx_batch::libsort): the sizes of the buckets
 __global__ void strata_kept_from_sort_kernel(const u32 *__restrict__ lib_start, int n_strata, u64 *__restrict__ kept) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;

@@ -47,7 +47,7 @@ EXPORTS = (
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
     "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
-    "mdx_set_strata", "mdx_set_strata_regions", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
+    "mdx_set_strata", "mdx_set_strata_regions", "mdx_set_strata_damage", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
     "mdx_stats_loglik", "mdx_stats_run", "mdx_stats_pmat",
     "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
     "mdx_gsam_filter_counts",
@@ -192,6 +192,7 @@ def load_library(path=None):
     lib.mdx_set_strata.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]
     lib.mdx_set_strata_regions.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_set_strata_damage.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
     lib.mdx_strata_groups.argtypes = [ctypes.c_void_p]
     lib.mdx_strata_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_merged_words.restype = ctypes.c_int64
@@ -268,7 +269,8 @@ class DamageEngine:
 
     ``groups``: names of groups of reference sequences — the engine then keeps one table set per (library, group), a
     *stratum* (include/mdx.h ``mdx_set_strata``): ``set_strata(group_of_tid)`` says which group each sequence of the
-    header belongs to (or ``set_strata_regions(...)`` which group each region of a BED file does), the batches keep naming
+    header belongs to (or ``set_strata_regions(...)`` which group each region of a BED file does, or ``set_strata_damage(...)``
+    that the groups are ``DAMAGE_GROUPS``, told by the substitutions at the record's own ends), the batches keep naming
     the library in their ``lib`` column, and ``finish()`` returns a ``tables.StratifiedTables``.  ``libraries`` then holds one entry per stratum, library-major (``base_libraries`` the
     caller's list)."""
 
@@ -366,6 +368,18 @@ class DamageEngine:
         rest = len(self.groups) - 1 if rest_group is None else int(rest_group)
         self._check(self._lib.mdx_set_strata_regions(self._ctx, ctypes.c_int32(len(self.groups)), ctypes.c_int32(off.shape[0] - 1),
                                                      _ptr(off), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ctypes.c_int32(rest)))
+        self._strata_set = True
+
+    DAMAGE_GROUPS = ["none", "5p", "3p", "both"]
+
+    def set_strata_damage(self, positions=1, single_stranded=False):
+        """The group of a record from the damage its own ends show (include/mdx.h ``mdx_set_strata_damage``): 5p-damaged if
+        the reference's 5p update would add to C>T within the first ``positions`` positions, 3p-damaged if its 3p update
+        would add to G>A there (``single_stranded``: C>T).  The engine's ``groups`` must be ``DAMAGE_GROUPS``.  Before the
+        first ``tabulate``; the key reads the reference, so ``set_reference`` comes before ``upload``."""
+        if self.groups != self.DAMAGE_GROUPS:
+            raise ValueError("set_strata_damage: the engine must be made with groups=%r" % (self.DAMAGE_GROUPS,))
+        self._check(self._lib.mdx_set_strata_damage(self._ctx, ctypes.c_int32(int(positions)), ctypes.c_int32(1 if single_stranded else 0)))
         self._strata_set = True
 
     def strata_kept(self):

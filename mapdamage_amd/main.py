@@ -10,6 +10,7 @@ import logging
 import sys
 import time
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -109,7 +110,8 @@ def build_parser():
                    help="estimate the damage parameters once the tables are written (mapdamage/r/stats/ on the GPU, one chain per "
                         "table set in one launch): Stats_out_MCMC_iter.csv, ..._iter_summ_stat.csv and ..._correct_prob.csv; needs "
                         "one of --fix-nicks, --use-raw-nick-freq and --single-stranded.  With --by-reference / --reference-groups / "
-                        "--regions / --region-groups every group gets a chain of its own and its three files beside its tables")
+                        "--regions / --region-groups / --by-terminal-damage every group gets a chain of its own and its three files "
+                        "beside its tables")
     g.add_argument("--stats-seed", type=int, default=0, metavar="N",
                    help="seed of the estimate's random numbers (Philox4x32-10; a chain is reproducible from it)")
     g.add_argument("--stats-chain", type=int, default=0, help=argparse.SUPPRESS)     # key word of the run's own chain (group g: g + 1)
@@ -160,6 +162,18 @@ def build_parser():
                    help="with --regions / --region-groups: the usual three files hold the records inside the regions only (the sum "
                         "of the named groups, '*' left out) — what `samtools view -L BED` in front would have produced; by_region/ "
                         "is still complete")
+    g.add_argument("--by-terminal-damage", action="store_true",
+                   help="also tabulate the records apart by the damage their own ends show, in the same pass: a record is "
+                        "5p-damaged if it adds to C>T within the first --terminal-positions positions of the 5p table, 3p-damaged "
+                        "if it adds to G>A within those of the 3p table (C>T with --single-stranded), by every rule the tables "
+                        "follow (clips, gaps, strand, --min-basequal); the usual three files are what the run writes without the "
+                        "option, and by_damage/ holds groups.tsv, the three files of the groups none, 5p, 3p and both in "
+                        "directories named by their index, and conditional.tsv: the substitution frequency at one end given the "
+                        "other end's state, which tells a damaged library from a contaminated one.  Not a reference option: "
+                        "mapdamage/config.py has none")
+    g.add_argument("--terminal-positions", type=_ranged(int, 1), default=None, metavar="K",
+                   help="with --by-terminal-damage: the positions from either end that decide a record's group (default 1, at "
+                        "most --length).  Not a reference option either")
     g.add_argument("--min-mapq", type=_ranged(int, 0, 255), default=0, metavar="Q",
                    help="drop the records whose MAPQ is below Q, as `samtools view -q Q` in front would (numeric: 255 passes any Q); "
                         "evaluated by the decoders, on the device where the file is decoded there.  Not a reference option "
@@ -245,6 +259,17 @@ def parse_args(argv):
         parser.error("--regions / --region-groups belong to the tabulation pass; --rescale-only counts nothing")
     if o.only_regions and not (o.regions or o.region_groups):
         parser.error("--only-regions needs --regions or --region-groups")
+    if o.by_terminal_damage and (o.by_reference or o.reference_groups or o.regions or o.region_groups):
+        parser.error("--by-terminal-damage and --by-reference / --reference-groups / --regions / --region-groups exclude each "
+                     "other: a run has one kind of groups")
+    if o.by_terminal_damage and o.rescale_only:
+        parser.error("--by-terminal-damage belongs to the tabulation pass; --rescale-only counts nothing")
+    if o.terminal_positions is not None and not o.by_terminal_damage:
+        parser.error("--terminal-positions needs --by-terminal-damage")
+    if o.by_terminal_damage:
+        o.terminal_positions = 1 if o.terminal_positions is None else o.terminal_positions
+        if o.terminal_positions > o.length:
+            parser.error("--terminal-positions must not be greater than --length: the tables hold no position beyond it")
     if o.rescale_only and not o.folder:
         parser.error("--folder required when using --rescale-only")
     if not o.filename:
@@ -372,13 +397,13 @@ def _group_has_data(folder):
 
 def bayesian_estimates(options, logger, ref=None, n_contig=0, device=0):
     """The estimate of the folder's tables and of every group directory beside them (by_reference/<index>,
-    by_region/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
+    by_region/<index>, by_damage/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
     from .stats import StatsError, estimate_folders
     start = time.time()
     try:
         acgt = _base_frequencies(options, ref, n_contig, device)
         folders, chains = [options.folder], [options.stats_chain]
-        for sub in ("by_reference", "by_region"):
+        for sub in ("by_reference", "by_region", "by_damage"):
             if not (options.folder / sub / "groups.tsv").is_file():
                 continue
             index = 0
@@ -493,10 +518,19 @@ def launch_command(argv, gpus):
             "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "mapdamage_amd"] + keep
 
 
+class TerminalDamage(NamedTuple):
+    """What --by-terminal-damage hands to ``DamageEngine.set_strata_damage``."""
+    positions: int
+    single_stranded: bool
+
+
 def reference_strata(options, references, lengths=None):
     """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, (group names,
-    tables.Regions) of --regions / --region-groups (``lengths``: the sequences' lengths), or None."""
+    tables.Regions) of --regions / --region-groups (``lengths``: the sequences' lengths), (group names, TerminalDamage) of
+    --by-terminal-damage, or None."""
     from .tables import Regions, groups_by_reference, parse_reference_groups, parse_regions
+    if getattr(options, "by_terminal_damage", False):
+        return list(DamageEngine.DAMAGE_GROUPS), TerminalDamage(options.terminal_positions, bool(options.single_stranded))
     if options.by_reference:
         return groups_by_reference(references)
     if options.reference_groups:
@@ -509,15 +543,17 @@ def reference_strata(options, references, lengths=None):
 
 
 def _make_engine(options, libraries, device):
-    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups one table set per (library,
-    group) — the input routes hand it the same batches either way."""
+    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups / --by-terminal-damage one
+    table set per (library, group) — the input routes hand it the same batches either way."""
     from .tables import Regions
     strata = getattr(options, "strata", None)
     engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=device,
                           groups=None if strata is None else strata[0])
     if strata is not None:
         try:
-            if isinstance(strata[1], Regions):
+            if isinstance(strata[1], TerminalDamage):
+                engine.set_strata_damage(strata[1].positions, strata[1].single_stranded)
+            elif isinstance(strata[1], Regions):
                 engine.set_strata_regions(strata[1].iv_off, strata[1].iv_start, strata[1].iv_end, strata[1].iv_group)
             else:
                 engine.set_strata(strata[1])
@@ -907,7 +943,7 @@ def main(argv):
             logger.error("%s", error)
             return 1
         if options.strata is not None:
-            kind = "regions" if options.regions or options.region_groups else "reference sequences"
+            kind = "terminal damage" if options.by_terminal_damage else "regions" if options.regions or options.region_groups else "reference sequences"
             logger.info("Tabulating %d groups of %s x %d libraries in one pass", len(options.strata[0]), kind, len(libraries))
             if len(options.strata[0]) * len(libraries) > DamageEngine.MAX_TABLES:
                 logger.error("%d groups of %s x %d libraries: more than the %d tables a run can keep",
@@ -949,7 +985,11 @@ def main(argv):
             return 0
         if options.strata is not None:
             # the three usual files from the sum over the groups, and by_reference/ beside them
-            if options.regions or options.region_groups:
+            if options.by_terminal_damage:
+                tables.write(options.folder, subdir="by_damage", groups_text=tables.damage_groups_text())
+                (options.folder / "by_damage" / "conditional.tsv").write_text(tables.conditional_text(options.strata[1].single_stranded))
+                tables = tables.merged
+            elif options.regions or options.region_groups:
                 from .tables import region_groups_text
                 r, ng = options.strata[1], len(options.strata[0])
                 text = region_groups_text(options.strata[0], r.iv_start, r.iv_end, r.iv_group, r.lengths,

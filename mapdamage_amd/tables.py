@@ -354,6 +354,40 @@ class StratifiedTables:
             out.write("%d\t%s\t%d\t%d\n" % (g, name, int(n_seq[g]), self.group_kept(g)))
         return out.getvalue()
 
+    def damage_groups_text(self):
+        """``by_damage/groups.tsv``: index, group name, kept reads."""
+        out = io.StringIO()
+        out.write("Index\tGroup\tReads\n")
+        for g, name in enumerate(self.groups):
+            out.write("%d\t%s\t%d\n" % (g, name, self.group_kept(g)))
+        return out.getvalue()
+
+    def conditional_text(self, single_stranded=False):
+        """``by_damage/conditional.tsv`` of a run stratified by terminal damage (groups ``none, 5p, 3p, both``): the
+        substitution frequency at one end given the damage state of the OTHER end — the conditional substitution analysis
+        that tells a damaged library from a contaminated one (a row conditioned on its own end would be 1 by construction
+        within the positions the groups were told by).  Per library (the emitters' order), end (5p, then 3p), condition
+        (``all``, other end damaged, other end undamaged) and position 1..length, strands summed: 5p rows C>T over C; 3p
+        rows G>A over G (``single_stranded``: C>T over C).  ``Frequency`` as ``damage_frequency_text`` writes it."""
+        if self.groups != ["none", "5p", "3p", "both"]:
+            raise ValueError("conditional_text: the groups are not those of terminal damage")
+        mis = self._split(self.strata.mis)                  # [library][group][end][strand][pos][col]
+        rows = (("5p", "C>T", "C", (("all", (0, 1, 2, 3)), ("3p-damaged", (2, 3)), ("3p-undamaged", (0, 1)))),
+                ("3p",) + (("C>T", "C") if single_stranded else ("G>A", "G")) +
+                ((("all", (0, 1, 2, 3)), ("5p-damaged", (1, 3)), ("5p-undamaged", (0, 2))),))
+        out = io.StringIO()
+        out.write("Sample\tLibrary\tEnd\tPos\tGiven\tSubstitutions\tBases\tFrequency\n")
+        for (sample, library), li in sorted((tuple(lib), i) for i, lib in enumerate(self.libraries)):
+            for end, num_col, den_col, conditions in rows:
+                ei = L.ENDS.index(end)
+                for given, groups in conditions:
+                    block = mis[li, list(groups), ei].sum(axis=(0, 1), dtype=np.uint64)         # [pos][col]
+                    for p in range(self.strata.length):
+                        num, den = int(block[p, L.MIS_COLS.index(num_col)]), int(block[p, L.MIS_COLS.index(den_col)])
+                        out.write("%s\t%s\t%s\t%d\t%s\t%d\t%d\t%s\n"
+                                  % (sample, library, end, p + 1, given, num, den, "%.15g" % (num / den) if den else "NaN"))
+        return out.getvalue()
+
     def write(self, folder, group_of_tid=None, subdir="by_reference", groups_text=None, usual=None):
         """The run's three files into ``folder`` from the merged block (``usual``: from that ``TableSet`` instead), and
         ``folder/subdir``: ``groups.tsv`` (``groups_text``; default: that of the sequence groups ``group_of_tid``) and one
