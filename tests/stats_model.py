@@ -62,11 +62,13 @@ def pmat(tmu, rho, acgt, jukes_cantor=False):
 
 
 def dnbinom(x, size, prob):
+    """R's dnbinom as seqProbVecLambda calls it (function.r:76).  prob == 1 and size == 0 are the point mass at 0; prob == 0
+    (Lambda = 0, which the updates let through) puts no mass on any count, so the overhang stays at 1/2 in every row."""
     x = np.asarray(x, float)
     if prob == 1.0 or size == 0.0:
         return (x == 0).astype(float)
-    with np.errstate(divide="ignore"):
-        return np.exp(_lgamma(x + size) - math.lgamma(size) - _lgamma(x + 1.0) + size * math.log(prob) + x * math.log1p(-prob))
+    log_prob = math.log(prob) if prob > 0.0 else -math.inf                  # (math.log raises at 0)
+    return np.exp(_lgamma(x + size) - math.lgamma(size) - _lgamma(x + 1.0) + size * log_prob + x * math.log1p(-prob))
 
 
 def seq_prob_vec(lam, disp, m, termini="both"):

@@ -12,7 +12,7 @@ GOLDEN = pathlib.Path(__file__).resolve().parent / "golden"
 
 
 # fixtures of other kinds in the same folder (no count tables: the reference's downsampling draws, the hand-assembled BAM's truth)
-_NOT_TABLES = {"downsample", "foreign_bam"}
+_NOT_TABLES = {"downsample", "foreign_bam", "stats_loglik_exact"}
 
 
 def golden_names():
