@@ -307,6 +307,35 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
  *                      the reference or a window beyond its sequence: group none, reported by the tabulation if kept.
  *                      cfg.nlib no multiple of 4, positions outside [1, cfg.length]: MDX_ERR_ARG.  State rules, the flag
  *                      filter, the fused calls and "one kind per context" as above.
+ *   mdx_set_strata_pmd  the group from the record's post-mortem damage score (PMDS; Skoglund et al. 2014, PNAS 111:2229): the
+ *                      log-likelihood ratio, over the whole alignment and with the base qualities, that the read carries
+ *                      deamination damage.  n_thresholds + 1 groups: a record's group is the number of thresholds its score
+ *                      reaches.  The rule, per record in its TRUE alignment (an N operation does not shift the columns behind
+ *                      it): the query is SEQ without its terminal soft clips, nq bases q = 0 .. nq - 1; z5 = q + 1 and
+ *                      z3 = nq - q for a forward record, the other way round for a reverse one; only the columns of M = X add
+ *                      terms — in the molecule's orientation (a reverse record complemented) a 5p term at z5 where the
+ *                      reference holds C and the read C (match) or T (mismatch), a 3p term at z3 where the reference holds G
+ *                      and the read G or A (single_stranded: C and C or T again: a C column then adds both); exact symbols only.
+ *                      terms[mismatch][min(z, 256) - 1][quality column] is the caller's table of the terms, 2^24 to the unit
+ *                      (mapdamage_amd/pmd.py term_table builds it from D_z = p (1-p)^(z-1) + C and eps_q = 10^(-q/10) / 3);
+ *                      the quality column is min(quality, 93), or 94 (eps = 0) for a record without qualities (no qual
+ *                      column, or 0xFF as the record's first quality).  The score is the int64 sum of the record's terms —
+ *                      exact, whatever the order —, thresholds_fx the thresholds in the same unit (ceil(t 2^24)), strictly
+ *                      increasing, 1 to 15 of them.  A tid outside the reference, a pos < 0 or a window beyond its sequence:
+ *                      score 0, nothing read, reported by the tabulation if kept.  The key kernel reads every aligned base
+ *                      (ASCII and MDX_SEQ_4BIT forms of `seq`), its quality and its reference base — some 250 bytes per
+ *                      record, a group of 16 lanes per record: mdx_set_reference comes before the first tabulation and before
+ *                      mdx_batch_upload (MDX_ERR_STATE), and a batch brings its qual column if the qualities are to count.
+ *                      cfg.nlib no multiple of n_thresholds + 1, thresholds not increasing or not 1 to 15, a null pointer, or
+ *                      a context with cfg.minqual > 0 (the decoders fold the mask into SEQ and may drop the quality column:
+ *                      the score together with --min-basequal is not defined here): MDX_ERR_ARG.  State rules, the flag
+ *                      filter, the fused calls and "one kind per context" as above.  The arrays are copied.
+ *   mdx_strata_pmd_histogram  hist[cfg.nlib / n_groups][82] (host): the kept records of each library by their score, bin
+ *                      clamp((S >> 23) + 41, 0, 81) — half units over [-20, 20), bin 0 what lies below, bin 81 what lies at
+ *                      or above 20 — of this context's batches since mdx_create / mdx_reset.  Counted by the kernel that makes
+ *                      the key (a resident batch that brings its buckets: by a launch of it for the histogram alone), so a
+ *                      library's bins sum to its strata's mdx_strata_kept; synchronous.  MDX_ERR_STATE without PMD strata.
+ *   mdx_strata_pmd_unqualified  *n (host): how many of those records were scored without qualities (eps = 0); synchronous.
  *   mdx_strata_groups  n_groups, 0 for a context without strata
  *   mdx_strata_kept    kept[cfg.nlib] (host): the records the flag filter (reader.py:121-132) kept, per stratum, of this
  *                      context's batches since mdx_create / mdx_reset — the block's n_kept is one word for the whole run.
@@ -328,6 +357,10 @@ int mdx_set_strata(mdx_ctx *ctx, int32_t n_groups, const int32_t *group_of_tid, 
 int mdx_set_strata_regions(mdx_ctx *ctx, int32_t n_groups, int32_t n_contig, const int64_t *iv_off /* n_contig+1 */,
                            const int32_t *iv_start, const int32_t *iv_end, const int32_t *iv_group, int32_t rest_group);
 int mdx_set_strata_damage(mdx_ctx *ctx, int32_t positions, int32_t single_stranded);
+int mdx_set_strata_pmd(mdx_ctx *ctx, int32_t n_thresholds, const int64_t *thresholds_fx, const int32_t *terms /* [2][256][95] */,
+                       int32_t single_stranded);
+int mdx_strata_pmd_histogram(mdx_ctx *ctx, uint64_t *hist /* n_libraries x 82 */);
+int mdx_strata_pmd_unqualified(mdx_ctx *ctx, uint64_t *n);
 int mdx_strata_groups(const mdx_ctx *ctx);
 int mdx_strata_kept(mdx_ctx *ctx, uint64_t *kept);
 int64_t mdx_merged_words(const mdx_ctx *ctx);

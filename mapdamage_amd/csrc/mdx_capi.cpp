@@ -165,6 +165,12 @@ struct mdx_ctx {
     // ... or (mdx_set_strata_damage) from the record's own terminal substitutions: none, 5p, 3p, both
     int damage_positions = 0;      // > 0: damage strata, the terminal columns looked at
     int damage_single_stranded = 0;
+    // ... or (mdx_set_strata_pmd) from the record's post-mortem damage score: the number of thresholds it reaches
+    int pmd_n_thresholds = 0;      // > 0: PMD strata
+    int pmd_single_stranded = 0;
+    int64_t pmd_thresholds[MDX_PMD_MAX_THRESHOLDS] = {};
+    int32_t *d_pmd_terms = nullptr;            // [2][MDX_PMD_Z][MDX_PMD_QCOLS]
+    unsigned long long *d_pmd_hist = nullptr;  // [libraries][MDX_PMD_BINS] and one word: the kept records scored without qualities
     DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -216,12 +222,15 @@ int64_t lgd_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * c->cfg.l
 int64_t mis_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * c->cfg.length * MDX_N_MIS_COLS; }
 int64_t comp_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * (c->cfg.length + c->cfg.around) * 4; }
 
+size_t pmd_hist_words(const mdx_ctx *c) { return (size_t)(c->cfg.nlib / (c->pmd_n_thresholds + 1)) * MDX_PMD_BINS + 1; }
+
 int zero_accumulators(mdx_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(c->d_raw, 0, (size_t)c->dims.w_total * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_lgd_dense, 0, (size_t)lgd_words(c) * 8 * c->lgd_copies, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_n_lgd_over, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, 8, c->stream));
     if (c->d_strata_kept) HIP_TRY(c, hipMemsetAsync(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8, c->stream));
+    if (c->d_pmd_hist) HIP_TRY(c, hipMemsetAsync(c->d_pmd_hist, 0, pmd_hist_words(c) * 8, c->stream));
     return MDX_OK;
 }
 
@@ -391,7 +400,7 @@ void mdx_destroy(mdx_ctx *c) {
         if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
     }
     void *ptrs[] = {c->d_ref, c->d_ref4, c->d_contig_off, c->d_raw, c->d_lgd_dense, c->d_lgd_over,
-                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_regions, c->d_strata_kept};
+                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_regions, c->d_strata_kept, c->d_pmd_terms, c->d_pmd_hist};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -557,11 +566,38 @@ static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, i
 // A stratified context (mdx_set_strata, mdx_set_strata_regions, mdx_set_strata_damage): *out = the device batch b with the key column — library x
 // groups + group of the record's sequence, of the first region it overlaps, or of the damage its ends show — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
 // stream; valid until the next such call).  count: the kept records are added to the context's counts per stratum.
+// The PMD key (mdx_set_strata_pmd) of the device batch b into `key` (null: none is written), its kept records counted per
+// stratum (count) and into the score histogram (hist).
+// (MDX_PMD_LANE=1 in the environment: the trivial kernel, a lane per record; MDX_PMD_NO_LDS=1: the cooperative kernel with every
+// term read from global memory — for A/B runs, read at every call)
+static int pmd_key(mdx_ctx *c, const mdx_batch *b, uint16_t *key, bool count, bool hist) {
+    if (!c->d_ref) return fail(c, MDX_ERR_STATE, "PMD strata (mdx_set_strata_pmd) read the reference: mdx_set_reference has not been called");
+    const char *e = getenv("MDX_PMD_LANE"), *e2 = getenv("MDX_PMD_NO_LDS");
+    const int form = e && *e && *e != '0' ? 1 : e2 && *e2 && *e2 != '0' ? 2 : 0;
+    MdxPmdKey k{};
+    k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
+    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos;
+    k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off; k.seq = b->seq; k.qual = b->qual;
+    k.seq_packed = b->seq_format != MDX_SEQ_ASCII;
+    k.ref = c->d_ref + 256;   // (kRefPad)
+    k.contig_off = c->d_contig_off; k.n_contig = c->n_contig;
+    k.n_libraries = c->cfg.nlib / c->n_groups;
+    k.n_thresholds = c->pmd_n_thresholds; k.single_stranded = c->pmd_single_stranded;
+    k.terms = c->d_pmd_terms;
+    for (int t = 0; t < c->pmd_n_thresholds; t++) k.thresholds[t] = c->pmd_thresholds[t];
+    mdx_k_strata_pmd_key(k, key, count ? c->d_strata_kept : nullptr, hist ? c->d_pmd_hist : nullptr, form, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return MDX_OK;
+}
+
 static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool count) {
     *out = *b;
     if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
     HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
-    if (c->damage_positions > 0) {
+    if (c->pmd_n_thresholds > 0) {
+        const int rc = pmd_key(c, b, (uint16_t *)c->strata_key.p, count, count);
+        if (rc != MDX_OK) return rc;
+    } else if (c->damage_positions > 0) {
         // (the key reads the batch as the caller brings it — under --min-basequal the mask from the nibbles of a MDX_SEQ_4BITQ
         // column, else from the qualities or the caller's bitmap of them, as the launch's own fold would take it)
         if (!c->d_ref) return fail(c, MDX_ERR_STATE, "damage strata (mdx_set_strata_damage) read the reference: mdx_set_reference has not been called");
@@ -607,7 +643,9 @@ int mdx_batch_upload(mdx_ctx *c, const mdx_batch *h, mdx_batch *dv) {
     int rc = check_batch(c, h);
     if (rc != MDX_OK) return rc;
     if (!dv) return MDX_ERR_ARG;
-    // (damage strata: the resident batch is bucketed by a key that reads the reference)
+    // (PMD strata, damage strata: the resident batch is bucketed by a key that reads the reference)
+    if (c->pmd_n_thresholds > 0 && !c->d_ref)
+        return fail(c, MDX_ERR_STATE, "mdx_batch_upload: a context with mdx_set_strata_pmd buckets the batch by a key that reads the reference; call mdx_set_reference first");
     if (c->damage_positions > 0 && !c->d_ref)
         return fail(c, MDX_ERR_STATE, "mdx_batch_upload: a context with mdx_set_strata_damage buckets the batch by a key that reads the reference; call mdx_set_reference first");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -733,13 +771,18 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     mdx_batch b_key;
     if (c->n_groups > 0) {
         if (fuse) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
-        if (c->damage_positions == 0 && c->strata_n_contig != c->n_contig)
+        if (c->damage_positions == 0 && c->pmd_n_thresholds == 0 && c->strata_n_contig != c->n_contig)
             return fail(c, MDX_ERR_ARG, std::string(c->d_regions ? "mdx_set_strata_regions" : "mdx_set_strata") + " named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
                                         std::to_string(c->n_contig));
         if (!(ml && b_in->libsort)) {
             rc = strata_view(c, b_in, &b_key, true);
             if (rc != MDX_OK) return rc;
             b_in = &b_key;
+        } else if (c->pmd_n_thresholds > 0) {
+            // (a batch that brings its buckets is not keyed again — their sizes are the kept counts —, but its scores are not
+            // in the histogram yet: the key kernel over the batch's own columns, for the histogram alone)
+            rc = pmd_key(c, b_in, nullptr, false, true);
+            if (rc != MDX_OK) return rc;
         }
     }
     c->counted = true;
@@ -1285,6 +1328,7 @@ int mdx_set_strata(mdx_ctx *c, int32_t n_groups, const int32_t *group_of_tid, in
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata: records have been counted already (mdx_reset first)");
     if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata: the context has region strata (mdx_set_strata_regions); a context has one kind");
     if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata: the context has damage strata (mdx_set_strata_damage); a context has one kind");
+    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_group_of_tid) { (void)hipFree(c->d_group_of_tid); c->d_group_of_tid = nullptr; }
@@ -1327,6 +1371,7 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_regions: records have been counted already (mdx_reset first)");
     if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has tid strata (mdx_set_strata); a context has one kind");
     if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has damage strata (mdx_set_strata_damage); a context has one kind");
+    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_regions) { (void)hipFree(c->d_regions); c->d_regions = nullptr; }
@@ -1364,6 +1409,7 @@ int mdx_set_strata_damage(mdx_ctx *c, int32_t positions, int32_t single_stranded
     if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_damage: records have been counted already (mdx_reset first)");
     if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has tid strata (mdx_set_strata); a context has one kind");
     if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has region strata (mdx_set_strata_regions); a context has one kind");
+    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     if (!c->d_strata_kept) {
         HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
@@ -1372,6 +1418,62 @@ int mdx_set_strata_damage(mdx_ctx *c, int32_t positions, int32_t single_stranded
     c->n_groups = 4;
     c->damage_positions = positions;
     c->damage_single_stranded = single_stranded ? 1 : 0;
+    return MDX_OK;
+}
+
+int mdx_set_strata_pmd(mdx_ctx *c, int32_t n_thresholds, const int64_t *thresholds_fx, const int32_t *terms, int32_t single_stranded) {
+    if (!c) return MDX_ERR_ARG;
+    if (n_thresholds < 1 || n_thresholds > MDX_PMD_MAX_THRESHOLDS)
+        return fail(c, MDX_ERR_ARG, "set_strata_pmd: " + std::to_string(n_thresholds) + " thresholds are outside [1, " + std::to_string(MDX_PMD_MAX_THRESHOLDS) + "]");
+    if (!thresholds_fx || !terms) return fail(c, MDX_ERR_ARG, "set_strata_pmd: null thresholds or terms");
+    for (int t = 1; t < n_thresholds; t++)
+        if (thresholds_fx[t] <= thresholds_fx[t - 1])
+            return fail(c, MDX_ERR_ARG, "set_strata_pmd: threshold " + std::to_string(t) + " is not above the one before it (strictly increasing)");
+    if (c->cfg.nlib % (n_thresholds + 1) != 0)
+        return fail(c, MDX_ERR_ARG, "set_strata_pmd: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of the " +
+                                    std::to_string(n_thresholds + 1) + " groups of " + std::to_string(n_thresholds) + " thresholds (create it with nlib = libraries x groups)");
+    if (c->cfg.minqual > 0)
+        return fail(c, MDX_ERR_ARG, "set_strata_pmd: the context has a --min-basequal (cfg.minqual " + std::to_string(c->cfg.minqual) +
+                                    "): the decoders fold its mask into SEQ and may drop the quality column the score reads");
+    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_pmd: records have been counted already (mdx_reset first)");
+    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has tid strata (mdx_set_strata); a context has one kind");
+    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has region strata (mdx_set_strata_regions); a context has one kind");
+    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has damage strata (mdx_set_strata_damage); a context has one kind");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!c->d_strata_kept) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
+        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
+    }
+    const size_t term_bytes = (size_t)2 * MDX_PMD_Z * MDX_PMD_QCOLS * 4;
+    if (!c->d_pmd_terms) HIP_TRY(c, hipMalloc((void **)&c->d_pmd_terms, term_bytes));
+    HIP_TRY(c, hipMemcpy(c->d_pmd_terms, terms, term_bytes, hipMemcpyHostToDevice));
+    // (the histogram's size follows the groups: a second call with another number of thresholds gets another one)
+    if (c->d_pmd_hist) { (void)hipFree(c->d_pmd_hist); c->d_pmd_hist = nullptr; }
+    c->n_groups = n_thresholds + 1;
+    c->pmd_n_thresholds = n_thresholds;
+    c->pmd_single_stranded = single_stranded ? 1 : 0;
+    for (int t = 0; t < n_thresholds; t++) c->pmd_thresholds[t] = thresholds_fx[t];
+    HIP_TRY(c, hipMalloc((void **)&c->d_pmd_hist, pmd_hist_words(c) * 8));
+    HIP_TRY(c, hipMemset(c->d_pmd_hist, 0, pmd_hist_words(c) * 8));
+    return MDX_OK;
+}
+
+int mdx_strata_pmd_histogram(mdx_ctx *c, uint64_t *hist) {
+    if (!c || !hist) return MDX_ERR_ARG;
+    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_histogram: the context has no PMD strata (mdx_set_strata_pmd)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(hist, c->d_pmd_hist, (pmd_hist_words(c) - 1) * 8, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_strata_pmd_unqualified(mdx_ctx *c, uint64_t *n) {
+    if (!c || !n) return MDX_ERR_ARG;
+    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_unqualified: the context has no PMD strata (mdx_set_strata_pmd)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(n, c->d_pmd_hist + (pmd_hist_words(c) - 1), 8, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 

@@ -404,6 +404,14 @@ void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *li
 // (MdxDamageKey and the rule itself: mdx_damage_key.h)
 #include "mdx_damage_key.h"
 void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long long *kept, hipStream_t s);
+// PMD strata (mdx_set_strata_pmd): the group from the record's post-mortem damage score, summed in fixed point over its whole
+// alignment against the resident reference, with its qualities (MdxPmdKey and the rule itself: mdx_pmd_key.h).  The batch
+// with an ASCII or MDX_SEQ_4BIT column.  kept [libraries x groups] and hist [libraries x MDX_PMD_BINS + 1] may be null, and so
+// may key (a launch for the histogram alone).  form: 0 the cooperative kernel with part of the term table in the LDS; for
+// measurements 1 the trivial kernel, a lane per record, and 2 the cooperative one with every term from global memory.
+#include "mdx_pmd_key.h"
+void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, unsigned long long *kept, unsigned long long *hist, int form,
+                          hipStream_t s);
 void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
 // a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
 // n_libraries tables, the groups of each library summed

@@ -533,6 +533,140 @@ void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long
                        (u64 *)kept);
 }
 
+// The same with the group taken from the record's post-mortem damage score (mdx_set_strata_pmd): the number of thresholds
+// the score reaches — the rule is mdx_pmd_key.h.  Unlike the keys above this one reads the whole alignment: every aligned
+// base, its quality and its reference base, some 250 bytes per record, and two table words per C or G column.  So a record
+// is not one lane's: PMD_GROUP = 16 lanes share it, four records per wavefront.  Every lane of the group opens the record
+// (the same addresses: one request) and walks its operations; a run of M = X columns is cut into pieces of four columns and
+// lane l takes the pieces l, l + 16, ... (mdx_pmd_walk4): four reference bytes, four qualities and four read symbols in one
+// load each, all three issued before any is looked at, so that a step of the group reads 64 consecutive bytes of QUAL and of
+// the reference and 32 of a 4-bit SEQ, and a 100-base read is two steps; the partial sums meet in a butterfly over the
+// group.  16 lanes of four columns because reads are 35 to 150 bases, most of them one run: a 35-base read is one step with
+// nine lanes busy, a 150-base read three steps; 64 lanes of one column would keep 27 % of them busy on the former, and
+// a lane per record (the trivial form below) walks its columns one load chain after the other.  The sums are integers, so the mapping does not show in the result.  A CIGAR of more than PMD_COOP_OPS
+// operations is walked by the group's first lane alone: its runs are short, and sixteen lanes stepping over the same
+// operations would mostly find no column of their own.  The term table is 190 KB, and a step's lanes each want a word of a
+// row of their own (their distance) at a column of their own (their quality): read from global memory every such load is
+// 64 cache lines.  The block therefore keeps the words most loads ask for in the LDS — the match terms of the first
+// PMD_LDS_Z distances at the qualities below PMD_LDS_Q, 24 KB, 2 % of what the block's records stream — and reads the
+// rest (mismatches, long reads' middles, qualities of 48 and more, records without qualities) from global memory.
+// kept: counted per stratum as the keys above do; hist: every kept record into the bin of its score, per library
+// ([n_libraries][MDX_PMD_BINS], and one word behind them: the kept records scored without qualities) — in the LDS up to
+// PMD_HIST_LDS words, one atomic per non-empty bin and block; beyond, straight into global memory.  key may be null (a
+// launch for the histogram alone: a resident batch that brings its buckets is not keyed again).
+#define PMD_GROUP 16
+#define PMD_COOP_OPS 8
+#define PMD_HIST_LDS 4096
+#define PMD_LDS_Z 128             // the terms of a match at the first PMD_LDS_Z distances and for the qualities below
+#define PMD_LDS_Q 48              // PMD_LDS_Q, kept in the LDS by the cooperative kernel: 24 KB
+
+// the terms, those of PmdLdsTerms::lds from the LDS (most of what a file asks for: a mismatch is rare, reads are short)
+struct PmdLdsTerms {
+    const int32_t *g, *lds;
+    __device__ __forceinline__ int32_t operator()(u32 mism, u32 z1, u32 qc) const {
+        if (mism == 0u && z1 < (u32)PMD_LDS_Z && qc < (u32)PMD_LDS_Q) return lds[z1 * PMD_LDS_Q + qc];
+        return g[(mism * MDX_PMD_Z + z1) * MDX_PMD_QCOLS + qc];
+    }
+};
+
+struct PmdCounts {
+    u32 *h, *hh;
+    bool in_lds, hist_lds;
+};
+
+__device__ __forceinline__ void pmd_count(const MdxPmdKey &a, i64 i, u32 lb, u32 fl, i64 s, const PmdCounts &pc, u16 *__restrict__ key,
+                                          u64 *__restrict__ kept, u64 *__restrict__ hist) {
+    u32 k = 0xFFFFu;
+    if (lb < (u32)a.n_libraries) k = lb * (u32)(a.n_thresholds + 1) + mdx_pmd_group(a, s);
+    if (key) key[i] = (u16)k;
+    if (k == 0xFFFFu || (fl & 0xF04u)) return;
+    if (kept) {
+        if (pc.in_lds) atomicAdd(&pc.h[k], 1u);
+        else atomicAdd(&kept[k], 1ull);
+    }
+    if (hist) {
+        const u32 b = lb * MDX_PMD_BINS + mdx_pmd_bin(s), last = (u32)a.n_libraries * MDX_PMD_BINS;
+        const bool noq = mdx_pmd_no_qual(a, i);
+        if (pc.hist_lds) {
+            atomicAdd(&pc.hh[b], 1u);
+            if (noq) atomicAdd(&pc.hh[last], 1u);
+        } else {
+            atomicAdd(&hist[b], 1ull);
+            if (noq) atomicAdd(&hist[last], 1ull);
+        }
+    }
+}
+
+// COOP: a group of lanes per record; else a lane per record (the trivial form, kept to be measured against: tools/strata_cost.py)
+// STAGE: COOP with part of the term table in the LDS; without, every term from global memory (kept to be measured against too)
+template <bool COOP, bool STAGE>
+__global__ __launch_bounds__(256) void strata_pmd_key_kernel(MdxPmdKey a, u16 *__restrict__ key, u64 *__restrict__ kept, u64 *__restrict__ hist) {
+    // the LDS as the launch sized it (pmd_lds_words): [the staged terms, COOP][strata counts][histogram]
+    extern __shared__ u32 pmd_lds[];
+    const int n_strata = a.n_libraries * (a.n_thresholds + 1), n_hist = a.n_libraries * MDX_PMD_BINS + 1;
+    PmdCounts pc;
+    pc.in_lds = n_strata <= LS_LDS_LIBS;
+    pc.hist_lds = n_hist <= PMD_HIST_LDS;
+    int32_t *const tab = (int32_t *)pmd_lds;
+    u32 *const h = pmd_lds + (STAGE ? PMD_LDS_Z * PMD_LDS_Q : 0), *const hh = h + (pc.in_lds ? n_strata : 0);
+    pc.h = h; pc.hh = hh;
+    if (STAGE)
+        for (int l = threadIdx.x; l < PMD_LDS_Z * PMD_LDS_Q; l += 256) tab[l] = a.terms[(l / PMD_LDS_Q) * MDX_PMD_QCOLS + l % PMD_LDS_Q];
+    if (pc.in_lds && kept)
+        for (int l = threadIdx.x; l < n_strata; l += 256) h[l] = 0u;
+    if (pc.hist_lds && hist)
+        for (int l = threadIdx.x; l < n_hist; l += 256) hh[l] = 0u;
+    __syncthreads();
+    const PmdLdsTerms terms{a.terms, tab};
+    const i64 lo = (i64)blockIdx.x * STRATA_KEY_PER, hi = lo + STRATA_KEY_PER < a.n ? lo + STRATA_KEY_PER : a.n;
+    if (COOP) {
+        const int g = threadIdx.x / PMD_GROUP, l = threadIdx.x % PMD_GROUP;
+        // (the bounds of the loop are the block's: every lane of a wavefront reaches the butterfly)
+        for (i64 base = lo; base < hi; base += 256 / PMD_GROUP) {
+            const i64 i = base + g;
+            const bool live = i < hi;
+            u32 lb = 0xFFFFu, fl = 0u;
+            i64 s = 0;
+            if (live) {
+                lb = a.lib[i]; fl = a.flag[i];
+                MdxPmdRecord r;
+                if (lb < (u32)a.n_libraries && mdx_pmd_open(a, i, fl, r)) {
+                    if (r.c1 - r.c0 <= (u32)PMD_COOP_OPS) s = STAGE ? mdx_pmd_walk4(a, r, l, PMD_GROUP, terms) : mdx_pmd_walk4(a, r, l, PMD_GROUP);
+                    else if (l == 0) s = mdx_pmd_walk(a, r, 0, 1);
+                }
+            }
+#pragma unroll
+            for (int o = PMD_GROUP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, PMD_GROUP);
+            if (live && l == 0) pmd_count(a, i, lb, fl, s, pc, key, kept, hist);
+        }
+    } else {
+        for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
+            const u32 lb = a.lib[i], fl = a.flag[i];
+            const i64 s = lb < (u32)a.n_libraries ? mdx_pmd_score(a, i, fl) : 0;
+            pmd_count(a, i, lb, fl, s, pc, key, kept, hist);
+        }
+    }
+    __syncthreads();
+    if (pc.in_lds && kept)
+        for (int l = threadIdx.x; l < n_strata; l += 256)
+            if (h[l]) atomicAdd(&kept[l], (u64)h[l]);
+    if (pc.hist_lds && hist)
+        for (int l = threadIdx.x; l < n_hist; l += 256)
+            if (hh[l]) atomicAdd(&hist[l], (u64)hh[l]);
+}
+
+void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, unsigned long long *kept, unsigned long long *hist, int form,
+                          hipStream_t s) {
+    if (a.n <= 0) return;
+    const dim3 grid((unsigned)((a.n + STRATA_KEY_PER - 1) / STRATA_KEY_PER));
+    // (at most 24 + 16 + 16 KB: within what a launch gets without asking)
+    const int n_strata = a.n_libraries * (a.n_thresholds + 1), n_hist = a.n_libraries * MDX_PMD_BINS + 1;
+    const size_t words = (size_t)(n_strata <= LS_LDS_LIBS ? n_strata : 0) + (size_t)(n_hist <= PMD_HIST_LDS ? n_hist : 0);
+    if (form == 1) hipLaunchKernelGGL((strata_pmd_key_kernel<false, false>), grid, dim3(256), words * 4, s, a, key, (u64 *)kept, (u64 *)hist);
+    else if (form == 2) hipLaunchKernelGGL((strata_pmd_key_kernel<true, false>), grid, dim3(256), words * 4, s, a, key, (u64 *)kept, (u64 *)hist);
+    else hipLaunchKernelGGL((strata_pmd_key_kernel<true, true>), grid, dim3(256), (words + PMD_LDS_Z * PMD_LDS_Q) * 4, s, a, key, (u64 *)kept, (u64 *)hist);
+}
+
 // ... and for a batch that brings its columns bucketed by stratum (mdx_batch::libsort): the sizes of the buckets
 __global__ void strata_kept_from_sort_kernel(const u32 *__restrict__ lib_start, int n_strata, u64 *__restrict__ kept) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;

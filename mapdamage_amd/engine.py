@@ -47,7 +47,7 @@ EXPORTS = (
     "mdx_gsam_view_flags", "mdx_gsam_view_set_flags", "mdx_gsam_missing_qualities", "mdx_gsam_close",
     "mdx_gsam_is_bgzf", "mdx_gsam_tell_bgzf",
     "mdx_last_launch_geometry",
-    "mdx_set_strata", "mdx_set_strata_regions", "mdx_set_strata_damage", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
+    "mdx_set_strata", "mdx_set_strata_regions", "mdx_set_strata_damage", "mdx_set_strata_pmd", "mdx_strata_pmd_histogram", "mdx_strata_pmd_unqualified", "mdx_strata_groups", "mdx_strata_kept", "mdx_merged_words", "mdx_finish_merged", "mdx_finish_merged_host", "mdx_lgd_copies",
     "mdx_stats_loglik", "mdx_stats_run", "mdx_stats_pmat",
     "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
     "mdx_gsam_filter_counts",
@@ -193,6 +193,9 @@ def load_library(path=None):
     lib.mdx_set_strata_regions.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
     lib.mdx_set_strata_damage.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+    lib.mdx_set_strata_pmd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_strata_pmd_histogram.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_strata_pmd_unqualified.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_strata_groups.argtypes = [ctypes.c_void_p]
     lib.mdx_strata_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_merged_words.restype = ctypes.c_int64
@@ -270,7 +273,8 @@ class DamageEngine:
     ``groups``: names of groups of reference sequences — the engine then keeps one table set per (library, group), a
     *stratum* (include/mdx.h ``mdx_set_strata``): ``set_strata(group_of_tid)`` says which group each sequence of the
     header belongs to (or ``set_strata_regions(...)`` which group each region of a BED file does, or ``set_strata_damage(...)``
-    that the groups are ``DAMAGE_GROUPS``, told by the substitutions at the record's own ends), the batches keep naming
+    that the groups are ``DAMAGE_GROUPS``, told by the substitutions at the record's own ends, or ``set_strata_pmd(...)`` that
+    they are the intervals between thresholds of the record's post-mortem damage score), the batches keep naming
     the library in their ``lib`` column, and ``finish()`` returns a ``tables.StratifiedTables``.  ``libraries`` then holds one entry per stratum, library-major (``base_libraries`` the
     caller's list)."""
 
@@ -293,6 +297,7 @@ class DamageEngine:
                              % (len(self.base_libraries), len(self.groups or [None]), n_tables, self.MAX_TABLES))
         self._lib = load_library()
         self._strata_set = False
+        self._pmd = False
         self.libraries = [lib for lib in self.base_libraries for _ in (self.groups or [None])]
         self.length, self.around, self.minqual, self.lgd_max = length, around, minqual, lgd_max
         self.lgd_over_cap = lgd_over_cap
@@ -381,6 +386,43 @@ class DamageEngine:
             raise ValueError("set_strata_damage: the engine must be made with groups=%r" % (self.DAMAGE_GROUPS,))
         self._check(self._lib.mdx_set_strata_damage(self._ctx, ctypes.c_int32(int(positions)), ctypes.c_int32(1 if single_stranded else 0)))
         self._strata_set = True
+
+    def set_strata_pmd(self, thresholds, model=(0.3, 0.01, 0.001), single_stranded=False):
+        """The group of a record from its post-mortem damage score (include/mdx.h ``mdx_set_strata_pmd``; the rule is
+        ``csrc/mdx_pmd_key.h``): the number of ``thresholds`` (1 to 15, strictly increasing) the score reaches, under the
+        model ``(p, C, pi)`` of ``pmd.term_table``.  The engine's ``groups`` number ``len(thresholds) + 1``
+        (``pmd.group_names``), and it has no ``minqual``.  Before the first ``tabulate``; the key reads the reference, so
+        ``set_reference`` comes before ``upload``; the batches bring their qualities if these are to count."""
+        from . import pmd
+        ts = pmd.check_thresholds(thresholds)
+        if self.groups is None or len(self.groups) != len(ts) + 1:
+            raise ValueError("set_strata_pmd: %d thresholds make %d groups; the engine was made with %s"
+                             % (len(ts), len(ts) + 1, "none" if self.groups is None else "%d" % len(self.groups)))
+        fx = np.array([pmd.threshold_fx(t) for t in ts], np.int64)
+        terms = np.ascontiguousarray(pmd.term_table(*model), np.int32)
+        self._check(self._lib.mdx_set_strata_pmd(self._ctx, ctypes.c_int32(len(ts)), _ptr(fx), _ptr(terms),
+                                                 ctypes.c_int32(1 if single_stranded else 0)))
+        self._strata_set = True
+        self._pmd = True
+
+    @property
+    def pmd_strata(self):
+        """The engine's strata are those of ``set_strata_pmd``: ``finish()`` brings the score histogram."""
+        return self._pmd
+
+    def pmd_histogram(self):
+        """uint64 [base libraries][82]: the kept records of each library by their score (``mdx_strata_pmd_histogram``; bin
+        ``b`` holds the scores of ``pmd.bin_edges(b)``)."""
+        # (sized by the context's own count of libraries: its tables over its groups)
+        hist = np.zeros((len(self.libraries) // max(1, int(self._lib.mdx_strata_groups(self._ctx))), 82), np.uint64)
+        self._check(self._lib.mdx_strata_pmd_histogram(self._ctx, _ptr(hist)))
+        return hist
+
+    def pmd_unqualified(self):
+        """How many of the histogram's records were scored without qualities (``mdx_strata_pmd_unqualified``)."""
+        n = np.zeros(1, np.uint64)
+        self._check(self._lib.mdx_strata_pmd_unqualified(self._ctx, _ptr(n)))
+        return int(n[0])
 
     def strata_kept(self):
         """Records the flag filter kept, per stratum (library-major), of this engine's batches (``mdx_strata_kept``)."""
@@ -581,6 +623,8 @@ class DamageEngine:
                              "(finish_allreduce) and split it with tables.StratifiedTables.from_block")
         strata = self._finish_block()
         out = StratifiedTables.from_block(strata, self.base_libraries, self.groups, self.strata_kept())
+        if self._pmd:
+            out.pmd_hist, out.pmd_unqualified = self.pmd_histogram(), self.pmd_unqualified()
         merged = np.zeros(int(self._lib.mdx_merged_words(self._ctx)), np.uint64)
         self._check(self._lib.mdx_finish_merged_host(self._ctx, _ptr(merged)))
         out.merged = unpack_words(merged, self.base_libraries, self.length, self.around, self.lgd_max, out.merged.lgd_over)

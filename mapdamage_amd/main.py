@@ -174,6 +174,22 @@ def build_parser():
     g.add_argument("--terminal-positions", type=_ranged(int, 1), default=None, metavar="K",
                    help="with --by-terminal-damage: the positions from either end that decide a record's group (default 1, at "
                         "most --length).  Not a reference option either")
+    g.add_argument("--by-pmd-score", action="store_true",
+                   help="also tabulate the records apart by their post-mortem damage score (PMDS; Skoglund et al. 2014, PNAS "
+                        "111:2229), in the same pass: the log-likelihood ratio, over the record's whole alignment and with its "
+                        "base qualities, that it carries deamination damage — C>T from its 5p end, G>A from its 3p end (C>T "
+                        "with --single-stranded).  The usual three files are what the run writes without the option; by_pmd/ "
+                        "holds groups.tsv, the three files of the records below, between and at or above the --pmd-thresholds in "
+                        "directories named by their index, and scores.tsv: the score distribution per library in half-unit bins. "
+                        "What `pmdtools --threshold T` in front of the run would have kept is the last group.  Not with "
+                        "--min-basequal, whose mask replaces the qualities the score reads.  Not a reference option: "
+                        "mapdamage/config.py has none")
+    g.add_argument("--pmd-thresholds", default=None, metavar="T[,T...]",
+                   help="with --by-pmd-score: 1 to 15 strictly increasing scores that part the groups (default 3; a list that begins with a "
+                        "negative number is written --pmd-thresholds=-1,3)")
+    g.add_argument("--pmd-model", default=None, metavar="p,C,pi",
+                   help="with --by-pmd-score: the damage model D_z = p (1-p)^(z-1) + C at distance z from the end and the "
+                        "polymorphism rate pi (default 0.3,0.01,0.001; 0 < p < 1, 0 <= C, p + C < 1, 0 < pi < 1)")
     g.add_argument("--min-mapq", type=_ranged(int, 0, 255), default=0, metavar="Q",
                    help="drop the records whose MAPQ is below Q, as `samtools view -q Q` in front would (numeric: 255 passes any Q); "
                         "evaluated by the decoders, on the device where the file is decoded there.  Not a reference option "
@@ -239,6 +255,28 @@ def parse_args(argv):
     if o.record_filter.active and (o.rescale_only or o.stats_only):
         parser.error("--min-mapq / --require-flags / --exclude-flags / --min-read-length / --max-read-length belong to the "
                      "tabulation pass; neither --rescale-only nor --stats-only counts records")
+    if (o.pmd_thresholds is not None or o.pmd_model is not None) and not o.by_pmd_score:
+        parser.error("--pmd-thresholds / --pmd-model need --by-pmd-score")
+    if o.by_pmd_score:
+        from . import pmd
+        if o.by_reference or o.reference_groups or o.regions or o.region_groups or o.by_terminal_damage:
+            parser.error("--by-pmd-score and --by-reference / --reference-groups / --regions / --region-groups / "
+                         "--by-terminal-damage exclude each other: a run has one kind of groups")
+        if o.rescale_only or o.stats_only:
+            parser.error("--by-pmd-score belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
+        if o.minqual > 0:
+            parser.error("--by-pmd-score cannot be combined with -Q / --min-basequal: the score weighs every base by its "
+                         "quality, and under --min-basequal the decoders fold the mask into the bases and may drop the "
+                         "quality column")
+        try:
+            o.pmd_thresholds = pmd.check_thresholds(
+                [float(t) for t in ("3" if o.pmd_thresholds is None else o.pmd_thresholds).split(",")])
+            model = [float(v) for v in ("0.3,0.01,0.001" if o.pmd_model is None else o.pmd_model).split(",")]
+            if len(model) != 3:
+                raise ValueError("--pmd-model takes three numbers: p,C,pi")
+            o.pmd_model = pmd.check_model(*model)
+        except ValueError as error:
+            parser.error("--by-pmd-score: %s" % error)
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -397,13 +435,13 @@ def _group_has_data(folder):
 
 def bayesian_estimates(options, logger, ref=None, n_contig=0, device=0):
     """The estimate of the folder's tables and of every group directory beside them (by_reference/<index>,
-    by_region/<index>, by_damage/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
+    by_region/<index>, by_damage/<index>, by_pmd/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
     from .stats import StatsError, estimate_folders
     start = time.time()
     try:
         acgt = _base_frequencies(options, ref, n_contig, device)
         folders, chains = [options.folder], [options.stats_chain]
-        for sub in ("by_reference", "by_region", "by_damage"):
+        for sub in ("by_reference", "by_region", "by_damage", "by_pmd"):
             if not (options.folder / sub / "groups.tsv").is_file():
                 continue
             index = 0
@@ -485,7 +523,16 @@ class _Ranks:
         if device is not None:
             kept = kept.to(device)
         kept = allreduce_words(kept).cpu().numpy().view(np.uint64)
-        return StratifiedTables.from_block(block, engine.base_libraries, engine.groups, kept)
+        out = StratifiedTables.from_block(block, engine.base_libraries, engine.groups, kept)
+        if engine.pmd_strata:
+            # (--by-pmd-score: the score histogram and the records scored without qualities, summed as the kept reads are)
+            words = np.concatenate([engine.pmd_histogram().reshape(-1), np.array([engine.pmd_unqualified()], np.uint64)])
+            words = torch.from_numpy(words.view(np.int64).copy())
+            if device is not None:
+                words = words.to(device)
+            words = allreduce_words(words).cpu().numpy().view(np.uint64)
+            out.pmd_hist, out.pmd_unqualified = words[:-1].reshape(len(engine.base_libraries), -1), int(words[-1])
+        return out
 
     def sum_counts(self, counts):
         """The record filters' counts (uint64[6]) summed over the ranks, as the kept reads per stratum are."""
@@ -524,11 +571,22 @@ class TerminalDamage(NamedTuple):
     single_stranded: bool
 
 
+class PmdScore(NamedTuple):
+    """What --by-pmd-score hands to ``DamageEngine.set_strata_pmd``."""
+    thresholds: tuple
+    model: tuple
+    single_stranded: bool
+
+
 def reference_strata(options, references, lengths=None):
     """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, (group names,
     tables.Regions) of --regions / --region-groups (``lengths``: the sequences' lengths), (group names, TerminalDamage) of
-    --by-terminal-damage, or None."""
+    --by-terminal-damage, (group names, PmdScore) of --by-pmd-score, or None."""
     from .tables import Regions, groups_by_reference, parse_reference_groups, parse_regions
+    if getattr(options, "by_pmd_score", False):
+        from .pmd import group_names
+        return group_names(options.pmd_thresholds), PmdScore(tuple(options.pmd_thresholds), tuple(options.pmd_model),
+                                                             bool(options.single_stranded))
     if getattr(options, "by_terminal_damage", False):
         return list(DamageEngine.DAMAGE_GROUPS), TerminalDamage(options.terminal_positions, bool(options.single_stranded))
     if options.by_reference:
@@ -543,15 +601,17 @@ def reference_strata(options, references, lengths=None):
 
 
 def _make_engine(options, libraries, device):
-    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups / --by-terminal-damage one
-    table set per (library, group) — the input routes hand it the same batches either way."""
+    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups / --by-terminal-damage /
+    --by-pmd-score one table set per (library, group) — the input routes hand it the same batches either way."""
     from .tables import Regions
     strata = getattr(options, "strata", None)
     engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=device,
                           groups=None if strata is None else strata[0])
     if strata is not None:
         try:
-            if isinstance(strata[1], TerminalDamage):
+            if isinstance(strata[1], PmdScore):
+                engine.set_strata_pmd(strata[1].thresholds, strata[1].model, strata[1].single_stranded)
+            elif isinstance(strata[1], TerminalDamage):
                 engine.set_strata_damage(strata[1].positions, strata[1].single_stranded)
             elif isinstance(strata[1], Regions):
                 engine.set_strata_regions(strata[1].iv_off, strata[1].iv_start, strata[1].iv_end, strata[1].iv_group)
@@ -697,6 +757,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         lib_default = None
     engine = _make_engine(options, libraries, ranks.device)
     stages.mark("engine")
+    # (--by-pmd-score: the key reads the qualities beside the nibbles the packed kernel counts from)
+    by_pmd = bool(getattr(options, "by_pmd_score", False))
     carry = None
     try:
         engine.set_reference(ref)
@@ -710,8 +772,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         stages.mark("warm-up joined")
         with (GpuSamStream if sam_text else GpuBamStream)(
                 engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
-                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0, min_basequal=options.minqual,
-                record_filter=options.record_filter) as stream:
+                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0 or by_pmd, min_basequal=options.minqual,
+                packed=True if by_pmd else None, record_filter=options.record_filter) as stream:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
             slab, n_reads, n_kept = 0, 0, 0
             try:
@@ -943,7 +1005,7 @@ def main(argv):
             logger.error("%s", error)
             return 1
         if options.strata is not None:
-            kind = "terminal damage" if options.by_terminal_damage else "regions" if options.regions or options.region_groups else "reference sequences"
+            kind = "PMD score" if options.by_pmd_score else "terminal damage" if options.by_terminal_damage else "regions" if options.regions or options.region_groups else "reference sequences"
             logger.info("Tabulating %d groups of %s x %d libraries in one pass", len(options.strata[0]), kind, len(libraries))
             if len(options.strata[0]) * len(libraries) > DamageEngine.MAX_TABLES:
                 logger.error("%d groups of %s x %d libraries: more than the %d tables a run can keep",
@@ -985,7 +1047,16 @@ def main(argv):
             return 0
         if options.strata is not None:
             # the three usual files from the sum over the groups, and by_reference/ beside them
-            if options.by_terminal_damage:
+            if options.by_pmd_score:
+                from .pmd import groups_text, scores_text
+                tables.write(options.folder, subdir="by_pmd",
+                             groups_text=groups_text(tables.groups, [tables.group_kept(g) for g in range(len(tables.groups))]))
+                (options.folder / "by_pmd" / "scores.tsv").write_text(scores_text(tables.libraries, tables.pmd_hist))
+                if tables.pmd_unqualified:
+                    logger.info("PMD scores: %d records without PHRED scores were scored with a base error of 0",
+                                tables.pmd_unqualified)
+                tables = tables.merged
+            elif options.by_terminal_damage:
                 tables.write(options.folder, subdir="by_damage", groups_text=tables.damage_groups_text())
                 (options.folder / "by_damage" / "conditional.tsv").write_text(tables.conditional_text(options.strata[1].single_stranded))
                 tables = tables.merged

@@ -307,6 +307,8 @@ class StratifiedTables:
     strata: TableSet
     kept: np.ndarray = None
     merged: TableSet = None
+    pmd_hist: np.ndarray = None      # --by-pmd-score: kept records per library and bin of the score (``pmd.scores_text``)
+    pmd_unqualified: int = 0         # ... and those of them scored without qualities
 
     @classmethod
     def from_block(cls, strata, libraries, groups, kept=None):

@@ -7,7 +7,7 @@ interleaved in one process — a, b, a, b, ... — and timed on the wall clock, 
 the box does to one it does to the other; the spread of (b)'s own repeats is quoted beside the ratio.  The key moves 10
 bytes per record (flag, tid and lib in, a key out) against the 240 of the tabulation: a ratio near 1.03 is what the
 arithmetic allows.  The two blocks are compared bit for bit on the way.  Run on the GPU box:
-    python tools/strata_cost.py [--out FILE] [--regions | --damage] [records] [repeats]
+    python tools/strata_cost.py [--out FILE] [--regions | --damage | --pmd] [records] [repeats]
 --regions: (a) is a region-stratified context (mdx_set_strata_regions) of 1 library x 8 groups — 4 000 regions of 150 bases
 per contig in seven groups and the rest, so the binary search of a sequence's slice takes 12 steps — and (b)'s lib column
 holds the same key made on the host with numpy.  The region key reads pos, the two CIGAR offsets and the CIGAR words (one
@@ -17,7 +17,18 @@ stay in the L2 (384 KB of intervals).  No bound is fixed: the rows say what was 
 a plain context of 4 libraries whose lib column holds the same key, made on the host with numpy from the rule.  On top of
 the tid key's 10 bytes the damage key reads pos, the CIGAR offsets and words, the SEQ offsets and a symbol of SEQ and of the
 reference per end — some 40 bytes, in one or two random 128-byte lines each of SEQ and reference per record.  No bound is
-fixed here either."""
+fixed here either.
+--pmd: the records carry qualities; (a) is a PMD-stratified context (mdx_set_strata_pmd, thresholds 0 and 3, the default
+model) of 1 library x 3 groups, (a') the same context with the trivial key kernel — a lane per record, MDX_PMD_LANE=1 —
+instead of the cooperative one, (a'') the cooperative kernel with every term read from global memory instead of part of the
+table kept in the LDS (MDX_PMD_NO_LDS=1), and (b) a plain context of 3 libraries whose lib column holds the same key, made on
+the host by the rule's header compiled for the host (csrc/mdx_pmd_key.h through tests/pmd_key_host.cpp, which
+tests/test_pmd.py holds to the rule's restatement: this mode needs a host C++ compiler where it runs, and that file of the
+tests).  A repeat is a, b, a', b, a'', b — every timed call behind a call of the other context; the first b of a repeat is
+the timed one, the other two keep (b)'s tables in step with (a)'s for the comparison of the blocks.  The key reads every aligned base: the 4-bit SEQ, the
+QUAL bytes and the reference window of a record, some 250 bytes on top of the fixed columns — as much again as the
+tabulation streams; the rows give the key kernels' own time (a - b, a' - b), the bytes they move and what that is of an
+8 TB/s roofline.  No bound is fixed."""
 import ctypes
 import json
 import pathlib
@@ -128,6 +139,34 @@ def host_damage_key(b, ref):
     return (p5.astype(np.uint16) + 2 * p3.astype(np.uint16)).astype(np.uint16)
 
 
+def host_pmd_key(b, ref, thresholds, workdir):
+    """(group, histogram bin) of every record by csrc/mdx_pmd_key.h compiled for the host (the default model, double-stranded)."""
+    import subprocess
+    from mapdamage_amd import pmd
+    so = pathlib.Path(workdir) / "pmd_key_host.so"
+    subprocess.check_call(["c++", "-O2", "-shared", "-fPIC", "-I", str(ROOT / "mapdamage_amd" / "csrc"),
+                           str(ROOT / "tests" / "pmd_key_host.cpp"), "-o", str(so)])
+    lib = ctypes.CDLL(str(so))
+    bases, offs = ref.concat()
+    up = np.where((bases >= 97) & (bases <= 122), bases - 32, bases).astype(np.uint8)
+    resident = np.where(np.isin(up, np.frombuffer(b"ACGT", np.uint8)), up, np.uint8(0x85)).astype(np.uint8)
+    offs = np.ascontiguousarray(offs, np.int64)
+    terms = np.ascontiguousarray(pmd.term_table())
+    fx = np.array([pmd.threshold_fx(t) for t in thresholds], np.int64)
+    score, group = np.zeros(b.n, np.int64), np.zeros(b.n, np.uint8)
+    bins, noq = np.zeros(b.n, np.uint8), np.zeros(b.n, np.uint8)
+
+    def ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p)
+    lib.pmd_scores_host(ctypes.c_int64(b.n), ctypes.c_int64(b.cigar.shape[0]), ctypes.c_int64(b.seq.shape[0]), ptr(b.flag), ptr(b.tid),
+                        ptr(b.pos), ptr(b.cigar_off), ptr(b.cigar), ptr(b.seq_off), ptr(b.seq), ptr(b.qual), 0, ptr(resident), ptr(offs),
+                        len(ref.names), 0, ptr(terms), len(thresholds), ptr(fx), 1, ptr(score), ptr(group), ptr(bins), ptr(noq))
+    return group.astype(np.uint16), bins
+
+
+PMD_THRESHOLDS = (0.0, 3.0)
+
+
 def main():
     argv = list(sys.argv[1:])
     out = None
@@ -137,6 +176,9 @@ def main():
     damage = "--damage" in argv
     if damage:
         argv.remove("--damage")
+    by_pmd = "--pmd" in argv
+    if by_pmd:
+        argv.remove("--pmd")
     if "--out" in argv:
         at = argv.index("--out")
         out = argv[at + 1]
@@ -145,14 +187,21 @@ def main():
     reps = int(argv[1]) if len(argv) > 1 else 9
     ref = synth.make_genome(sizes=tuple(("contig%d" % i, 1_250_000) for i in range(N_CONTIG)))
     # (before the process touches the GPU: the generator forks)
-    b = synth.parallel_batch(CONFIG3, ref, n, 3)
-    names = list(DamageEngine.DAMAGE_GROUPS) if damage else list(ref.names)
+    b = synth.parallel_batch(dict(CONFIG3, with_qual=True) if by_pmd else CONFIG3, ref, n, 3)
+    names = ["<0", "[0,3)", ">=3"] if by_pmd else list(DamageEngine.DAMAGE_GROUPS) if damage else list(ref.names)
+    if by_pmd:
+        import os
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            pmd_key, pmd_bins = host_pmd_key(b, ref, PMD_THRESHOLDS, tmp)
     with DamageEngine([("s", "l")], 70, 10, 0, lgd_max=4096, groups=names) as ea, \
             DamageEngine([("s", "l%d" % i) for i in range(len(names))], 70, 10, 0, lgd_max=4096) as eb:
         cols = region_columns() if regions else None
 
         def set_strata():
-            if damage:
+            if by_pmd:
+                ea.set_strata_pmd(PMD_THRESHOLDS)
+            elif damage:
                 ea.set_strata_damage(1)
             elif regions:
                 ea.set_strata_regions(*cols)
@@ -165,7 +214,7 @@ def main():
         b.lib[:] = 0
         da, va = resident_without_sort(ea, b)
         # the same key, made on the host
-        b.lib[:] = host_damage_key(b, ref) if damage else host_region_key(b, cols) if regions else np.clip(b.tid, 0, N_CONTIG - 1).astype(np.uint16)
+        b.lib[:] = pmd_key if by_pmd else host_damage_key(b, ref) if damage else host_region_key(b, cols) if regions else np.clip(b.tid, 0, N_CONTIG - 1).astype(np.uint16)
         per_group = np.bincount(b.lib, minlength=len(names)).tolist()
         db, vb = resident_without_sort(eb, b)
         for _ in range(2):
@@ -174,33 +223,66 @@ def main():
         ea.reset()
         eb.reset()
         set_strata()
-        ta, tb = [], []
+        ta, tb, tl, tn = [], [], [], []
         for _ in range(reps):
             ta.append(one_call(ea, va))
             tb.append(one_call(eb, vb))
+            if by_pmd:
+                # (a'), (a''): the same context and batch through the other two kernels; their counts go to the same tables,
+                # so (b) is called behind each, untimed, and the parity below is taken over a + a' + a'' against b three times
+                for knob, times in (("MDX_PMD_LANE", tl), ("MDX_PMD_NO_LDS", tn)):
+                    os.environ[knob] = "1"
+                    times.append(one_call(ea, va))
+                    del os.environ[knob]
+                    one_call(eb, vb)
         sorts = (ea.libsorts(), eb.libsorts())
         got, want = ea.finish(), eb.finish()
+        hist_ok = True
+        if by_pmd:
+            hist_ok = bool((got.pmd_hist[0] == 3 * reps * np.bincount(pmd_bins[(b.flag & 0xF04) == 0], minlength=82)).all())
         parity = bool((got.strata.mis == want.mis).all() and (got.strata.comp == want.comp).all() and
                       (got.strata.lgd == want.lgd).all() and got.n_kept == want.n_kept and
-                      int(got.kept.sum()) == want.n_kept)
+                      int(got.kept.sum()) == want.n_kept and hist_ok)
         da.free()
         db.free()
     med_a, med_b = float(np.median(ta)), float(np.median(tb))
     spread_b = (max(tb) - min(tb)) / med_b
     ratio = med_a / med_b
+    if by_pmd:
+        med_l, med_n = float(np.median(tl)), float(np.median(tn))
+        # what the key kernel streams: the fixed columns (flag, lib, tid, pos, two offsets in, the key out), the CIGAR words,
+        # 4-bit SEQ, QUAL, and a reference byte per reference base of the alignment
+        op, ln = b.cigar & 15, (b.cigar >> 4).astype(np.int64)
+        key_bytes = 22 * n + 4 * int(b.cigar.shape[0]) + int(b.seq.shape[0]) // 2 + int(b.seq.shape[0]) + int(ln[np.isin(op, (0, 2, 3, 7, 8))].sum())
+
+        def kernel_row(what, med):
+            own = med - med_b
+            return {"what": what, "ms": round(own, 3), "bytes_per_record": round(key_bytes / n, 1),
+                    "TB_per_s": round(key_bytes / (own * 1e-3) / 1e12, 3) if own > 0 else None,
+                    "of_8_TB_per_s_roofline": round(key_bytes / (own * 1e-3) / 8e12, 3) if own > 0 else None}
     rows = [
-        {"what": "strata_cost_damage" if damage else "strata_cost_regions" if regions else "strata_cost",
-         "form": "damage key (one terminal position, double-stranded) into a scratch column in front of the launch" if damage else ("region key (%d regions of %d bases per contig, 7 groups and the rest) into a scratch column in front of the launch"
+        {"what": "strata_cost_pmd" if by_pmd else "strata_cost_damage" if damage else "strata_cost_regions" if regions else "strata_cost",
+         "form": "PMD key (thresholds 0 and 3, default model, double-stranded, records with qualities) into a scratch column in front of the launch" if by_pmd else "damage key (one terminal position, double-stranded) into a scratch column in front of the launch" if damage else ("region key (%d regions of %d bases per contig, 7 groups and the rest) into a scratch column in front of the launch"
                   % (REGIONS_PER_CONTIG, REGION_BASES)) if regions else "scratch key column in front of the launch",
          "records": n, "contigs": N_CONTIG, "repeats": reps, "records_per_group": per_group,
          "timed": "wall clock of tabulate + sync per call, a and b interleaved in one process", "sorts_in_launch": sorts,
          "parity_a_equals_b": parity},
-        {"what": "a: %sstratified context, 1 library x %d groups" % ("damage-" if damage else "region-" if regions else "", len(names)), "ms": [round(x, 3) for x in ta], "median_ms": round(med_a, 3)},
+        {"what": "a: %sstratified context, 1 library x %d groups" % ("PMD-" if by_pmd else "damage-" if damage else "region-" if regions else "", len(names)), "ms": [round(x, 3) for x in ta], "median_ms": round(med_a, 3)},
         {"what": "b: plain context, %d libraries, key in the lib column (baseline)" % len(names), "ms": [round(x, 3) for x in tb],
          "median_ms": round(med_b, 3), "spread": round(spread_b, 4)},
-        {"what": "ratio a / b", "ratio": round(ratio, 4)} if regions or damage else
+        {"what": "ratio a / b", "ratio": round(ratio, 4)} if regions or damage or by_pmd else
         {"what": "ratio a / b", "ratio": round(ratio, 4), "bound": round(1.03 + spread_b, 4), "within_bound": bool(ratio <= 1.03 + spread_b)},
     ]
+    if by_pmd:
+        rows += [{"what": "a': the same context, trivial key kernel (a lane per record, MDX_PMD_LANE=1)", "ms": [round(x, 3) for x in tl],
+                  "median_ms": round(med_l, 3)},
+                 {"what": "ratio a' / b", "ratio": round(med_l / med_b, 4)},
+                 {"what": "a'': the same context, cooperative key kernel with every term from global memory (MDX_PMD_NO_LDS=1)",
+                  "ms": [round(x, 3) for x in tn], "median_ms": round(med_n, 3)},
+                 {"what": "ratio a'' / b", "ratio": round(med_n / med_b, 4)},
+                 kernel_row("key kernel alone, cooperative (16 lanes per record), match terms of 128 distances x 48 qualities in the LDS: median a - median b", med_a),
+                 kernel_row("key kernel alone, cooperative, every term from global memory: median a'' - median b", med_n),
+                 kernel_row("key kernel alone, trivial (a lane per record): median a' - median b", med_l)]
     text = "".join(json.dumps(r) + "\n" for r in rows)
     sys.stdout.write(text)
     if out:
