@@ -587,6 +587,29 @@ int mdx_gbam_rescale_slab(struct mdx_gbam *g, uint8_t *out, int64_t out_cap, int
 int mdx_gbam_write_rescaled(struct mdx_gbam *g, const uint64_t *d_patch, int64_t patch_cap, int32_t n_parts, const uint64_t *d_n_patch,
                             const float *mr, const uint8_t *rescaled, uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *mr_clash);
 int mdx_gbam_record_name(struct mdx_gbam *g, int64_t index, char *buf, int32_t cap);
+/* --write-kept: the records a run counted, handed on as BAM in the pass that counts them (not a reference option; what
+ * `samtools view -q/-F/-L` or `pmdtools --threshold` behind the run would have written).  After every mdx_gbam_next, and behind the
+ * tabulation launch of its view (mdx_tabulate_device):
+ *   mdx_gbam_kept_bound     *bytes = an `out_cap` that always suffices for mdx_gbam_write_kept on the view handed out last: the
+ *                           inflated bytes of the view's records (exact, from the chain of record offsets), 64 more per 0xFF00 of
+ *                           them, and 64.
+ *   mdx_gbam_write_kept     the view's records with (flag & 0xF04) == 0 in the flag column as it stands now (after the record
+ *                           filter's 0x200 and whatever mdx_gbam_view_set_flags marked), in the file's order, each copied byte for
+ *                           byte from its block_size field to its last tag byte, as BGZF members to `out` (host): no header, no
+ *                           end-of-file marker, nothing at all for a view without such a record.  *n_written = the records,
+ *                           *raw_bytes = their bytes before compression, *out_len = the members' bytes.
+ *                           group_selected (host, one byte per group; NULL: every such record): only the records whose group is
+ *                           listed — the context must be stratified (mdx_set_strata*) with n_groups groups, else MDX_ERR_ARG, and
+ *                           its key column must be that of this very view: the view tabulated, and no other batch since, else
+ *                           MDX_ERR_STATE.  A record without a library (key 0xFFFF) is never written with a selection.  The rule
+ *                           is csrc/mdx_kept.h.
+ * Sizes, their prefix sum (64-bit offsets) and the gather run on the device; sixteen bytes come back before the members do.  The
+ * handle owns the scratch (sizes, offsets, tile sums, the stream, the selection), grown when a slab needs more and released by
+ * mdx_gbam_close: no allocation per slab.  Synchronous, on the context's stream.  The header (mdx_bgzf_deflate takes any bytes)
+ * and the end-of-file marker are the caller's to write. */
+int mdx_gbam_kept_bound(struct mdx_gbam *g, int64_t *bytes);
+int mdx_gbam_write_kept(struct mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                        int64_t *n_written, int64_t *raw_bytes);
 /* mdx_mr_round: float("%.5f" % x) of rescale.py:275-276 for n MR sums (mr_raw of the rescale calls) on `threads` host threads —
  * the value printed with five decimals, read back, and narrowed to the 32 bits of an MR:f tag; NaN (a record written back
  * unchanged) gives 0. */

@@ -1554,6 +1554,12 @@ struct mdx_gbam {
     int view_slab = 0;                   // ... and the one the last call did (mdx_gbam_view_flags)
     mdx_batch last_view{};               // ... its view (mdx_gbam_rescale_slab)
     const int32_t *last_mtid = nullptr, *last_mpos = nullptr;
+    // --write-kept (mdx_gbam_kept_bound / mdx_gbam_write_kept): the inflated bytes of the last view's records — from the first
+    // one's block_size field to the last one's last byte, as the chain of record offsets gave them —, the context's count of
+    // keyed batches when the view was handed out, and the scratch of the kernels (grown when a slab needs more, freed at close)
+    size_t view_rec_bytes = 0;
+    uint64_t view_key_serial = 0;
+    Buf kept_sizes, kept_off, kept_tiles, kept_sel, kept_stream;
     bool reserve(Buf &b, size_t bytes) {
         if (bytes <= b.cap) return true;
         if (b.p) (void)hipFree(b.p);
@@ -2106,6 +2112,7 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
         if (!have) at = slab_end;              // no record starts in this slab
     }
     bool grow = false;
+    const size_t at_first = at;
     while (at < slab_end) {
         while (seg < nba && (size_t)blk[4 * seg + 2] + blk[4 * seg + 3] <= at) seg++;
         if (seg >= nb) break;
@@ -2213,6 +2220,8 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
     g->phase_known = have;
     g->slabs_done++;
     g->view_reads = view->n_reads;
+    g->view_rec_bytes = at - at_first;
+    (void)mdx_ctx_strata_key(g->ctx, nullptr, nullptr, nullptr, &g->view_key_serial);
     s.ready = false;
     return MDX_OK;
 }
@@ -2495,6 +2504,7 @@ void mdx_gbam_close(mdx_gbam *g) {
     g->copy_stream = nullptr;
     rg_buffer_give(g->device, g->d_rg, g->d_rg_cap);
     if (g->d_filter_counts) (void)hipFree(g->d_filter_counts);
+    for (mdx_gbam::Buf *b : {&g->kept_sizes, &g->kept_off, &g->kept_tiles, &g->kept_sel, &g->kept_stream}) if (b->p) (void)hipFree(b->p);
     for (int k = 0; k < 3; k++) pf_buffer_give(g->device, g->pf_buf[k], g->pf_cap[k]);
     lap("device");
     // (unmapping the file — a few hundred thousand touched pages — is 3-4 ms of an 8 M-record file's 63; done behind the
@@ -2669,6 +2679,78 @@ int mdx_gbam_record_name(mdx_gbam *g, int64_t index, char *buf, int32_t cap) {
     if (len > 0 && hipMemcpy(buf, (const uint8_t *)s.unc.p + off + 32, (size_t)len, hipMemcpyDeviceToHost) != hipSuccess) return MDX_ERR_HIP;
     buf[len] = 0;
     return MDX_OK;
+}
+
+// --write-kept (include/mdx.h): the capacity that suffices for mdx_gbam_write_kept on the view handed out last — its records'
+// inflated bytes (every one of them kept, stored members: 26 bytes each and a few for the stored blocks' headers) —
+int mdx_gbam_kept_bound(mdx_gbam *g, int64_t *bytes) {
+    if (!g || !bytes) return MDX_ERR_ARG;
+    const int64_t b = (int64_t)g->view_rec_bytes;
+    *bytes = b + 64 * (b / 0xFF00) + 64;
+    return MDX_OK;
+}
+
+// ... and the records the run counted (or those of the chosen groups among them) as BGZF members: sizes by the rule of
+// mdx_kept.h and their prefix sum on the device, one copy of sixteen bytes back (records written, bytes of the stream), the
+// records gathered into the handle's stream buffer, that stream through the device's BGZF writer.  On the context's stream,
+// behind the tabulation launch of the view; nothing is allocated unless a slab needs more than any slab before it.
+int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                        int64_t *n_written, int64_t *raw_bytes) {
+    if (!g || !out_len || !n_written || !raw_bytes || out_cap < 0 || (out_cap > 0 && !out)) return MDX_ERR_ARG;
+    *out_len = 0; *n_written = 0; *raw_bytes = 0;
+    try {
+        const uint16_t *d_key = nullptr;
+        if (group_selected) {
+            const uint16_t *key_flag = nullptr;
+            int64_t key_n = 0;
+            uint64_t serial = 0;
+            const int ctx_groups = mdx_ctx_strata_key(g->ctx, &d_key, &key_flag, &key_n, &serial);
+            if (ctx_groups <= 0) { g->error = "mdx_gbam_write_kept: a selection of groups on a context without strata"; return MDX_ERR_ARG; }
+            if (n_groups != ctx_groups) {
+                g->error = "mdx_gbam_write_kept: n_groups " + std::to_string(n_groups) + ", the context has " + std::to_string(ctx_groups) + " groups";
+                return MDX_ERR_ARG;
+            }
+            // (an empty view is keyed by nobody: nothing to write, nothing to check)
+            if (g->view_reads > 0 && (serial == g->view_key_serial || !d_key || key_flag != g->last_view.flag || key_n != g->view_reads)) {
+                g->error = "mdx_gbam_write_kept: the context's key column is not that of this view (tabulate the view first, and nothing else in between)";
+                return MDX_ERR_STATE;
+            }
+        }
+        const int64_t n = g->view_reads;
+        if (n == 0) return MDX_OK;
+        if (n > 0xFFFFFFFFll) return MDX_ERR_ARG;
+        if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
+        hipStream_t st = g->stream;
+        mdx_gbam::Slab &s = g->slab[g->view_slab];
+        const size_t n_tiles = ((size_t)n + (size_t)mdx_k_gbam_kept_tile() - 1) / (size_t)mdx_k_gbam_kept_tile();
+        // (tile sums, and the tile bases with the total behind them: 16 bytes each)
+        if (!g->reserve(g->kept_sizes, (size_t)n * 4) || !g->reserve(g->kept_off, (size_t)n * 8) ||
+            !g->reserve(g->kept_tiles, (2 * n_tiles + 1) * 16) || !g->reserve(g->kept_stream, g->view_rec_bytes + 64) ||
+            (group_selected && !g->reserve(g->kept_sel, (size_t)n_groups))) return MDX_ERR_HIP;
+        int rc = MDX_OK;
+        auto ok = [&](hipError_t e) { if (e != hipSuccess) { rc = MDX_ERR_HIP; g->error = std::string("mdx_gbam_write_kept: ") + hipGetErrorString(e); (void)hipGetLastError(); } return e == hipSuccess; };
+        if (group_selected && !ok(hipMemcpyAsync(g->kept_sel.p, group_selected, (size_t)n_groups, hipMemcpyHostToDevice, st))) return rc;
+        char *tiles = (char *)g->kept_tiles.p;
+        void *tile_sum = tiles, *tile_base = tiles + n_tiles * 16;
+        mdx_k_gbam_kept_offsets((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint16_t *)s.flag.p, group_selected ? d_key : nullptr,
+                                group_selected ? (const uint8_t *)g->kept_sel.p : nullptr, (uint32_t)(group_selected ? n_groups : 0), (uint32_t)n,
+                                (uint32_t *)g->kept_sizes.p, tile_sum, tile_base, (unsigned long long *)g->kept_off.p, st);
+        unsigned long long total[2] = {0, 0};
+        if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(total, (char *)tile_base + n_tiles * 16, 16, hipMemcpyDeviceToHost, st)) ||
+            !ok(hipStreamSynchronize(st))) return rc;
+        if (total[1] > (unsigned long long)g->view_rec_bytes) { g->error = "mdx_gbam_write_kept: the kept records are larger than the slab that holds them"; return MDX_ERR_ARG; }
+        if (total[0] == 0) return MDX_OK;
+        mdx_k_gbam_kept_gather((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
+                               (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, st);
+        if (!ok(hipGetLastError())) return rc;
+        rc = bgzf_deflate_impl(st, g->device, nullptr, (const uint8_t *)g->kept_stream.p, (int64_t)total[1], out, out_cap, out_len);
+        if (rc != MDX_OK) { g->error = "mdx_gbam_write_kept: the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
+        *n_written = (int64_t)total[0]; *raw_bytes = (int64_t)total[1];
+        return MDX_OK;
+    } catch (const std::exception &e) {
+        g->error = std::string("mdx_gbam_write_kept: ") + e.what();
+        return MDX_ERR_ARG;
+    }
 }
 
 // One call per slab of a --rescale-only pass on the device (rescale.py:285-365): the view mdx_gbam_next handed out last (it

@@ -172,6 +172,9 @@ struct mdx_ctx {
     int32_t *d_pmd_terms = nullptr;            // [2][MDX_PMD_Z][MDX_PMD_QCOLS]
     unsigned long long *d_pmd_hist = nullptr;  // [libraries][MDX_PMD_BINS] and one word: the kept records scored without qualities
     DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
+    const uint16_t *strata_key_flag = nullptr;   // ... the flag column and n_reads of the batch it was made for (mdx_gbam_write_kept
+    int64_t strata_key_n = 0;                    // writes chosen groups of the view it was handed only behind that view's launch)
+    uint64_t strata_key_serial = 0;              // ... and how many batches have been keyed so far
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -622,6 +625,7 @@ static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool coun
                          (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
     HIP_TRY(c, hipGetLastError());
     out->lib = (const uint16_t *)c->strata_key.p;
+    c->strata_key_flag = b->flag; c->strata_key_n = b->n_reads; c->strata_key_serial++;
     return MDX_OK;
 }
 
@@ -1576,6 +1580,15 @@ void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, 
 }
 
 int mdx_ctx_minqual(const mdx_ctx *c) { return c ? c->cfg.minqual : -1; }
+
+int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const uint16_t **flag, int64_t *n_reads, uint64_t *serial) {
+    if (serial) *serial = c ? c->strata_key_serial : 0;
+    if (!c || c->n_groups <= 0) return 0;
+    if (key) *key = (const uint16_t *)c->strata_key.p;
+    if (flag) *flag = c->strata_key_flag;
+    if (n_reads) *n_reads = c->strata_key_n;
+    return c->n_groups;
+}
 
 int mdx_ctx_stream(mdx_ctx *c, void **stream, int *device) {
     if (!c) return MDX_ERR_ARG;

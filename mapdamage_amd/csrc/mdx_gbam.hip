@@ -531,3 +531,141 @@ void mdx_k_bgzf_gather(const uint8_t *d_in, long long n, const uint8_t *d_slots,
     if (n_members <= 0) return;
     hipLaunchKernelGGL(bgzf_gather_kernel, dim3(n_members), dim3(64), 0, s, d_in, n, d_slots, d_sizes, d_offsets, (const mdx_crc32::Tables *)tables, d_out);
 }
+
+// ---- the records a run counted, or those of chosen groups, laid out as an output stream on the device (--write-kept; host
+// side: mdx_gbam_write_kept).  Reduce, then scan — four launches, no block waits for another one:
+//   gbam_kept_sizes_kernel    a lane per record: its bytes in the output by the rule of mdx_kept.h (0: dropped) into sizes[], and
+//                             per tile of KEPT_TILE records the pair (records written, bytes)
+//   gbam_kept_tiles_kernel    ONE block: the exclusive scan of the tile pairs, KEPT_SCAN_ROUND tiles per round with the carry
+//                             in registers, as many rounds as there are tiles; the grand total behind the last tile's entry
+//   gbam_kept_offsets_kernel  a lane per record: the tile's own exclusive scan on top of the tile's base -> 64-bit offsets
+//   gbam_kept_gather_kernel   the records to their places
+#include "mdx_kept.h"
+namespace {
+enum { KEPT_TILE = 256, KEPT_SCAN_ROUND = 256, KEPT_WAVE_BYTES = 4096 };
+
+// the inclusive scan of one value per lane of a 256-lane block (Hillis-Steele in the LDS); every lane of the block calls it
+__device__ __forceinline__ u64 kept_block_scan(u64 v, u64 *sh) {
+    static_assert(KEPT_TILE == 256 && KEPT_SCAN_ROUND == 256, "kept_block_scan scans 256 lanes");
+    const u32 t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+#pragma unroll
+    for (u32 d = 1; d < 256u; d <<= 1) {
+        const u64 add = t >= d ? sh[t - d] : 0ull;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    const u64 r = sh[t];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_sizes_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                                   const uint16_t *__restrict__ flag, const uint16_t *__restrict__ key,
+                                                                   const u8 *__restrict__ selected, u32 n_groups, u32 n_rec,
+                                                                   u32 *__restrict__ sizes, ulonglong2 *__restrict__ tile_sum) {
+    __shared__ u64 sh_n[4], sh_b[4];
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    u32 sz = 0;
+    if (r < n_rec) {
+        sz = mdx_kept_bytes(flag[r], key ? (u32)key[r] : 0u, n_groups, selected, g32(unc + rec_off[r] - 4));
+        sizes[r] = sz;
+    }
+    // the tile's pair: within the wavefront by shuffles, the four wavefronts by lane 0
+    u64 nn = sz ? 1ull : 0ull, bb = sz;
+    for (int o = 32; o > 0; o >>= 1) {
+        nn += (u64)__shfl_down((unsigned long long)nn, o);
+        bb += (u64)__shfl_down((unsigned long long)bb, o);
+    }
+    if ((threadIdx.x & 63u) == 0) { sh_n[threadIdx.x >> 6] = nn; sh_b[threadIdx.x >> 6] = bb; }
+    __syncthreads();
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = make_ulonglong2(sh_n[0] + sh_n[1] + sh_n[2] + sh_n[3], sh_b[0] + sh_b[1] + sh_b[2] + sh_b[3]);
+}
+
+// tile_base[t] = the pairs of the tiles in front of t; tile_base[n_tiles] = the slab's total (records written, bytes)
+__global__ __launch_bounds__(KEPT_SCAN_ROUND) void gbam_kept_tiles_kernel(const ulonglong2 *__restrict__ tile_sum, u32 n_tiles,
+                                                                         ulonglong2 *__restrict__ tile_base) {
+    __shared__ u64 sh[KEPT_SCAN_ROUND];
+    u64 carry_n = 0, carry_b = 0;                   // (the same in every lane)
+    for (u32 t0 = 0; t0 < n_tiles; t0 += KEPT_SCAN_ROUND) {
+        const u32 t = t0 + threadIdx.x;
+        const ulonglong2 v = t < n_tiles ? tile_sum[t] : make_ulonglong2(0, 0);
+        const u64 in_n = kept_block_scan(v.x, sh), in_b = kept_block_scan(v.y, sh);
+        if (t < n_tiles) tile_base[t] = make_ulonglong2(carry_n + in_n - v.x, carry_b + in_b - v.y);
+        // the round's total: the last lane's inclusive value, through the LDS
+        if (threadIdx.x == KEPT_SCAN_ROUND - 1) { sh[0] = in_n; sh[1] = in_b; }
+        __syncthreads();
+        carry_n += sh[0]; carry_b += sh[1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tile_base[n_tiles] = make_ulonglong2(carry_n, carry_b);
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_offsets_kernel(const u32 *__restrict__ sizes, const ulonglong2 *__restrict__ tile_base,
+                                                                     u32 n_rec, unsigned long long *__restrict__ offsets) {
+    __shared__ u64 sh[KEPT_TILE];
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    const u64 sz = r < n_rec ? sizes[r] : 0u;
+    const u64 incl = kept_block_scan(sz, sh);
+    if (r < n_rec) offsets[r] = tile_base[blockIdx.x].y + incl - sz;
+}
+
+// `lanes` lanes (lane j of them) copy size bytes from src to dst, both of any alignment.  The bytes in front of the
+// destination's first 16-byte boundary and those behind its last one go a byte per lane; everything between goes sixteen bytes
+// per lane and step: one load of any alignment (the hardware takes an unaligned global_load_dwordx4) and one aligned store.
+// No load leaves [src, src + size) and no store leaves [dst, dst + size): the slab's last record ends where the contents of the
+// inflated buffer end, and the neighbouring bytes of the stream are another record's, written by other lanes.
+template <u32 LANES>
+__device__ __forceinline__ void kept_copy(const u8 *__restrict__ src, u8 *__restrict__ dst, u32 size, u32 j) {
+    typedef u32 v4 __attribute__((ext_vector_type(4)));
+    typedef v4 v4u __attribute__((aligned(1)));
+    u32 head = (0u - (u32)(uintptr_t)dst) & 15u;
+    if (head > size) head = size;
+    for (u32 i = j; i < head; i += LANES) dst[i] = src[i];
+    const u32 n16 = (size - head) >> 4;
+    const u8 *__restrict__ s = src + head;
+    u8 *__restrict__ d = dst + head;
+    for (u32 k = j; k < n16; k += LANES) *(v4 *)(d + 16ull * k) = *(const v4u *)(s + 16ull * k);
+    for (u32 i = head + 16u * n16 + j; i < size; i += LANES) dst[i] = src[i];
+}
+
+// Eight lanes per record, thirty-two records per block.  A wavefront's step moves 128 bytes of each of its eight records — 1 KiB,
+// each record's lanes on consecutive 16-byte pieces — which covers a short read's record (150 to 400 bytes) in two or three
+// steps.  A record of more than KEPT_WAVE_BYTES bytes (a long read: 100 kb are 150 KB) is left by its eight lanes and taken by the
+// whole wavefront afterwards, 1 KiB of the one record per step.  Every lane of the wavefront stays to the end (the ballot).
+__global__ __launch_bounds__(256) void gbam_kept_gather_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                               const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                               u32 n_rec, u8 *__restrict__ out) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 r = t >> 3, j = t & 7u;
+    const u32 sz = r < n_rec ? sizes[r] : 0u;
+    if (sz != 0u && sz <= (u32)KEPT_WAVE_BYTES) kept_copy<8u>(unc + rec_off[r] - 4, out + offsets[r], sz, j);
+    unsigned long long big = __ballot(sz > (u32)KEPT_WAVE_BYTES && j == 0u);
+    const u32 lane = threadIdx.x & 63u;
+    while (big) {
+        const int src_lane = __ffsll((long long)big) - 1;
+        big &= big - 1ull;
+        const u32 rb = (u32)__shfl((int)r, src_lane);
+        kept_copy<64u>(unc + rec_off[rb] - 4, out + offsets[rb], sizes[rb], lane);
+    }
+}
+}  // namespace
+
+int mdx_k_gbam_kept_tile() { return KEPT_TILE; }
+void mdx_k_gbam_kept_offsets(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint16_t *key, const uint8_t *selected,
+                             uint32_t n_groups, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base, unsigned long long *offsets,
+                             hipStream_t s) {
+    if (n_rec == 0) return;
+    const uint32_t n_tiles = (n_rec + KEPT_TILE - 1) / KEPT_TILE;
+    hipLaunchKernelGGL(gbam_kept_sizes_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, unc, rec_off, flag, key, selected, n_groups, n_rec, sizes,
+                       (ulonglong2 *)tile_sum);
+    hipLaunchKernelGGL(gbam_kept_tiles_kernel, dim3(1), dim3(KEPT_SCAN_ROUND), 0, s, (const ulonglong2 *)tile_sum, n_tiles, (ulonglong2 *)tile_base);
+    hipLaunchKernelGGL(gbam_kept_offsets_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, sizes, (const ulonglong2 *)tile_base, n_rec, offsets);
+}
+void mdx_k_gbam_kept_gather(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec,
+                            uint8_t *out, hipStream_t s) {
+    if (n_rec == 0) return;
+    hipLaunchKernelGGL(gbam_kept_gather_kernel, dim3((n_rec + 31) / 32), dim3(256), 0, s, unc, rec_off, sizes, offsets, n_rec, out);
+}

@@ -476,6 +476,9 @@ void mdx_k_rescale_lists(int64_t n_reads, int n_cu, int64_t *n_waves, int64_t *c
 // (mdx_capi.cpp) the device decode's arena and CRC tables, kept by the context between files
 struct mdx_ctx;
 extern "C" int mdx_ctx_minqual(const mdx_ctx *c);        // the context's --min-basequal (-1: no context)
+// the key column of a stratified context's last keyed batch (device), the flag column and n_reads of that batch, and the
+// number of batches keyed so far; returns the context's groups (0: not stratified — only *serial is written)
+extern "C" int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const uint16_t **flag, int64_t *n_reads, uint64_t *serial);
 extern "C" void mdx_ctx_scratch_give(mdx_ctx *c, void *arena, size_t cap, void *tables, void *stream, void *event);
 extern "C" void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, void **stream, void **event);
 
@@ -543,6 +546,19 @@ void mdx_k_gbam_patch_qual(uint8_t *unc, const uint32_t *rec_off, const uint32_t
 void mdx_k_gbam_out_sizes(const uint8_t *unc, const uint32_t *rec_off, const uint8_t *rescaled, uint32_t n_rec, uint32_t *sizes, hipStream_t s);
 void mdx_k_gbam_write_back(const uint8_t *unc, const uint32_t *rec_off, const unsigned long long *out_off, const uint8_t *rescaled, const float *mr,
                            uint32_t n_rec, uint8_t *out, int *clash, hipStream_t s);
+
+// ---- the counted records of a decoded slab, or those of chosen groups, laid out as an output stream on the device (mdx_gbam.hip;
+// host side: mdx_gbam_write_kept; the rule: mdx_kept.h).  mdx_k_gbam_kept_offsets: sizes[r] = the record's bytes in the stream (0:
+// dropped) and offsets[r] = their exclusive prefix sum, by three launches (tile sums, their scan by one block, offsets within
+// the tiles); key / selected may be null; tile_sum holds a pair of 64-bit words per tile of mdx_k_gbam_kept_tile() records,
+// tile_base one pair more: the last one = (records written, bytes of the stream).  mdx_k_gbam_kept_gather: the records to
+// out + offsets[r].
+int mdx_k_gbam_kept_tile();
+void mdx_k_gbam_kept_offsets(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint16_t *key, const uint8_t *selected,
+                             uint32_t n_groups, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base, unsigned long long *offsets,
+                             hipStream_t s);
+void mdx_k_gbam_kept_gather(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec,
+                            uint8_t *out, hipStream_t s);
 
 // ---- GPU-side SAM text decode (mdx_gsam.hip; host side: mdx_gsam_* in mdx_samio.cpp)
 // why a slab is given up (status[0] of the kernels; status[1] = the lowest line of the slab that gave a reason)

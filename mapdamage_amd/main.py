@@ -7,6 +7,7 @@ are out of scope: their flags are parsed, and asking for them is
 import argparse
 import dataclasses
 import logging
+import os
 import sys
 import time
 from pathlib import Path
@@ -207,6 +208,18 @@ def build_parser():
                         "stored sequence, not the query length of the CIGAR")
     g.add_argument("--max-read-length", type=_ranged(int, 0, 2**31 - 1), default=0, metavar="L",
                    help="drop the records whose SEQ field is longer than L bases (0: no upper bound)")
+    g.add_argument("--write-kept", type=Path, default=None, metavar="BAM",
+                   help="also write the records the run counts to a BAM file, in the same pass: those the flag filter 0xF04, the "
+                        "record filters and --downsample to a fraction leave, in the input's order, every record byte for byte as "
+                        "the input has it, under the input's header (no @PG line is added).  Selected, compacted and compressed on "
+                        "the device, so BAM input on the device decode path only: not SAM text, --host-decode, --gpus above 1 or "
+                        "-n N.  The tables and logs are what the run writes without the option; write_kept.tsv gives the records "
+                        "and bytes written.  Not a reference option: mapdamage/config.py has none")
+    g.add_argument("--write-groups", default=None, metavar="I[,I...]",
+                   help="with --write-kept in a run that has groups (--by-reference, --reference-groups, --regions, --region-groups, "
+                        "--by-terminal-damage, --by-pmd-score): write only the records of the groups with these indices of "
+                        "groups.tsv, for all libraries — `--by-pmd-score --pmd-thresholds 3 --write-groups 1` is what `pmdtools "
+                        "--threshold 3` would have written (default: every counted record)")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -222,6 +235,71 @@ def build_parser():
                    help="decode a BAM file in chunks of this many MiB of uncompressed records, overlapped with "
                         "the tabulation of the previous chunk (0: decode the whole file first)")
     return p
+
+
+def parse_write_groups(text):
+    """The list of --write-groups, ``I[,I...]``, as a sorted tuple of group indices: any order, no repeats.  ValueError with
+    the entry at fault for an empty entry, one that is not a decimal integer, a negative one or a repeat."""
+    groups = []
+    for entry in str(text).split(","):
+        entry = entry.strip()
+        if not entry:
+            raise ValueError("an empty entry in %r (indices of groups.tsv, separated by commas)" % str(text))
+        try:
+            index = int(entry, 10)
+        except ValueError:
+            raise ValueError("%r is not an integer (indices of groups.tsv, not group names)" % entry) from None
+        if index < 0:
+            raise ValueError("group index %d is negative" % index)
+        if index in groups:
+            raise ValueError("group index %d is listed twice" % index)
+        groups.append(index)
+    return tuple(sorted(groups))
+
+
+def check_write_groups(groups, n_groups):
+    """... against the number of groups of the run, known once the header, the BED file or the thresholds are read."""
+    for index in groups:
+        if index >= n_groups:
+            raise ValueError("--write-groups: group index %d is outside 0..%d (the run has %d groups, see groups.tsv)"
+                             % (index, n_groups - 1, n_groups))
+
+
+def _check_write_kept(parser, o):
+    """The argument errors of --write-kept / --write-groups."""
+    has_groups = bool(o.by_reference or o.reference_groups or o.regions or o.region_groups or o.by_terminal_damage
+                      or o.by_pmd_score)
+    if o.write_groups is not None:
+        if o.write_kept is None:
+            parser.error("--write-groups needs --write-kept: it chooses the groups whose records that file receives")
+        if not has_groups:
+            parser.error("--write-groups needs a run with groups: one of --by-reference, --reference-groups, --regions, "
+                         "--region-groups, --by-terminal-damage, --by-pmd-score")
+        try:
+            o.write_groups = parse_write_groups(o.write_groups)
+        except ValueError as error:
+            parser.error("--write-groups: %s" % error)
+    if o.write_kept is None:
+        return
+    if o.rescale_only or o.stats_only:
+        parser.error("--write-kept belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
+    if not o.gpu_decode:
+        parser.error("--write-kept is written by the device decode path: not with --host-decode")
+    if o.gpus > 1:
+        parser.error("--write-kept cannot be combined with --gpus %d: the ranks take alternate slabs of the input, and one "
+                     "file has one order; use --gpus 1" % o.gpus)
+    if o.downsample is not None and o.downsample >= 1:
+        parser.error("--write-kept cannot be combined with -n %d: the reservoir of a fixed number of reads is the host's and "
+                     "knows its sample at the end of the input only; a fraction (-n below 1) is drawn on the way" % int(o.downsample))
+    if not Path(o.write_kept).absolute().parent.is_dir():
+        parser.error("--write-kept %s: its directory does not exist" % o.write_kept)
+    if o.filename is not None and not is_stream(o.filename):
+        try:
+            same = os.path.samefile(o.filename, o.write_kept)
+        except OSError:
+            same = False
+        if same:
+            parser.error("--write-kept %s is the input file: the run would overwrite what it reads" % o.write_kept)
 
 
 def parse_args(argv):
@@ -277,6 +355,7 @@ def parse_args(argv):
             o.pmd_model = pmd.check_model(*model)
         except ValueError as error:
             parser.error("--by-pmd-score: %s" % error)
+    _check_write_kept(parser, o)
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -731,11 +810,71 @@ def _slab_bytes(options, world):
     return slab
 
 
+class _KeptOutput:
+    """--write-kept on the device decode path: the BAM file under a temporary name in its own directory — the input's header
+    first, then every slab's kept records as the device hands them over (``sam.GpuBamStream.write_kept``), written by the
+    writer's thread under the next slab's decode and tabulation —, moved into place by ``commit`` behind the end-of-file marker.
+    Leaving the ``with`` block any other way removes the temporary file."""
+
+    def __init__(self, options, engine, stream):
+        from .sam import BgzfWriter, bam_header_bytes
+        self.path = Path(options.write_kept)
+        self.tmp = self.path.with_name("%s.%d.tmp" % (self.path.name, os.getpid()))
+        self.groups = options.write_groups
+        self.n_groups = len(options.strata[0]) if self.groups is not None else 0
+        self.stream, self.folder = stream, options.folder
+        self.records = self.raw_bytes = 0
+        self.writer = BgzfWriter(self.tmp, engine=engine)
+        try:
+            self.writer.write(bam_header_bytes(stream.header))
+        except BaseException:
+            self._remove()
+            raise
+
+    def add(self, view):
+        """The slab's kept records: right behind ``engine.tabulate_view(view)`` — the flags are final, the key column is the
+        view's."""
+        self.writer.flush()             # (the one output array is the writer thread's until its write is done)
+        members, n, raw = self.stream.write_kept(view, self.groups, self.n_groups)
+        self.records += n
+        self.raw_bytes += raw
+        if len(members):
+            self.writer.write_members(members)
+
+    def commit(self, logger):
+        self.writer.close()             # (the queued writes, then the end-of-file marker)
+        self.writer = None
+        os.replace(self.tmp, self.path)
+        which = "all" if self.groups is None else ",".join(str(g) for g in self.groups)
+        logger.info("Wrote %d records to %s (groups: %s)", self.records, self.path, which)
+        (self.folder / "write_kept.tsv").write_text("path\tgroups\trecords\tuncompressed_bytes\n%s\t%s\t%d\t%d\n"
+                                                    % (self.path, which, self.records, self.raw_bytes))
+
+    def _remove(self):
+        if self.writer is not None:
+            try:
+                self.writer.abandon()
+            except Exception:
+                pass
+            self.writer = None
+        try:
+            self.tmp.unlink()
+        except OSError:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self._remove()          # (nothing to remove behind commit)
+
+
 def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     """--gpu-decode: the file inflated, unpacked and counted on the GPU.  Returns (tables, None), or (None, carry) when
     the path does not apply or has given up — the caller decodes on the host, which also words the errors the way the
     reference does: the whole file (carry None), or, when the device path failed on a slab it had not begun to count,
     the rest of it with the same engine (``_tabulate_on_host``'s ``carry``)."""
+    import contextlib
     from .sam import GpuBamStream, GpuDecodeUnsupported, GpuSamStream
     # a stream (stdin, a pipe) is read once: a host decoder that takes over goes on where the device path stopped, never
     # from the start
@@ -759,6 +898,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     stages.mark("engine")
     # (--by-pmd-score: the key reads the qualities beside the nibbles the packed kernel counts from)
     by_pmd = bool(getattr(options, "by_pmd_score", False))
+    # (--write-kept: BAM input, one rank — parse_args and main have seen to it)
+    write_kept = getattr(options, "write_kept", None) is not None and not sam_text
     carry = None
     try:
         engine.set_reference(ref)
@@ -773,7 +914,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         with (GpuSamStream if sam_text else GpuBamStream)(
                 engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
                 lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0 or by_pmd, min_basequal=options.minqual,
-                packed=True if by_pmd else None, record_filter=options.record_filter) as stream:
+                packed=True if by_pmd else None, record_filter=options.record_filter) as stream, \
+                (_KeptOutput(options, engine, stream) if write_kept else contextlib.nullcontext()) as kept_out:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
             slab, n_reads, n_kept = 0, 0, 0
             try:
@@ -830,6 +972,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                         logger.warning("Reads without PHRED scores found; cannot filter by --min-basequal")
                         warned_about_quals = True
                     engine.tabulate_view(view, record_base=n_reads)
+                    if kept_out is not None:
+                        kept_out.add(view)
                     if sam_stream:
                         try:
                             engine.sync()
@@ -853,6 +997,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             if error is None:
                 options.filter_counts = stream.filter_counts()
             tables = ranks.finish(engine, error)
+            if kept_out is not None:
+                kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
         engine.close()
         return tables, None
@@ -876,6 +1022,11 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         reason = str(error)
     # never silent: a regression of the device path must not show up as nothing but a slow run
     options.gpu_decode_fallbacks = getattr(options, "gpu_decode_fallbacks", 0) + 1
+    if write_kept:
+        # (no route through the host decoder: the run ends, main says why)
+        engine.close()
+        logger.warning("GPU decode path gave up: %s", reason)
+        return None, None
     if carry is None:
         engine.close()
         logger.warning("GPU decode path gave up: %s; decoding on the host (the whole file again)", reason)
@@ -998,12 +1149,22 @@ def main(argv):
                         else "stripped of line ends in HBM")
         else:
             logger.info("Reference: plain gzip FASTA, read by the host (Python reader)")
+        if options.write_kept is not None and not reader.is_bam:
+            logger.error("--write-kept needs BAM input: '%s' is SAM text, and writing BAM from parsed text is not part of the "
+                         "option (samtools view -b in front of the run)", options.filename)
+            return 1
         libraries = reader.get_libraries()
         try:
             options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
         except (ValueError, OSError) as error:
             logger.error("%s", error)
             return 1
+        if options.write_groups is not None:
+            try:
+                check_write_groups(options.write_groups, len(options.strata[0]))
+            except ValueError as error:
+                logger.error("%s", error)
+                return 1
         if options.strata is not None:
             kind = "PMD score" if options.by_pmd_score else "terminal damage" if options.by_terminal_damage else "regions" if options.regions or options.region_groups else "reference sequences"
             logger.info("Tabulating %d groups of %s x %d libraries in one pass", len(options.strata[0]), kind, len(libraries))
@@ -1031,6 +1192,10 @@ def main(argv):
         logger.info("Writing results to '%s/'", options.folder)
 
         tables, carry = _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages) if options.gpu_decode else (None, None)
+        if tables is None and options.write_kept is not None:
+            logger.error("--write-kept is written by the device decode path, which did not finish this run: nothing is "
+                         "written, and the run does not go on without its output")
+            return 1
         if tables is None:
             tables = _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry)
         fallbacks = getattr(options, "gpu_decode_fallbacks", 0)

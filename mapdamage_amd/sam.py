@@ -453,6 +453,18 @@ class BgzfWriter:
         self._out = None
         self._pool.shutdown()
 
+    def abandon(self):
+        """Close the file as it stands — no tail, no end-of-file marker, whatever the writes still queued come to: the
+        caller removes it (--write-kept on an error path)."""
+        if self._out is None:
+            return
+        self._pool.shutdown(wait=True)
+        self._pending.clear()
+        try:
+            self._out.close()
+        finally:
+            self._out = None
+
     def __enter__(self):
         return self
 
@@ -706,6 +718,50 @@ class GpuBamStream:
         if rc != 0:
             raise ValueError("%r: %s" % (str(self.path), self._error()))
         return out[:out_len.value]
+
+    def kept_bound(self):
+        """Bytes that always suffice for the members ``write_kept`` makes of the view handed out last (include/mdx.h
+        ``mdx_gbam_kept_bound``: from the view's record offsets, never a guess)."""
+        import ctypes
+        fn = self._lib.mdx_gbam_kept_bound
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        bound = ctypes.c_int64(0)
+        if fn(self._g, ctypes.byref(bound)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        return int(bound.value)
+
+    def write_kept(self, view, groups=None, n_groups=0):
+        """The records of the view ``next_view`` handed out last that the run counts — ``(flag & 0xF04) == 0`` in the flag column
+        as it stands, so behind ``set_view_flags`` — selected, compacted and compressed on the device (include/mdx.h
+        ``mdx_gbam_write_kept``): returns ``(members, n_written, raw_bytes)``, the records byte for byte as BGZF members (a uint8
+        array, valid until the next call: one output array, grown when ``kept_bound`` says so), their number and their bytes
+        before compression.  ``groups``: indices of the groups of a stratified engine (``n_groups`` of them in all) whose records
+        alone are written — behind ``DamageEngine.tabulate_view`` of this very view (MdxError -3 otherwise)."""
+        import ctypes
+        import numpy as np
+        bound = self.kept_bound()
+        out = getattr(self, "_kept_out", None)
+        if out is None or out.shape[0] < bound:
+            out = self._kept_out = np.empty(bound + bound // 8, np.uint8)
+        selected = None
+        if groups is not None:
+            selected = np.zeros(max(1, int(n_groups)), np.uint8)
+            for g in groups:
+                if not 0 <= int(g) < int(n_groups):
+                    raise ValueError("group %d is outside 0..%d" % (int(g), int(n_groups) - 1))
+                selected[int(g)] = 1
+        fn = self._lib.mdx_gbam_write_kept
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        out_len, n_written, raw_bytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        rc = fn(self._g, None if selected is None else ctypes.c_void_p(selected.ctypes.data), ctypes.c_int32(int(n_groups)),
+                ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(out.shape[0]), ctypes.byref(out_len), ctypes.byref(n_written),
+                ctypes.byref(raw_bytes))
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        return out[:out_len.value], int(n_written.value), int(raw_bytes.value)
 
     def fixups(self):
         """BGZF blocks whose guessed first record was not where the chain of the records in front of it ended (rescanned

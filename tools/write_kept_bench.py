@@ -1,0 +1,110 @@
+"""What --write-kept costs: config-3 records with qualities (8 M by default, the 10 Mb genome, qualities from a seed) written as
+one BAM, then three commands timed as cold processes, each under a time limit of its own:
+
+  plain   `python -m mapdamage_amd -i x.bam -r x.fa --no-stats ...`                                       what a run did before
+  kept    the same with `--write-kept kept.bam`                                                          every counted record
+  pmd     the same with `--by-pmd-score --pmd-thresholds 3 --write-kept pmd.bam --write-groups 1`        the top PMD group
+
+The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
+times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
+(write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost.  --parent-root DIR: a
+built checkout of the parent commit; `plain` is then also timed there, in the same alternation — a difference between the two
+beyond the spread means the option-less path has changed.  One JSON line on stdout.
+
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR]"""
+import argparse
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FILES = ("misincorporation.txt", "dnacomp.txt", "lgdistribution.txt")
+
+
+def timed(argv, limit, root):
+    t0 = time.perf_counter()
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + argv, cwd=root, env=dict(os.environ, PYTHONPATH=root),
+                       stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+    return time.perf_counter() - t0, p.returncode, p.stderr.decode(errors="replace")[-800:]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reads", type=int, default=8_000_000)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--dir", help="where the BAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
+    ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
+    ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
+    args = ap.parse_args()
+    import numpy as np
+
+    from mapdamage_amd import fasta, sam, synth
+    work = args.dir or tempfile.mkdtemp(prefix="mdx_write_kept_bench_")
+    os.makedirs(work, exist_ok=True)
+    try:
+        ref = synth.make_genome()
+        bam, fa = os.path.join(work, "x.bam"), os.path.join(work, "x.fa")
+        t0 = time.perf_counter()
+        batch = synth.config3_batch(ref, args.reads, seed=args.seed, with_qual=True)
+        sam.write_bam(bam, batch, ref.names, ref.lengths, [{"ID": "rg1", "SM": "synthetic", "LB": "lib1"}],
+                      rg_of_record=["rg1"] * args.reads)
+        fasta.write_fasta(fa, ref)
+        n_counted = int(((batch.flag & 0xF04) == 0).sum())
+        del batch
+        result = {"tool": "write_kept_bench", "reads": args.reads, "counted": n_counted, "bam_bytes": os.path.getsize(bam),
+                  "write_bam_s": round(time.perf_counter() - t0, 1), "repeats": args.repeats}
+        base = [sys.executable, "-m", "mapdamage_amd", "-i", bam, "-r", fa, "--no-stats", "--log-level", "DEBUG"]
+        legs = [("plain", ROOT, []), ("kept", ROOT, ["--write-kept", os.path.join(work, "kept.bam")]),
+                ("pmd", ROOT, ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept", os.path.join(work, "pmd.bam"), "--write-groups", "1"])]
+        if args.parent_root:
+            legs.insert(1, ("parent_plain", os.path.abspath(args.parent_root), []))
+        times = {name: [] for name, _, _ in legs}
+        status = 0
+        for _ in range(args.repeats):
+            for name, root, extra in legs:
+                t, rc, err = timed(base + ["-d", os.path.join(work, name)] + extra, args.timeout, root)
+                if rc != 0:
+                    result["error"] = "%s: exit %d %s" % (name, rc, err)
+                    status = 1
+                    break
+                times[name].append(round(t, 3))
+            if status:
+                break
+        for name, _, _ in legs:
+            ts = times[name]
+            if not ts:
+                continue
+            med = statistics.median(ts)
+            result[name] = {"wall_s": ts, "median_s": round(med, 3), "spread_s": round(max(ts) - min(ts), 3), "reads_per_s": round(args.reads / med)}
+            log = open(os.path.join(work, name, "Runtime_log.txt")).read()
+            result[name]["decode_path"] = "device" if "Decode path: device; fallbacks from the device path: 0" in log else "host decoder"
+            tsv = os.path.join(work, name, "write_kept.tsv")
+            if os.path.exists(tsv):
+                path, groups, records, raw = open(tsv).read().splitlines()[1].split("\t")
+                result[name].update(groups=groups, records_written=int(records), uncompressed_bytes=int(raw), file_bytes=os.path.getsize(path))
+        if status == 0:
+            for name in ("kept", "pmd"):
+                result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            tables = {name: [open(os.path.join(work, name, f)).read() for f in FILES] for name, _, _ in legs}
+            same = all(t == tables["plain"] for t in tables.values())
+            result["usual_tables"] = "byte-identical" if same else "MISMATCH"
+            if result["kept"]["records_written"] != n_counted:
+                result["error"] = "kept.bam holds %d records, the run counted %d" % (result["kept"]["records_written"], n_counted)
+            status = 0 if same and "error" not in result else 1
+        print(json.dumps(result))
+        return status
+    finally:
+        if not args.dir:
+            shutil.rmtree(work, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    sys.exit(main())
