@@ -336,6 +336,13 @@ int mdx_finish_allreduce(mdx_ctx *ctx, uint64_t *d_tables);
  *                      the key (a resident batch that brings its buckets: by a launch of it for the histogram alone), so a
  *                      library's bins sum to its strata's mdx_strata_kept; synchronous.  MDX_ERR_STATE without PMD strata.
  *   mdx_strata_pmd_unqualified  *n (host): how many of those records were scored without qualities (eps = 0); synchronous.
+ *   mdx_strata_pmd_keep_scores  on != 0: from the next keyed batch on the key kernel also leaves every record's score, as the
+ *                      float32 a score tag holds (mdx_gbam_write_kept_tagged: the nearest float32 to the fixed-point S, ties to
+ *                      even, times 2^-24; a record outside the reference 0.0) — a column of the context, of the batch keyed
+ *                      last.  Off (the default): no column, no store.  MDX_ERR_STATE without PMD strata.
+ *   mdx_strata_pmd_scores  out[n] (host): that column, n = the records of the batch keyed last (else MDX_ERR_ARG); synchronous.
+ *                      MDX_ERR_STATE without PMD strata, with the switch off, or when the batch tabulated last was not keyed
+ *                      (none since the switch; a resident batch that brought its buckets).
  *   mdx_strata_groups  n_groups, 0 for a context without strata
  *   mdx_strata_kept    kept[cfg.nlib] (host): the records the flag filter (reader.py:121-132) kept, per stratum, of this
  *                      context's batches since mdx_create / mdx_reset — the block's n_kept is one word for the whole run.
@@ -361,6 +368,8 @@ int mdx_set_strata_pmd(mdx_ctx *ctx, int32_t n_thresholds, const int64_t *thresh
                        int32_t single_stranded);
 int mdx_strata_pmd_histogram(mdx_ctx *ctx, uint64_t *hist /* n_libraries x 82 */);
 int mdx_strata_pmd_unqualified(mdx_ctx *ctx, uint64_t *n);
+int mdx_strata_pmd_keep_scores(mdx_ctx *ctx, int32_t on);
+int mdx_strata_pmd_scores(mdx_ctx *ctx, float *out, int64_t n);
 int mdx_strata_groups(const mdx_ctx *ctx);
 int mdx_strata_kept(mdx_ctx *ctx, uint64_t *kept);
 int64_t mdx_merged_words(const mdx_ctx *ctx);
@@ -610,6 +619,25 @@ int mdx_gbam_record_name(struct mdx_gbam *g, int64_t index, char *buf, int32_t c
 int mdx_gbam_kept_bound(struct mdx_gbam *g, int64_t *bytes);
 int mdx_gbam_write_kept(struct mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
                         int64_t *n_written, int64_t *raw_bytes);
+/* ... with what the run computed per record appended to every written record as tags (--tag-group, --tag-pmd-score; the rule
+ * is csrc/mdx_kept_tags.h):
+ *   mdx_gbam_write_kept_tagged  mdx_gbam_write_kept, and behind the last tag byte of every written record first
+ *                           group_tag 'S' <uint16>: its group, key % n_groups, the index of groups.tsv — then score_tag 'f'
+ *                           <float32>: its PMD score, the fixed-point score rounded to the nearest float32 (ties to even) times
+ *                           2^-24; block_size grows by 5, 7 or 12 and no other byte changes.  group_tag / score_tag: two
+ *                           characters [A-Za-z][A-Za-z0-9] each (no terminator is read), different from one another, or NULL:
+ *                           no such tag — both NULL is mdx_gbam_write_kept.  Either tag takes the context's key column as a
+ *                           selection does: a stratified context of n_groups groups (MDX_ERR_ARG), the key column of this very
+ *                           view (MDX_ERR_STATE), and no record with key 0xFFFF is written.  The score tag needs the score
+ *                           column of the same keyed batch too: PMD strata with mdx_strata_pmd_keep_scores (MDX_ERR_STATE).
+ *                           A written record that has a tag of one of the two names already: MDX_ERR_BAD_READ, *clash = the lowest
+ *                           such index of the slab (mdx_gbam_record_name gives its name), nothing of the slab is written; else
+ *                           *clash = -1 (clash may be NULL).  A tag region that cannot be followed (an unknown type, a B array
+ *                           past the record's end) ends the search without a clash; dropped records are not searched.
+ *   mdx_gbam_kept_bound_tagged  mdx_gbam_kept_bound with tag_bytes (0, 5, 7 or 12) more for every record of the view. */
+int mdx_gbam_kept_bound_tagged(struct mdx_gbam *g, int32_t tag_bytes, int64_t *bytes);
+int mdx_gbam_write_kept_tagged(struct mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, const char *group_tag, const char *score_tag,
+                               uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *n_written, int64_t *raw_bytes, int64_t *clash);
 /* mdx_mr_round: float("%.5f" % x) of rescale.py:275-276 for n MR sums (mr_raw of the rescale calls) on `threads` host threads —
  * the value printed with five decimals, read back, and narrowed to the 32 bits of an MR:f tag; NaN (a record written back
  * unchanged) gives 0. */

@@ -7,6 +7,7 @@
 #include "mdx_internal.h"
 #endif
 #include "mdx_filter.h"
+#include "mdx_kept_tags.h"
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
@@ -2682,38 +2683,61 @@ int mdx_gbam_record_name(mdx_gbam *g, int64_t index, char *buf, int32_t cap) {
 }
 
 // --write-kept (include/mdx.h): the capacity that suffices for mdx_gbam_write_kept on the view handed out last — its records'
-// inflated bytes (every one of them kept, stored members: 26 bytes each and a few for the stored blocks' headers) —
-int mdx_gbam_kept_bound(mdx_gbam *g, int64_t *bytes) {
-    if (!g || !bytes) return MDX_ERR_ARG;
-    const int64_t b = (int64_t)g->view_rec_bytes;
+// inflated bytes (every one of them kept, stored members: 26 bytes each and a few for the stored blocks' headers) —, with
+// tag_bytes more for every record of the view where tags are appended (mdx_gbam_write_kept_tagged: 5, 7 or 12)
+int mdx_gbam_kept_bound_tagged(mdx_gbam *g, int32_t tag_bytes, int64_t *bytes) {
+    if (!g || !bytes || tag_bytes < 0 || tag_bytes > (int32_t)(MDX_KEPT_GROUP_TAG_BYTES + MDX_KEPT_SCORE_TAG_BYTES)) return MDX_ERR_ARG;
+    const int64_t b = (int64_t)g->view_rec_bytes + (int64_t)tag_bytes * g->view_reads;
     *bytes = b + 64 * (b / 0xFF00) + 64;
     return MDX_OK;
 }
+int mdx_gbam_kept_bound(mdx_gbam *g, int64_t *bytes) { return mdx_gbam_kept_bound_tagged(g, 0, bytes); }
 
 // ... and the records the run counted (or those of the chosen groups among them) as BGZF members: sizes by the rule of
 // mdx_kept.h and their prefix sum on the device, one copy of sixteen bytes back (records written, bytes of the stream), the
 // records gathered into the handle's stream buffer, that stream through the device's BGZF writer.  On the context's stream,
 // behind the tabulation launch of the view; nothing is allocated unless a slab needs more than any slab before it.
-int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
-                        int64_t *n_written, int64_t *raw_bytes) {
+// With tags (mdx_kept_tags.h): the tagged forms of the sizes and gather kernels, the key kernel's columns of this very view,
+// and one word more in the copy back: the lowest written record that has such a tag already (nothing is gathered then).
+int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, const char *group_tag, const char *score_tag,
+                               uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *n_written, int64_t *raw_bytes, int64_t *clash) {
     if (!g || !out_len || !n_written || !raw_bytes || out_cap < 0 || (out_cap > 0 && !out)) return MDX_ERR_ARG;
     *out_len = 0; *n_written = 0; *raw_bytes = 0;
+    if (clash) *clash = -1;
+    const char *const fn = group_tag || score_tag ? "mdx_gbam_write_kept_tagged: " : "mdx_gbam_write_kept: ";
     try {
+        const bool tagged = group_tag || score_tag;
+        auto well_formed = [](const char *t) {
+            return !t || ((((t[0] | 0x20) >= 'a' && (t[0] | 0x20) <= 'z')) && (((t[1] | 0x20) >= 'a' && (t[1] | 0x20) <= 'z') || (t[1] >= '0' && t[1] <= '9')));
+        };
+        if (!well_formed(group_tag) || !well_formed(score_tag)) { g->error = std::string(fn) + "a tag is two characters, [A-Za-z][A-Za-z0-9]"; return MDX_ERR_ARG; }
+        if (group_tag && score_tag && group_tag[0] == score_tag[0] && group_tag[1] == score_tag[1]) {
+            g->error = std::string(fn) + "the group tag and the score tag have the same name";
+            return MDX_ERR_ARG;
+        }
         const uint16_t *d_key = nullptr;
-        if (group_selected) {
+        const float *d_score = nullptr;
+        if (group_selected || tagged) {
             const uint16_t *key_flag = nullptr;
             int64_t key_n = 0;
-            uint64_t serial = 0;
+            uint64_t serial = 0, score_serial = 0;
             const int ctx_groups = mdx_ctx_strata_key(g->ctx, &d_key, &key_flag, &key_n, &serial);
-            if (ctx_groups <= 0) { g->error = "mdx_gbam_write_kept: a selection of groups on a context without strata"; return MDX_ERR_ARG; }
+            if (ctx_groups <= 0) { g->error = std::string(fn) + (group_selected ? "a selection of groups" : "tags") + " on a context without strata"; return MDX_ERR_ARG; }
             if (n_groups != ctx_groups) {
-                g->error = "mdx_gbam_write_kept: n_groups " + std::to_string(n_groups) + ", the context has " + std::to_string(ctx_groups) + " groups";
+                g->error = fn + ("n_groups " + std::to_string(n_groups)) + ", the context has " + std::to_string(ctx_groups) + " groups";
                 return MDX_ERR_ARG;
             }
             // (an empty view is keyed by nobody: nothing to write, nothing to check)
             if (g->view_reads > 0 && (serial == g->view_key_serial || !d_key || key_flag != g->last_view.flag || key_n != g->view_reads)) {
-                g->error = "mdx_gbam_write_kept: the context's key column is not that of this view (tabulate the view first, and nothing else in between)";
+                g->error = std::string(fn) + "the context's key column is not that of this view (tabulate the view first, and nothing else in between)";
                 return MDX_ERR_STATE;
+            }
+            if (score_tag && g->view_reads > 0) {
+                d_score = mdx_ctx_strata_scores(g->ctx, &score_serial);
+                if (!d_score || score_serial != serial) {
+                    g->error = std::string(fn) + "the context has no score column of this view (PMD strata with mdx_strata_pmd_keep_scores, before the view is tabulated)";
+                    return MDX_ERR_STATE;
+                }
             }
         }
         const int64_t n = g->view_reads;
@@ -2722,35 +2746,63 @@ int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_gr
         if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
         hipStream_t st = g->stream;
         mdx_gbam::Slab &s = g->slab[g->view_slab];
+        MdxKeptTags tg{};
+        tg.group_name = group_tag ? MDX_TAG_NAME(group_tag[0], group_tag[1]) : MDX_TAG_NONE;
+        tg.score_name = score_tag ? MDX_TAG_NAME(score_tag[0], score_tag[1]) : MDX_TAG_NONE;
+        tg.bytes = (group_tag ? MDX_KEPT_GROUP_TAG_BYTES : 0u) + (score_tag ? MDX_KEPT_SCORE_TAG_BYTES : 0u);
+        tg.n_groups = (uint32_t)n_groups; tg.key = d_key; tg.score = d_score;
+        const size_t stream_bytes = g->view_rec_bytes + (size_t)tg.bytes * (size_t)n;
         const size_t n_tiles = ((size_t)n + (size_t)mdx_k_gbam_kept_tile() - 1) / (size_t)mdx_k_gbam_kept_tile();
-        // (tile sums, and the tile bases with the total behind them: 16 bytes each)
+        // (tile sums, and the tile bases with the total behind them: 16 bytes each; behind the total the word of the clash)
         if (!g->reserve(g->kept_sizes, (size_t)n * 4) || !g->reserve(g->kept_off, (size_t)n * 8) ||
-            !g->reserve(g->kept_tiles, (2 * n_tiles + 1) * 16) || !g->reserve(g->kept_stream, g->view_rec_bytes + 64) ||
+            !g->reserve(g->kept_tiles, (2 * n_tiles + 2) * 16) || !g->reserve(g->kept_stream, stream_bytes + 64) ||
             (group_selected && !g->reserve(g->kept_sel, (size_t)n_groups))) return MDX_ERR_HIP;
         int rc = MDX_OK;
-        auto ok = [&](hipError_t e) { if (e != hipSuccess) { rc = MDX_ERR_HIP; g->error = std::string("mdx_gbam_write_kept: ") + hipGetErrorString(e); (void)hipGetLastError(); } return e == hipSuccess; };
+        auto ok = [&](hipError_t e) { if (e != hipSuccess) { rc = MDX_ERR_HIP; g->error = std::string(fn) + hipGetErrorString(e); (void)hipGetLastError(); } return e == hipSuccess; };
         if (group_selected && !ok(hipMemcpyAsync(g->kept_sel.p, group_selected, (size_t)n_groups, hipMemcpyHostToDevice, st))) return rc;
         char *tiles = (char *)g->kept_tiles.p;
         void *tile_sum = tiles, *tile_base = tiles + n_tiles * 16;
-        mdx_k_gbam_kept_offsets((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint16_t *)s.flag.p, group_selected ? d_key : nullptr,
-                                group_selected ? (const uint8_t *)g->kept_sel.p : nullptr, (uint32_t)(group_selected ? n_groups : 0), (uint32_t)n,
-                                (uint32_t *)g->kept_sizes.p, tile_sum, tile_base, (unsigned long long *)g->kept_off.p, st);
-        unsigned long long total[2] = {0, 0};
-        if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(total, (char *)tile_base + n_tiles * 16, 16, hipMemcpyDeviceToHost, st)) ||
+        char *d_total = (char *)tile_base + n_tiles * 16;
+        const uint8_t *d_sel = group_selected ? (const uint8_t *)g->kept_sel.p : nullptr;
+        if (tagged) {
+            if (!ok(hipMemsetAsync(d_total + 16, 0xFF, 16, st))) return rc;
+            mdx_k_gbam_kept_offsets_tagged((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint16_t *)s.flag.p, d_sel, tg, (uint32_t)n,
+                                           (uint32_t *)g->kept_sizes.p, tile_sum, tile_base, (unsigned long long *)g->kept_off.p,
+                                           (uint32_t *)(d_total + 16), st);
+        } else
+            mdx_k_gbam_kept_offsets((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint16_t *)s.flag.p, group_selected ? d_key : nullptr,
+                                    d_sel, (uint32_t)(group_selected ? n_groups : 0), (uint32_t)n,
+                                    (uint32_t *)g->kept_sizes.p, tile_sum, tile_base, (unsigned long long *)g->kept_off.p, st);
+        unsigned long long total[4] = {0, 0, ~0ull, ~0ull};
+        if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(total, d_total, tagged ? 32 : 16, hipMemcpyDeviceToHost, st)) ||
             !ok(hipStreamSynchronize(st))) return rc;
-        if (total[1] > (unsigned long long)g->view_rec_bytes) { g->error = "mdx_gbam_write_kept: the kept records are larger than the slab that holds them"; return MDX_ERR_ARG; }
+        if (total[1] > (unsigned long long)stream_bytes) { g->error = std::string(fn) + "the kept records are larger than the slab that holds them"; return MDX_ERR_ARG; }
+        if ((uint32_t)total[2] != 0xFFFFFFFFu) {
+            const int64_t at = (int64_t)(uint32_t)total[2];
+            if (clash) *clash = at;
+            g->error = "record " + std::to_string(at) + " of the slab is to be written and has a tag named like one to be added already";
+            return MDX_ERR_BAD_READ;
+        }
         if (total[0] == 0) return MDX_OK;
-        mdx_k_gbam_kept_gather((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
-                               (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, st);
+        if (tagged)
+            mdx_k_gbam_kept_gather_tagged((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
+                                          (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, tg, st);
+        else
+            mdx_k_gbam_kept_gather((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
+                                   (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, st);
         if (!ok(hipGetLastError())) return rc;
         rc = bgzf_deflate_impl(st, g->device, nullptr, (const uint8_t *)g->kept_stream.p, (int64_t)total[1], out, out_cap, out_len);
-        if (rc != MDX_OK) { g->error = "mdx_gbam_write_kept: the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
+        if (rc != MDX_OK) { g->error = std::string(fn) + "the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
         *n_written = (int64_t)total[0]; *raw_bytes = (int64_t)total[1];
         return MDX_OK;
     } catch (const std::exception &e) {
-        g->error = std::string("mdx_gbam_write_kept: ") + e.what();
+        g->error = std::string(fn) + e.what();
         return MDX_ERR_ARG;
     }
+}
+int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                        int64_t *n_written, int64_t *raw_bytes) {
+    return mdx_gbam_write_kept_tagged(g, group_selected, n_groups, nullptr, nullptr, out, out_cap, out_len, n_written, raw_bytes, nullptr);
 }
 
 // One call per slab of a --rescale-only pass on the device (rescale.py:285-365): the view mdx_gbam_next handed out last (it

@@ -175,6 +175,12 @@ struct mdx_ctx {
     const uint16_t *strata_key_flag = nullptr;   // ... the flag column and n_reads of the batch it was made for (mdx_gbam_write_kept
     int64_t strata_key_n = 0;                    // writes chosen groups of the view it was handed only behind that view's launch)
     uint64_t strata_key_serial = 0;              // ... and how many batches have been keyed so far
+    // (mdx_strata_pmd_keep_scores) the PMD key kernel also leaves every record's score, as the float of a score tag: the column
+    // of the batch keyed last, and the strata_key_serial it belongs to (0: none — nothing keyed since the switch, or the last
+    // batch brought its buckets and was not keyed)
+    bool pmd_keep_scores = false;
+    DevBuf pmd_scores;
+    uint64_t pmd_scores_serial = 0;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -394,6 +400,7 @@ void mdx_destroy(mdx_ctx *c) {
     c->libsort.release();
     c->libsort_scratch.release();
     c->strata_key.release();
+    c->pmd_scores.release();
     c->ml_partials.release();
     c->rs_part.release();
     c->rs_lists.release();
@@ -573,7 +580,7 @@ static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, i
 // stratum (count) and into the score histogram (hist).
 // (MDX_PMD_LANE=1 in the environment: the trivial kernel, a lane per record; MDX_PMD_NO_LDS=1: the cooperative kernel with every
 // term read from global memory — for A/B runs, read at every call)
-static int pmd_key(mdx_ctx *c, const mdx_batch *b, uint16_t *key, bool count, bool hist) {
+static int pmd_key(mdx_ctx *c, const mdx_batch *b, uint16_t *key, float *score, bool count, bool hist) {
     if (!c->d_ref) return fail(c, MDX_ERR_STATE, "PMD strata (mdx_set_strata_pmd) read the reference: mdx_set_reference has not been called");
     const char *e = getenv("MDX_PMD_LANE"), *e2 = getenv("MDX_PMD_NO_LDS");
     const int form = e && *e && *e != '0' ? 1 : e2 && *e2 && *e2 != '0' ? 2 : 0;
@@ -588,7 +595,7 @@ static int pmd_key(mdx_ctx *c, const mdx_batch *b, uint16_t *key, bool count, bo
     k.n_thresholds = c->pmd_n_thresholds; k.single_stranded = c->pmd_single_stranded;
     k.terms = c->d_pmd_terms;
     for (int t = 0; t < c->pmd_n_thresholds; t++) k.thresholds[t] = c->pmd_thresholds[t];
-    mdx_k_strata_pmd_key(k, key, count ? c->d_strata_kept : nullptr, hist ? c->d_pmd_hist : nullptr, form, c->stream);
+    mdx_k_strata_pmd_key(k, key, score, count ? c->d_strata_kept : nullptr, hist ? c->d_pmd_hist : nullptr, form, c->stream);
     HIP_TRY(c, hipGetLastError());
     return MDX_OK;
 }
@@ -597,8 +604,12 @@ static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool coun
     *out = *b;
     if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
     HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
+    bool scored = false;
     if (c->pmd_n_thresholds > 0) {
-        const int rc = pmd_key(c, b, (uint16_t *)c->strata_key.p, count, count);
+        // (mdx_strata_pmd_keep_scores: the scores of this batch beside its keys)
+        if (c->pmd_keep_scores) HIP_TRY(c, c->pmd_scores.reserve((size_t)b->n_reads * 4 + 64));
+        scored = c->pmd_keep_scores;
+        const int rc = pmd_key(c, b, (uint16_t *)c->strata_key.p, scored ? (float *)c->pmd_scores.p : nullptr, count, count);
         if (rc != MDX_OK) return rc;
     } else if (c->damage_positions > 0) {
         // (the key reads the batch as the caller brings it — under --min-basequal the mask from the nibbles of a MDX_SEQ_4BITQ
@@ -626,6 +637,7 @@ static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool coun
     HIP_TRY(c, hipGetLastError());
     out->lib = (const uint16_t *)c->strata_key.p;
     c->strata_key_flag = b->flag; c->strata_key_n = b->n_reads; c->strata_key_serial++;
+    c->pmd_scores_serial = scored ? c->strata_key_serial : 0;
     return MDX_OK;
 }
 
@@ -785,8 +797,9 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
         } else if (c->pmd_n_thresholds > 0) {
             // (a batch that brings its buckets is not keyed again — their sizes are the kept counts —, but its scores are not
             // in the histogram yet: the key kernel over the batch's own columns, for the histogram alone)
-            rc = pmd_key(c, b_in, nullptr, false, true);
+            rc = pmd_key(c, b_in, nullptr, nullptr, false, true);
             if (rc != MDX_OK) return rc;
+            c->pmd_scores_serial = 0;   // (the score column is another batch's)
         }
     }
     c->counted = true;
@@ -1463,6 +1476,28 @@ int mdx_set_strata_pmd(mdx_ctx *c, int32_t n_thresholds, const int64_t *threshol
     return MDX_OK;
 }
 
+int mdx_strata_pmd_keep_scores(mdx_ctx *c, int32_t on) {
+    if (!c) return MDX_ERR_ARG;
+    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_keep_scores: the context has no PMD strata (mdx_set_strata_pmd)");
+    c->pmd_keep_scores = on != 0;
+    c->pmd_scores_serial = 0;
+    return MDX_OK;
+}
+
+int mdx_strata_pmd_scores(mdx_ctx *c, float *out, int64_t n) {
+    if (!c || n < 0 || (n > 0 && !out)) return MDX_ERR_ARG;
+    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the context has no PMD strata (mdx_set_strata_pmd)");
+    if (!c->pmd_keep_scores) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the scores are not kept (mdx_strata_pmd_keep_scores)");
+    if (c->pmd_scores_serial == 0 || c->pmd_scores_serial != c->strata_key_serial)
+        return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the batch tabulated last was not keyed (none yet, or a resident batch that brought its buckets)");
+    if (n != c->strata_key_n)
+        return fail(c, MDX_ERR_ARG, "strata_pmd_scores: n " + std::to_string(n) + ", the batch keyed last has " + std::to_string(c->strata_key_n) + " records");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n > 0) HIP_TRY(c, hipMemcpy(out, c->pmd_scores.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
 int mdx_strata_pmd_histogram(mdx_ctx *c, uint64_t *hist) {
     if (!c || !hist) return MDX_ERR_ARG;
     if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_histogram: the context has no PMD strata (mdx_set_strata_pmd)");
@@ -1588,6 +1623,11 @@ int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const uint16_t **
     if (flag) *flag = c->strata_key_flag;
     if (n_reads) *n_reads = c->strata_key_n;
     return c->n_groups;
+}
+
+const float *mdx_ctx_strata_scores(const mdx_ctx *c, uint64_t *serial) {
+    if (serial) *serial = c ? c->pmd_scores_serial : 0;
+    return c && c->pmd_scores_serial != 0 ? (const float *)c->pmd_scores.p : nullptr;
 }
 
 int mdx_ctx_stream(mdx_ctx *c, void **stream, int *device) {

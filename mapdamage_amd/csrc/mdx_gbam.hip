@@ -18,6 +18,7 @@
 #include "mdx_deflate.h"
 #include "mdx_inflate.h"
 #include "mdx_internal.h"
+#include "mdx_kept_tags.h"
 
 namespace {
 
@@ -482,25 +483,8 @@ __global__ void gbam_write_back_kernel(const u8 *__restrict__ unc, const u32 *__
     u8 *t7 = o + 4 + bs;
     const u32 fb = __float_as_uint(mr[r]);
     t7[0] = 'M'; t7[1] = 'R'; t7[2] = 'f'; t7[3] = (u8)fb; t7[4] = (u8)(fb >> 8); t7[5] = (u8)(fb >> 16); t7[6] = (u8)(fb >> 24);
-    // an MR tag among the record's own?
-    const u32 l_name = p[8], n_cig = g16(p + 12), l_seq = g32(p + 16);
-    const u8 *q = p + 32 + l_name + 4u * n_cig + (l_seq + 1) / 2 + l_seq, *end = p + bs;
-    while (q + 3 <= end) {
-        const u32 t0 = q[0], t1 = q[1], ty = q[2];
-        if (t0 == 'M' && t1 == 'R') { atomicMin(clash, (int)r); break; }
-        q += 3;
-        if (ty == 'Z' || ty == 'H') { while (q < end && *q) q++; q++; }
-        else if (ty == 'A' || ty == 'c' || ty == 'C') q += 1;
-        else if (ty == 's' || ty == 'S') q += 2;
-        else if (ty == 'i' || ty == 'I' || ty == 'f') q += 4;
-        else if (ty == 'B') {
-            if (q + 5 > end) break;
-            const u32 sub = q[0], cntb = g32(q + 1);
-            const u32 w = (sub == 'c' || sub == 'C') ? 1u : ((sub == 's' || sub == 'S') ? 2u : 4u);
-            if ((u64)cntb * w > (u64)(end - q)) break;
-            q += 5 + cntb * w;
-        } else break;
-    }
+    // an MR tag among the record's own?  (the walk: mdx_kept_tags.h)
+    if (mdx_tags_have(p, mdx_record_tags_at(p), bs, MDX_TAG_NAME('M', 'R'), MDX_TAG_NONE)) atomicMin(clash, (int)r);
 }
 }  // namespace
 void mdx_k_gbam_patch_qual(uint8_t *unc, const uint32_t *rec_off, const uint32_t *seq_off, uint32_t n_rec, const unsigned long long *patch,
@@ -540,6 +524,8 @@ void mdx_k_bgzf_gather(const uint8_t *d_in, long long n, const uint8_t *d_slots,
 //                             in registers, as many rounds as there are tiles; the grand total behind the last tile's entry
 //   gbam_kept_offsets_kernel  a lane per record: the tile's own exclusive scan on top of the tile's base -> 64-bit offsets
 //   gbam_kept_gather_kernel   the records to their places
+// With tags behind every written record (mdx_gbam_write_kept_tagged; the rule: mdx_kept_tags.h) the first and the last launch
+// run in their tagged forms, gbam_kept_sizes_tagged_kernel and gbam_kept_gather_tagged_kernel; the two between are the same.
 #include "mdx_kept.h"
 namespace {
 enum { KEPT_TILE = 256, KEPT_SCAN_ROUND = 256, KEPT_WAVE_BYTES = 4096 };
@@ -562,18 +548,9 @@ __device__ __forceinline__ u64 kept_block_scan(u64 v, u64 *sh) {
     return r;
 }
 
-__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_sizes_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
-                                                                   const uint16_t *__restrict__ flag, const uint16_t *__restrict__ key,
-                                                                   const u8 *__restrict__ selected, u32 n_groups, u32 n_rec,
-                                                                   u32 *__restrict__ sizes, ulonglong2 *__restrict__ tile_sum) {
+// the tile's pair (records written, bytes) of one size per lane: within the wavefront by shuffles, the four wavefronts by lane 0
+__device__ __forceinline__ void kept_tile_pair(u32 sz, ulonglong2 *__restrict__ tile_sum) {
     __shared__ u64 sh_n[4], sh_b[4];
-    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
-    u32 sz = 0;
-    if (r < n_rec) {
-        sz = mdx_kept_bytes(flag[r], key ? (u32)key[r] : 0u, n_groups, selected, g32(unc + rec_off[r] - 4));
-        sizes[r] = sz;
-    }
-    // the tile's pair: within the wavefront by shuffles, the four wavefronts by lane 0
     u64 nn = sz ? 1ull : 0ull, bb = sz;
     for (int o = 32; o > 0; o >>= 1) {
         nn += (u64)__shfl_down((unsigned long long)nn, o);
@@ -582,6 +559,40 @@ __global__ __launch_bounds__(KEPT_TILE) void gbam_kept_sizes_kernel(const u8 *__
     if ((threadIdx.x & 63u) == 0) { sh_n[threadIdx.x >> 6] = nn; sh_b[threadIdx.x >> 6] = bb; }
     __syncthreads();
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = make_ulonglong2(sh_n[0] + sh_n[1] + sh_n[2] + sh_n[3], sh_b[0] + sh_b[1] + sh_b[2] + sh_b[3]);
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_sizes_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                                   const uint16_t *__restrict__ flag, const uint16_t *__restrict__ key,
+                                                                   const u8 *__restrict__ selected, u32 n_groups, u32 n_rec,
+                                                                   u32 *__restrict__ sizes, ulonglong2 *__restrict__ tile_sum) {
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    u32 sz = 0;
+    if (r < n_rec) {
+        sz = mdx_kept_bytes(flag[r], key ? (u32)key[r] : 0u, n_groups, selected, g32(unc + rec_off[r] - 4));
+        sizes[r] = sz;
+    }
+    kept_tile_pair(sz, tile_sum);
+}
+
+// (the tags of --tag-group / --tag-pmd-score: MdxKeptTags, mdx_internal.h)
+typedef MdxKeptTags KeptTags;
+
+// ... the sizes with tg.bytes more for every written record (key: never null here), and the lane of a written record walks the
+// record's own tags for one of the two names: the lowest such record of the slab into *clash (0xFFFFFFFF: none)
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_sizes_tagged_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                                          const uint16_t *__restrict__ flag, const u8 *__restrict__ selected,
+                                                                          KeptTags tg, u32 n_rec, u32 *__restrict__ sizes,
+                                                                          ulonglong2 *__restrict__ tile_sum, u32 *__restrict__ clash) {
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    u32 sz = 0;
+    if (r < n_rec) {
+        const u8 *__restrict__ p = unc + rec_off[r];
+        const u32 bs = g32(p - 4);
+        sz = mdx_kept_tagged_bytes(flag[r], (u32)tg.key[r], tg.n_groups, selected, bs, tg.bytes);
+        sizes[r] = sz;
+        if (sz != 0u && mdx_tags_have(p, mdx_record_tags_at(p), bs, tg.group_name, tg.score_name)) atomicMin(clash, r);
+    }
+    kept_tile_pair(sz, tile_sum);
 }
 
 // tile_base[t] = the pairs of the tiles in front of t; tile_base[n_tiles] = the slab's total (records written, bytes)
@@ -631,25 +642,61 @@ __device__ __forceinline__ void kept_copy(const u8 *__restrict__ src, u8 *__rest
     for (u32 i = head + 16u * n16 + j; i < size; i += LANES) dst[i] = src[i];
 }
 
+// A record of sz bytes of the output by `lanes` lanes.  Untagged: its bytes as they stand.  TAGGED: the block_size bytes
+// behind its block_size field go the same wide way, from src + 4 to dst + 4; lane 0 writes the four bytes of the new block_size
+// in front of them and the 5, 7 or 12 tag bytes behind them, a byte per store.  The three ranges are disjoint and fill
+// [dst, dst + sz): no store leaves it, no byte has two writers, and kept_copy's aligned stores lie inside the middle range.
+template <bool TAGGED, u32 LANES>
+__device__ __forceinline__ void kept_record(const u8 *__restrict__ src, u8 *__restrict__ dst, u32 sz, u32 j, u32 r, const KeptTags &tg) {
+    if (!TAGGED) { kept_copy<LANES>(src, dst, sz, j); return; }
+    const u32 bs = sz - 4u - tg.bytes;               // (the record's own block_size: sizes[] is bs + 4 + tg.bytes)
+    kept_copy<LANES>(src + 4, dst + 4, bs, j);
+    if (j != 0u) return;
+    const u32 nbs = bs + tg.bytes;
+    dst[0] = (u8)nbs; dst[1] = (u8)(nbs >> 8); dst[2] = (u8)(nbs >> 16); dst[3] = (u8)(nbs >> 24);
+    u8 *__restrict__ t = dst + 4 + bs;
+    if (tg.group_name != MDX_TAG_NONE) {
+        const u32 g = (u32)tg.key[r] % tg.n_groups;
+        t[0] = (u8)tg.group_name; t[1] = (u8)(tg.group_name >> 8); t[2] = 'S'; t[3] = (u8)g; t[4] = (u8)(g >> 8);
+        t += MDX_KEPT_GROUP_TAG_BYTES;
+    }
+    if (tg.score_name != MDX_TAG_NONE) {
+        const u32 fb = __float_as_uint(tg.score[r]);
+        t[0] = (u8)tg.score_name; t[1] = (u8)(tg.score_name >> 8); t[2] = 'f';
+        t[3] = (u8)fb; t[4] = (u8)(fb >> 8); t[5] = (u8)(fb >> 16); t[6] = (u8)(fb >> 24);
+    }
+}
+
 // Eight lanes per record, thirty-two records per block.  A wavefront's step moves 128 bytes of each of its eight records — 1 KiB,
 // each record's lanes on consecutive 16-byte pieces — which covers a short read's record (150 to 400 bytes) in two or three
 // steps.  A record of more than KEPT_WAVE_BYTES bytes (a long read: 100 kb are 150 KB) is left by its eight lanes and taken by the
 // whole wavefront afterwards, 1 KiB of the one record per step.  Every lane of the wavefront stays to the end (the ballot).
-__global__ __launch_bounds__(256) void gbam_kept_gather_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
-                                                               const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
-                                                               u32 n_rec, u8 *__restrict__ out) {
+// (sizes[] are those of the output: a tagged record's threshold is on its bytes with the tags)
+template <bool TAGGED>
+__device__ __forceinline__ void kept_gather(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off, const u32 *__restrict__ sizes,
+                                            const unsigned long long *__restrict__ offsets, u32 n_rec, u8 *__restrict__ out, const KeptTags &tg) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 r = t >> 3, j = t & 7u;
     const u32 sz = r < n_rec ? sizes[r] : 0u;
-    if (sz != 0u && sz <= (u32)KEPT_WAVE_BYTES) kept_copy<8u>(unc + rec_off[r] - 4, out + offsets[r], sz, j);
+    if (sz != 0u && sz <= (u32)KEPT_WAVE_BYTES) kept_record<TAGGED, 8u>(unc + rec_off[r] - 4, out + offsets[r], sz, j, r, tg);
     unsigned long long big = __ballot(sz > (u32)KEPT_WAVE_BYTES && j == 0u);
     const u32 lane = threadIdx.x & 63u;
     while (big) {
         const int src_lane = __ffsll((long long)big) - 1;
         big &= big - 1ull;
         const u32 rb = (u32)__shfl((int)r, src_lane);
-        kept_copy<64u>(unc + rec_off[rb] - 4, out + offsets[rb], sizes[rb], lane);
+        kept_record<TAGGED, 64u>(unc + rec_off[rb] - 4, out + offsets[rb], sizes[rb], lane, rb, tg);
     }
+}
+__global__ __launch_bounds__(256) void gbam_kept_gather_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                               const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                               u32 n_rec, u8 *__restrict__ out) {
+    kept_gather<false>(unc, rec_off, sizes, offsets, n_rec, out, KeptTags{});
+}
+__global__ __launch_bounds__(256) void gbam_kept_gather_tagged_kernel(const u8 *__restrict__ unc, const u32 *__restrict__ rec_off,
+                                                                      const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                                      u32 n_rec, u8 *__restrict__ out, KeptTags tg) {
+    kept_gather<true>(unc, rec_off, sizes, offsets, n_rec, out, tg);
 }
 }  // namespace
 
@@ -668,4 +715,19 @@ void mdx_k_gbam_kept_gather(const uint8_t *unc, const uint32_t *rec_off, const u
                             uint8_t *out, hipStream_t s) {
     if (n_rec == 0) return;
     hipLaunchKernelGGL(gbam_kept_gather_kernel, dim3((n_rec + 31) / 32), dim3(256), 0, s, unc, rec_off, sizes, offsets, n_rec, out);
+}
+void mdx_k_gbam_kept_offsets_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint8_t *selected,
+                                    const MdxKeptTags &tg, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base,
+                                    unsigned long long *offsets, uint32_t *clash, hipStream_t s) {
+    if (n_rec == 0) return;
+    const uint32_t n_tiles = (n_rec + KEPT_TILE - 1) / KEPT_TILE;
+    hipLaunchKernelGGL(gbam_kept_sizes_tagged_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, unc, rec_off, flag, selected, tg, n_rec, sizes,
+                       (ulonglong2 *)tile_sum, clash);
+    hipLaunchKernelGGL(gbam_kept_tiles_kernel, dim3(1), dim3(KEPT_SCAN_ROUND), 0, s, (const ulonglong2 *)tile_sum, n_tiles, (ulonglong2 *)tile_base);
+    hipLaunchKernelGGL(gbam_kept_offsets_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, sizes, (const ulonglong2 *)tile_base, n_rec, offsets);
+}
+void mdx_k_gbam_kept_gather_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets,
+                                   uint32_t n_rec, uint8_t *out, const MdxKeptTags &tg, hipStream_t s) {
+    if (n_rec == 0) return;
+    hipLaunchKernelGGL(gbam_kept_gather_tagged_kernel, dim3((n_rec + 31) / 32), dim3(256), 0, s, unc, rec_off, sizes, offsets, n_rec, out, tg);
 }

@@ -410,7 +410,8 @@ void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long
 // may key (a launch for the histogram alone).  form: 0 the cooperative kernel with part of the term table in the LDS; for
 // measurements 1 the trivial kernel, a lane per record, and 2 the cooperative one with every term from global memory.
 #include "mdx_pmd_key.h"
-void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, unsigned long long *kept, unsigned long long *hist, int form,
+// score (null: none): the float of every record's score as a score tag holds it (mdx_pmd_tag_bits, mdx_kept_tags.h).
+void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, float *score, unsigned long long *kept, unsigned long long *hist, int form,
                           hipStream_t s);
 void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
 // a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
@@ -479,6 +480,9 @@ extern "C" int mdx_ctx_minqual(const mdx_ctx *c);        // the context's --min-
 // the key column of a stratified context's last keyed batch (device), the flag column and n_reads of that batch, and the
 // number of batches keyed so far; returns the context's groups (0: not stratified — only *serial is written)
 extern "C" int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const uint16_t **flag, int64_t *n_reads, uint64_t *serial);
+// the score column beside it (mdx_strata_pmd_keep_scores; device) and the *serial of the keyed batch it belongs to; null and 0
+// where the batch keyed last left none
+extern "C" const float *mdx_ctx_strata_scores(const mdx_ctx *c, uint64_t *serial);
 extern "C" void mdx_ctx_scratch_give(mdx_ctx *c, void *arena, size_t cap, void *tables, void *stream, void *event);
 extern "C" void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, void **stream, void **event);
 
@@ -559,6 +563,20 @@ void mdx_k_gbam_kept_offsets(const uint8_t *unc, const uint32_t *rec_off, const 
                              hipStream_t s);
 void mdx_k_gbam_kept_gather(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec,
                             uint8_t *out, hipStream_t s);
+// ... with the tags of mdx_gbam_write_kept_tagged behind every written record (the rule: mdx_kept_tags.h): their names
+// (MDX_TAG_NAME; MDX_TAG_NONE: not asked for), the bytes they add per record (5, 7 or 12), and the key kernel's columns of this
+// very batch (key: never null; score: the bits of the score tag, null without one).  The sizes are those of the tagged
+// records, and *clash (device, 0xFFFFFFFF before the call) receives the lowest written record that has such a tag already.
+struct MdxKeptTags {
+    uint32_t group_name, score_name, bytes, n_groups;
+    const uint16_t *key;
+    const float *score;
+};
+void mdx_k_gbam_kept_offsets_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint8_t *selected,
+                                    const MdxKeptTags &tg, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base,
+                                    unsigned long long *offsets, uint32_t *clash, hipStream_t s);
+void mdx_k_gbam_kept_gather_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets,
+                                   uint32_t n_rec, uint8_t *out, const MdxKeptTags &tg, hipStream_t s);
 
 // ---- GPU-side SAM text decode (mdx_gsam.hip; host side: mdx_gsam_* in mdx_samio.cpp)
 // why a slab is given up (status[0] of the kernels; status[1] = the lowest line of the slab that gave a reason)

@@ -16,6 +16,7 @@
 // library handed out by ballot; an exclusive scan of the CIGAR and SEQ lengths in their new order (the new offset
 // columns); and the copy — CIGAR words, and SEQ nibbles shifted from the phase they had to the phase they get.  HBM-bound streaming work, about 100 bytes in and 100 out per record.
 #include "mdx_internal.h"
+#include "mdx_kept_tags.h"
 
 typedef uint8_t u8;
 typedef uint16_t u16;
@@ -553,7 +554,8 @@ void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long
 // kept: counted per stratum as the keys above do; hist: every kept record into the bin of its score, per library
 // ([n_libraries][MDX_PMD_BINS], and one word behind them: the kept records scored without qualities) — in the LDS up to
 // PMD_HIST_LDS words, one atomic per non-empty bin and block; beyond, straight into global memory.  key may be null (a
-// launch for the histogram alone: a resident batch that brings its buckets is not keyed again).
+// launch for the histogram alone: a resident batch that brings its buckets is not keyed again).  score (null: none): the
+// lane that writes a record's key also stores its score as the float of a score tag (mdx_pmd_tag_bits, mdx_kept_tags.h).
 #define PMD_GROUP 16
 #define PMD_COOP_OPS 8
 #define PMD_HIST_LDS 4096
@@ -575,10 +577,11 @@ struct PmdCounts {
 };
 
 __device__ __forceinline__ void pmd_count(const MdxPmdKey &a, i64 i, u32 lb, u32 fl, i64 s, const PmdCounts &pc, u16 *__restrict__ key,
-                                          u64 *__restrict__ kept, u64 *__restrict__ hist) {
+                                          float *__restrict__ score, u64 *__restrict__ kept, u64 *__restrict__ hist) {
     u32 k = 0xFFFFu;
     if (lb < (u32)a.n_libraries) k = lb * (u32)(a.n_thresholds + 1) + mdx_pmd_group(a, s);
     if (key) key[i] = (u16)k;
+    if (score) score[i] = __uint_as_float(mdx_pmd_tag_bits(s));
     if (k == 0xFFFFu || (fl & 0xF04u)) return;
     if (kept) {
         if (pc.in_lds) atomicAdd(&pc.h[k], 1u);
@@ -600,7 +603,8 @@ __device__ __forceinline__ void pmd_count(const MdxPmdKey &a, i64 i, u32 lb, u32
 // COOP: a group of lanes per record; else a lane per record (the trivial form, kept to be measured against: tools/strata_cost.py)
 // STAGE: COOP with part of the term table in the LDS; without, every term from global memory (kept to be measured against too)
 template <bool COOP, bool STAGE>
-__global__ __launch_bounds__(256) void strata_pmd_key_kernel(MdxPmdKey a, u16 *__restrict__ key, u64 *__restrict__ kept, u64 *__restrict__ hist) {
+__global__ __launch_bounds__(256) void strata_pmd_key_kernel(MdxPmdKey a, u16 *__restrict__ key, float *__restrict__ score, u64 *__restrict__ kept,
+                                                             u64 *__restrict__ hist) {
     // the LDS as the launch sized it (pmd_lds_words): [the staged terms, COOP][strata counts][histogram]
     extern __shared__ u32 pmd_lds[];
     const int n_strata = a.n_libraries * (a.n_thresholds + 1), n_hist = a.n_libraries * MDX_PMD_BINS + 1;
@@ -637,13 +641,13 @@ __global__ __launch_bounds__(256) void strata_pmd_key_kernel(MdxPmdKey a, u16 *_
             }
 #pragma unroll
             for (int o = PMD_GROUP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, PMD_GROUP);
-            if (live && l == 0) pmd_count(a, i, lb, fl, s, pc, key, kept, hist);
+            if (live && l == 0) pmd_count(a, i, lb, fl, s, pc, key, score, kept, hist);
         }
     } else {
         for (i64 i = lo + threadIdx.x; i < hi; i += 256) {
             const u32 lb = a.lib[i], fl = a.flag[i];
             const i64 s = lb < (u32)a.n_libraries ? mdx_pmd_score(a, i, fl) : 0;
-            pmd_count(a, i, lb, fl, s, pc, key, kept, hist);
+            pmd_count(a, i, lb, fl, s, pc, key, score, kept, hist);
         }
     }
     __syncthreads();
@@ -655,16 +659,16 @@ __global__ __launch_bounds__(256) void strata_pmd_key_kernel(MdxPmdKey a, u16 *_
             if (hh[l]) atomicAdd(&hist[l], (u64)hh[l]);
 }
 
-void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, unsigned long long *kept, unsigned long long *hist, int form,
+void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, float *score, unsigned long long *kept, unsigned long long *hist, int form,
                           hipStream_t s) {
     if (a.n <= 0) return;
     const dim3 grid((unsigned)((a.n + STRATA_KEY_PER - 1) / STRATA_KEY_PER));
     // (at most 24 + 16 + 16 KB: within what a launch gets without asking)
     const int n_strata = a.n_libraries * (a.n_thresholds + 1), n_hist = a.n_libraries * MDX_PMD_BINS + 1;
     const size_t words = (size_t)(n_strata <= LS_LDS_LIBS ? n_strata : 0) + (size_t)(n_hist <= PMD_HIST_LDS ? n_hist : 0);
-    if (form == 1) hipLaunchKernelGGL((strata_pmd_key_kernel<false, false>), grid, dim3(256), words * 4, s, a, key, (u64 *)kept, (u64 *)hist);
-    else if (form == 2) hipLaunchKernelGGL((strata_pmd_key_kernel<true, false>), grid, dim3(256), words * 4, s, a, key, (u64 *)kept, (u64 *)hist);
-    else hipLaunchKernelGGL((strata_pmd_key_kernel<true, true>), grid, dim3(256), (words + PMD_LDS_Z * PMD_LDS_Q) * 4, s, a, key, (u64 *)kept, (u64 *)hist);
+    if (form == 1) hipLaunchKernelGGL((strata_pmd_key_kernel<false, false>), grid, dim3(256), words * 4, s, a, key, score, (u64 *)kept, (u64 *)hist);
+    else if (form == 2) hipLaunchKernelGGL((strata_pmd_key_kernel<true, false>), grid, dim3(256), words * 4, s, a, key, score, (u64 *)kept, (u64 *)hist);
+    else hipLaunchKernelGGL((strata_pmd_key_kernel<true, true>), grid, dim3(256), (words + PMD_LDS_Z * PMD_LDS_Q) * 4, s, a, key, score, (u64 *)kept, (u64 *)hist);
 }
 
 // ... and for a batch that brings its columns bucketed by stratum (mdx_batch::libsort): the sizes of the buckets

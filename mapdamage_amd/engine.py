@@ -39,6 +39,7 @@ EXPORTS = (
     "mdx_gbam_view_flags", "mdx_gbam_view_set_flags",
     "mdx_rescale_patches_device", "mdx_tabulate_rescale_patches_device", "mdx_rescale_expand_device", "mdx_mr_round", "mdx_batch_fold", "mdx_bgzf_deflate",
     "mdx_gbam_rescale_slab", "mdx_gbam_write_rescaled", "mdx_gbam_record_name", "mdx_gbam_kept_bound", "mdx_gbam_write_kept",
+    "mdx_gbam_kept_bound_tagged", "mdx_gbam_write_kept_tagged", "mdx_strata_pmd_keep_scores", "mdx_strata_pmd_scores",
     "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_fasta_load_stats", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
     "mdx_source_open", "mdx_source_error", "mdx_source_is_stream", "mdx_source_peek", "mdx_source_read", "mdx_source_close",
     "mdx_bam_read_source", "mdx_bam_open_source", "mdx_gbam_open_source",
@@ -196,6 +197,8 @@ def load_library(path=None):
     lib.mdx_set_strata_pmd.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
     lib.mdx_strata_pmd_histogram.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_strata_pmd_unqualified.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_strata_pmd_keep_scores.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_strata_pmd_scores.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
     lib.mdx_strata_groups.argtypes = [ctypes.c_void_p]
     lib.mdx_strata_kept.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_merged_words.restype = ctypes.c_int64
@@ -387,12 +390,13 @@ class DamageEngine:
         self._check(self._lib.mdx_set_strata_damage(self._ctx, ctypes.c_int32(int(positions)), ctypes.c_int32(1 if single_stranded else 0)))
         self._strata_set = True
 
-    def set_strata_pmd(self, thresholds, model=(0.3, 0.01, 0.001), single_stranded=False):
+    def set_strata_pmd(self, thresholds, model=(0.3, 0.01, 0.001), single_stranded=False, keep_scores=False):
         """The group of a record from its post-mortem damage score (include/mdx.h ``mdx_set_strata_pmd``; the rule is
         ``csrc/mdx_pmd_key.h``): the number of ``thresholds`` (1 to 15, strictly increasing) the score reaches, under the
         model ``(p, C, pi)`` of ``pmd.term_table``.  The engine's ``groups`` number ``len(thresholds) + 1``
         (``pmd.group_names``), and it has no ``minqual``.  Before the first ``tabulate``; the key reads the reference, so
-        ``set_reference`` comes before ``upload``; the batches bring their qualities if these are to count."""
+        ``set_reference`` comes before ``upload``; the batches bring their qualities if these are to count.
+        ``keep_scores``: the key kernel also leaves every record's score as a float32 (``keep_pmd_scores``)."""
         from . import pmd
         ts = pmd.check_thresholds(thresholds)
         if self.groups is None or len(self.groups) != len(ts) + 1:
@@ -404,6 +408,23 @@ class DamageEngine:
                                                  ctypes.c_int32(1 if single_stranded else 0)))
         self._strata_set = True
         self._pmd = True
+        if keep_scores:
+            self.keep_pmd_scores(True)
+
+    def keep_pmd_scores(self, on=True):
+        """From the next keyed batch on, keep the scores of the batch keyed last on the device (include/mdx.h
+        ``mdx_strata_pmd_keep_scores``): what ``pmd_scores()`` fetches and the score tag of
+        ``sam.GpuBamStream.write_kept`` is written from."""
+        self._check(self._lib.mdx_strata_pmd_keep_scores(self._ctx, ctypes.c_int32(1 if on else 0)))
+
+    def pmd_scores(self, n=None):
+        """float32 [n]: the PMD scores of the ``n`` records of the batch tabulated last (default: as many as that batch had) (``mdx_strata_pmd_scores``) — the
+        fixed-point score as the nearest float32, times 2^-24.  MdxError -3 without PMD strata, without ``keep_pmd_scores``,
+        or behind a resident batch that brought its buckets."""
+        n = getattr(self, "_last_n_reads", 0) if n is None else int(n)
+        out = np.zeros(n, np.float32)
+        self._check(self._lib.mdx_strata_pmd_scores(self._ctx, _ptr(out), ctypes.c_int64(int(n))))
+        return out
 
     @property
     def pmd_strata(self):
@@ -509,8 +530,10 @@ class DamageEngine:
         ``packed`` (host batches): hand the SEQ column over in its 4-bit form (half the bytes across PCIe)."""
         self._set_record_base(0 if record_base is None else int(record_base))
         if isinstance(batch, DeviceBatch):
+            self._last_n_reads = int(batch.dev.n_reads)
             self._check(self._lib.mdx_tabulate_device(self._ctx, ctypes.byref(batch.dev)))
         else:
+            self._last_n_reads = int(batch.n)
             hb = _host_batch(batch, self.default_packed if packed is None else packed)
             self._check(self._lib.mdx_tabulate_host(self._ctx, ctypes.byref(hb)))
             if sync:
@@ -520,6 +543,7 @@ class DamageEngine:
     def tabulate_view(self, view, record_base=None):
         """An ``MdxBatch`` of device pointers (``sam.GpuBamStream.next_view``): enqueued, errors at ``sync``."""
         self._set_record_base(0 if record_base is None else int(record_base))
+        self._last_n_reads = int(view.n_reads)
         self._check(self._lib.mdx_tabulate_device(self._ctx, ctypes.byref(view)))
 
     def tabulate_pointers(self, n_reads, n_cigar, n_bases, **ptrs):

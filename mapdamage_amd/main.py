@@ -8,6 +8,7 @@ import argparse
 import dataclasses
 import logging
 import os
+import re
 import sys
 import time
 from pathlib import Path
@@ -21,7 +22,7 @@ from .engine import BadReadError, DamageEngine, MdxError
 from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
-from .sam import SAM_BGZF, SAM_GZIP, BAMError
+from .sam import SAM_BGZF, SAM_GZIP, BAMError, KeptTagClash
 from .statistics import check_table_and_warn_if_dmg_freq_is_low
 
 _LOG_FORMAT = "%(asctime)s %(name)s %(levelname)s %(message)s"
@@ -220,6 +221,14 @@ def build_parser():
                         "--by-terminal-damage, --by-pmd-score): write only the records of the groups with these indices of "
                         "groups.tsv, for all libraries — `--by-pmd-score --pmd-thresholds 3 --write-groups 1` is what `pmdtools "
                         "--threshold 3` would have written (default: every counted record)")
+    g.add_argument("--tag-group", default=None, metavar="TAG",
+                   help="with --write-kept in a run that has groups: append TAG:S (uint16) to every written record, its group's "
+                        "index in groups.tsv — the number --write-groups takes —, so that one file of one pass carries the "
+                        "partition (`samtools view -d TAG:1` splits it afterwards).  TAG: two characters, [A-Za-z][A-Za-z0-9]; a "
+                        "written record that has such a tag already ends the run")
+    g.add_argument("--tag-pmd-score", default=None, metavar="TAG",
+                   help="with --write-kept --by-pmd-score: append TAG:f to every written record, its PMD score (the run's "
+                        "fixed-point score as the nearest float32), so that the file can be split at any threshold afterwards")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -266,7 +275,7 @@ def check_write_groups(groups, n_groups):
 
 
 def _check_write_kept(parser, o):
-    """The argument errors of --write-kept / --write-groups."""
+    """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score."""
     has_groups = bool(o.by_reference or o.reference_groups or o.regions or o.region_groups or o.by_terminal_damage
                       or o.by_pmd_score)
     if o.write_groups is not None:
@@ -279,6 +288,20 @@ def _check_write_kept(parser, o):
             o.write_groups = parse_write_groups(o.write_groups)
         except ValueError as error:
             parser.error("--write-groups: %s" % error)
+    for option, tag in (("--tag-group", o.tag_group), ("--tag-pmd-score", o.tag_pmd_score)):
+        if tag is None:
+            continue
+        if o.write_kept is None:
+            parser.error("%s needs --write-kept: it tags the records that file receives" % option)
+        if not re.fullmatch(r"[A-Za-z][A-Za-z0-9]", tag):
+            parser.error("%s %s: a tag is two characters, [A-Za-z][A-Za-z0-9]" % (option, tag))
+    if o.tag_group is not None and not has_groups:
+        parser.error("--tag-group needs a run with groups: one of --by-reference, --reference-groups, --regions, "
+                     "--region-groups, --by-terminal-damage, --by-pmd-score")
+    if o.tag_pmd_score is not None and not o.by_pmd_score:
+        parser.error("--tag-pmd-score needs --by-pmd-score: the score is the one that run computes")
+    if o.tag_group is not None and o.tag_group == o.tag_pmd_score:
+        parser.error("--tag-group and --tag-pmd-score name the same tag, %s: a record has a tag once" % o.tag_group)
     if o.write_kept is None:
         return
     if o.rescale_only or o.stats_only:
@@ -689,7 +712,8 @@ def _make_engine(options, libraries, device):
     if strata is not None:
         try:
             if isinstance(strata[1], PmdScore):
-                engine.set_strata_pmd(strata[1].thresholds, strata[1].model, strata[1].single_stranded)
+                engine.set_strata_pmd(strata[1].thresholds, strata[1].model, strata[1].single_stranded,
+                                      keep_scores=getattr(options, "tag_pmd_score", None) is not None)
             elif isinstance(strata[1], TerminalDamage):
                 engine.set_strata_damage(strata[1].positions, strata[1].single_stranded)
             elif isinstance(strata[1], Regions):
@@ -821,7 +845,9 @@ class _KeptOutput:
         self.path = Path(options.write_kept)
         self.tmp = self.path.with_name("%s.%d.tmp" % (self.path.name, os.getpid()))
         self.groups = options.write_groups
-        self.n_groups = len(options.strata[0]) if self.groups is not None else 0
+        self.group_tag, self.score_tag = getattr(options, "tag_group", None), getattr(options, "tag_pmd_score", None)
+        tagged = self.group_tag is not None or self.score_tag is not None
+        self.n_groups = len(options.strata[0]) if self.groups is not None or tagged else 0
         self.stream, self.folder = stream, options.folder
         self.records = self.raw_bytes = 0
         self.writer = BgzfWriter(self.tmp, engine=engine)
@@ -835,7 +861,7 @@ class _KeptOutput:
         """The slab's kept records: right behind ``engine.tabulate_view(view)`` — the flags are final, the key column is the
         view's."""
         self.writer.flush()             # (the one output array is the writer thread's until its write is done)
-        members, n, raw = self.stream.write_kept(view, self.groups, self.n_groups)
+        members, n, raw = self.stream.write_kept(view, self.groups, self.n_groups, self.group_tag, self.score_tag)
         self.records += n
         self.raw_bytes += raw
         if len(members):
@@ -846,7 +872,9 @@ class _KeptOutput:
         self.writer = None
         os.replace(self.tmp, self.path)
         which = "all" if self.groups is None else ",".join(str(g) for g in self.groups)
-        logger.info("Wrote %d records to %s (groups: %s)", self.records, self.path, which)
+        tags = ["%s:S group" % self.group_tag] if self.group_tag is not None else []
+        tags += ["%s:f PMD score" % self.score_tag] if self.score_tag is not None else []
+        logger.info("Wrote %d records to %s (groups: %s)%s", self.records, self.path, which, "; tags: " + ", ".join(tags) if tags else "")
         (self.folder / "write_kept.tsv").write_text("path\tgroups\trecords\tuncompressed_bytes\n%s\t%s\t%d\t%d\n"
                                                     % (self.path, which, self.records, self.raw_bytes))
 
@@ -1002,6 +1030,10 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
         engine.close()
         return tables, None
+    except KeptTagClash:
+        # (--tag-group / --tag-pmd-score: a record has the tag already — the run's error, no other decoder would do better)
+        engine.close()
+        raise
     except GpuDecodeUnsupported as error:
         reason = "file layout the device path does not take (MDX_ERR_UNSUPPORTED): %s" % error
     except BadReadError as error:
@@ -1191,7 +1223,11 @@ def main(argv):
             logger.info("Filtering out bases with a Phred score < %d", options.minqual)
         logger.info("Writing results to '%s/'", options.folder)
 
-        tables, carry = _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages) if options.gpu_decode else (None, None)
+        try:
+            tables, carry = _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages) if options.gpu_decode else (None, None)
+        except KeptTagClash as error:
+            logger.error("%s", error)
+            return 1
         if tables is None and options.write_kept is not None:
             logger.error("--write-kept is written by the device decode path, which did not finish this run: nothing is "
                          "written, and the run does not go on without its output")

@@ -719,27 +719,44 @@ class GpuBamStream:
             raise ValueError("%r: %s" % (str(self.path), self._error()))
         return out[:out_len.value]
 
-    def kept_bound(self):
+    def kept_bound(self, group_tag=None, score_tag=None):
         """Bytes that always suffice for the members ``write_kept`` makes of the view handed out last (include/mdx.h
-        ``mdx_gbam_kept_bound``: from the view's record offsets, never a guess)."""
+        ``mdx_gbam_kept_bound``: from the view's record offsets, never a guess) — with the tags' 5 and 7 bytes for every record
+        of the view where they are asked for (``mdx_gbam_kept_bound_tagged``)."""
         import ctypes
-        fn = self._lib.mdx_gbam_kept_bound
-        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        tag_bytes = (5 if group_tag is not None else 0) + (7 if score_tag is not None else 0)
         bound = ctypes.c_int64(0)
-        if fn(self._g, ctypes.byref(bound)) != 0:
+        if tag_bytes:
+            fn = self._lib.mdx_gbam_kept_bound_tagged
+            fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int
+            rc = fn(self._g, ctypes.c_int32(tag_bytes), ctypes.byref(bound))
+        else:
+            fn = self._lib.mdx_gbam_kept_bound
+            fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+            rc = fn(self._g, ctypes.byref(bound))
+        if rc != 0:
             raise ValueError("%r: %s" % (str(self.path), self._error()))
         return int(bound.value)
 
-    def write_kept(self, view, groups=None, n_groups=0):
+    def write_kept(self, view, groups=None, n_groups=0, group_tag=None, score_tag=None):
         """The records of the view ``next_view`` handed out last that the run counts — ``(flag & 0xF04) == 0`` in the flag column
         as it stands, so behind ``set_view_flags`` — selected, compacted and compressed on the device (include/mdx.h
         ``mdx_gbam_write_kept``): returns ``(members, n_written, raw_bytes)``, the records byte for byte as BGZF members (a uint8
         array, valid until the next call: one output array, grown when ``kept_bound`` says so), their number and their bytes
         before compression.  ``groups``: indices of the groups of a stratified engine (``n_groups`` of them in all) whose records
-        alone are written — behind ``DamageEngine.tabulate_view`` of this very view (MdxError -3 otherwise)."""
+        alone are written — behind ``DamageEngine.tabulate_view`` of this very view (MdxError -3 otherwise).
+        ``group_tag`` / ``score_tag`` (two characters, ``[A-Za-z][A-Za-z0-9]``): every written record gets ``TAG:S``, its group
+        among the engine's ``n_groups``, and ``TAG:f``, its PMD score (an engine with ``keep_pmd_scores``), appended
+        (``mdx_gbam_write_kept_tagged``; behind ``tabulate_view`` of this very view as well).  A written record that has such
+        a tag already: ``KeptTagClash`` with the record's index in the slab and its name; nothing of the slab is written."""
         import ctypes
         import numpy as np
-        bound = self.kept_bound()
+        tags = []
+        for tag in (group_tag, score_tag):
+            if tag is not None and (len(tag) != 2 or not tag.isascii()):
+                raise ValueError("a tag is two ASCII characters, not %r" % (tag,))
+            tags.append(None if tag is None else tag.encode("ascii"))
+        bound = self.kept_bound(group_tag, score_tag)
         out = getattr(self, "_kept_out", None)
         if out is None or out.shape[0] < bound:
             out = self._kept_out = np.empty(bound + bound // 8, np.uint8)
@@ -750,14 +767,27 @@ class GpuBamStream:
                 if not 0 <= int(g) < int(n_groups):
                     raise ValueError("group %d is outside 0..%d" % (int(g), int(n_groups) - 1))
                 selected[int(g)] = 1
-        fn = self._lib.mdx_gbam_write_kept
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-        out_len, n_written, raw_bytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        rc = fn(self._g, None if selected is None else ctypes.c_void_p(selected.ctypes.data), ctypes.c_int32(int(n_groups)),
-                ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(out.shape[0]), ctypes.byref(out_len), ctypes.byref(n_written),
-                ctypes.byref(raw_bytes))
+        out_len, n_written, raw_bytes, clash = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(-1)
+        sel = None if selected is None else ctypes.c_void_p(selected.ctypes.data)
+        if tags[0] is None and tags[1] is None:
+            fn = self._lib.mdx_gbam_write_kept
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                           ctypes.c_void_p, ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+            rc = fn(self._g, sel, ctypes.c_int32(int(n_groups)), ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(out.shape[0]),
+                    ctypes.byref(out_len), ctypes.byref(n_written), ctypes.byref(raw_bytes))
+        else:
+            fn = self._lib.mdx_gbam_write_kept_tagged
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p,
+                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+            fn.restype = ctypes.c_int
+            rc = fn(self._g, sel, ctypes.c_int32(int(n_groups)), tags[0], tags[1], ctypes.c_void_p(out.ctypes.data),
+                    ctypes.c_int64(out.shape[0]), ctypes.byref(out_len), ctypes.byref(n_written), ctypes.byref(raw_bytes),
+                    ctypes.byref(clash))
+        if rc == -6 and clash.value >= 0:
+            name = ctypes.create_string_buffer(256)
+            self._lib.mdx_gbam_record_name(self._g, ctypes.c_int64(clash.value), name, 256)
+            raise KeptTagClash(clash.value, name.value.decode(errors="replace"), [t for t in (group_tag, score_tag) if t is not None])
         if rc != 0:
             from .engine import MdxError
             raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
@@ -1002,6 +1032,17 @@ def sam_header(src):
 
 class GpuDecodeUnsupported(ValueError):
     """The file's layout is not one the GPU decode path takes (MDX_ERR_UNSUPPORTED)."""
+
+
+class KeptTagClash(Exception):
+    """``GpuBamStream.write_kept`` with tags: a record to be written has a tag of one of the names already (MDX_ERR_BAD_READ,
+    ``code`` -6).  ``index``: the record's index in its slab, ``name``: its read name, ``tags``: the names asked for."""
+    code = -6
+
+    def __init__(self, index, name, tags):
+        super().__init__("Read: %s already has a tag named %s; the run appends such a tag to every record it writes "
+                         "(choose another name)" % (name, " or ".join(tags)))
+        self.index, self.name, self.tags = int(index), name, list(tags)
 
 
 class BamStream:

@@ -4,14 +4,18 @@ one BAM, then three commands timed as cold processes, each under a time limit of
   plain   `python -m mapdamage_amd -i x.bam -r x.fa --no-stats ...`                                       what a run did before
   kept    the same with `--write-kept kept.bam`                                                          every counted record
   pmd     the same with `--by-pmd-score --pmd-thresholds 3 --write-kept pmd.bam --write-groups 1`        the top PMD group
+  --tags adds two more:
+  pmd_all     `--by-pmd-score --pmd-thresholds 3 --write-kept pmd_all.bam`                               every counted record
+  pmd_tagged  the same with `--tag-group XG --tag-pmd-score DS`                                          ... with its two tags
 
 The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
 times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
-(write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost.  --parent-root DIR: a
+(write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost, pmd_tagged - pmd_all that
+of the tags (12 bytes a record, the score column, the walk over every written record's tags).  --parent-root DIR: a
 built checkout of the parent commit; `plain` is then also timed there, in the same alternation — a difference between the two
 beyond the spread means the option-less path has changed.  One JSON line on stdout.
 
-    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR]"""
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags]"""
 import argparse
 import json
 import os
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--dir", help="where the BAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
+    ap.add_argument("--tags", action="store_true", help="also time --by-pmd-score --write-kept with and without --tag-group / --tag-pmd-score")
     args = ap.parse_args()
     import numpy as np
 
@@ -64,6 +69,10 @@ def main():
         base = [sys.executable, "-m", "mapdamage_amd", "-i", bam, "-r", fa, "--no-stats", "--log-level", "DEBUG"]
         legs = [("plain", ROOT, []), ("kept", ROOT, ["--write-kept", os.path.join(work, "kept.bam")]),
                 ("pmd", ROOT, ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept", os.path.join(work, "pmd.bam"), "--write-groups", "1"])]
+        if args.tags:
+            pmd_all = ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept"]
+            legs += [("pmd_all", ROOT, pmd_all + [os.path.join(work, "pmd_all.bam")]),
+                     ("pmd_tagged", ROOT, pmd_all + [os.path.join(work, "pmd_tagged.bam"), "--tag-group", "XG", "--tag-pmd-score", "DS"])]
         if args.parent_root:
             legs.insert(1, ("parent_plain", os.path.abspath(args.parent_root), []))
         times = {name: [] for name, _, _ in legs}
@@ -93,6 +102,12 @@ def main():
         if status == 0:
             for name in ("kept", "pmd"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            if args.tags:
+                result["pmd_tagged_minus_pmd_all_s"] = round(result["pmd_tagged"]["median_s"] - result["pmd_all"]["median_s"], 3)
+                extra = result["pmd_tagged"]["uncompressed_bytes"] - result["pmd_all"]["uncompressed_bytes"]
+                if result["pmd_tagged"]["records_written"] != n_counted or extra != 12 * n_counted:
+                    result["error"] = "pmd_tagged.bam: %d records, %d bytes more than pmd_all.bam; %d records counted" % (
+                        result["pmd_tagged"]["records_written"], extra, n_counted)
             tables = {name: [open(os.path.join(work, name, f)).read() for f in FILES] for name, _, _ in legs}
             same = all(t == tables["plain"] for t in tables.values())
             result["usual_tables"] = "byte-identical" if same else "MISMATCH"
