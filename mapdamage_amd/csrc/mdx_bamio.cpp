@@ -2164,6 +2164,10 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
             // inside a record that straddles whole blocks — must not have produced one)
             bool clean = true;
             for (size_t i = nb; i < sg && i < nba; i++) clean = clean && info[4 * i + 2] == 1u;
+            // (the records end where the file's data ends — what follows is empty members, the end-of-file marker of a file whose
+            // last slab holds nothing else: the rank behind has no record to find, and finds none if nothing there made a guess)
+            if (sg >= nba && !more_file && at == unc_bytes) g->next_verified = clean;
+            else
             g->next_verified = clean && sg < nba && info[4 * sg + 2] != 1u && info[4 * sg] == (uint32_t)at;
         }
     }
