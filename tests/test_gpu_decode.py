@@ -640,25 +640,9 @@ def test_flag_bit_15_of_a_file_is_not_the_kernels_hint(tmp_path):
 
 def _inflate_on_device(eng, cases):
     """cases: [(deflate payload, ISIZE, CRC32)] -> [(status, bytes out, crc ok)] through mdx_gbam_inflate_blocks."""
-    lib = eng._lib
-    lib.mdx_gbam_inflate_blocks.restype = ctypes.c_int
-    lib.mdx_gbam_inflate_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    comp = np.frombuffer(b"".join(c for c, _, _ in cases) + b"\0" * 8, np.uint8).copy()
-    blk = np.zeros((len(cases), 4), np.uint32)
-    cin = cout = 0
-    for i, (c, isize, _) in enumerate(cases):
-        blk[i] = (cin, len(c), cout, isize)
-        cin += len(c)
-        cout += (isize + 15) & ~15
-    out = np.zeros(cout + 16, np.uint8)
-    status = np.zeros(len(cases), np.int32)
-    crc = np.asarray([k for _, _, k in cases], np.uint32)
-    crc_ok = np.zeros(len(cases), np.uint8)
-    rc = lib.mdx_gbam_inflate_blocks(eng._ctx, comp.ctypes.data, cin, blk.ctypes.data, len(cases), out.ctypes.data, cout,
-                                     status.ctypes.data, crc.ctypes.data, crc_ok.ctypes.data)
-    assert rc == 0, rc
-    return [(int(status[i]), out[int(blk[i, 2]):int(blk[i, 2]) + int(blk[i, 3])].tobytes(), bool(crc_ok[i])) for i in range(len(cases))]
+    from tests.inflate_util import inflate_blocks
+    status, out, crc_ok, offs = inflate_blocks(eng, cases)
+    return [(int(status[i]), out[int(offs[i]):int(offs[i]) + cases[i][1]].tobytes(), bool(crc_ok[i])) for i in range(len(cases))]
 
 
 def test_device_inflate_against_zlib_every_block_type_and_damage():

@@ -1,6 +1,8 @@
 """The DEFLATE decoder of the GPU decode path (mapdamage_amd/csrc/mdx_inflate.h) compiled for the host and held
-against zlib: valid streams of every block type, random bytes and bit-flipped streams (accepted / rejected alike, same
-bytes out).  The same header runs one BGZF block per wavefront on the GPU (tests/test_gpu_decode.py)."""
+against zlib: valid streams of every block type as zlib writes them, random bytes and bit-flipped streams (accepted /
+rejected alike, same bytes out).  The streams zlib does not write — other codes, matches, headers, empty blocks — are
+tests/deflate_craft.py's: tests/test_deflate_craft.py holds the same host build against zlib on those.  The same header
+runs one BGZF block per wavefront on the GPU (tests/test_gpu_decode.py, tests/test_gpu_inflate_craft.py)."""
 import os
 import pathlib
 import random
