@@ -638,6 +638,41 @@ int mdx_gbam_write_kept(struct mdx_gbam *g, const uint8_t *group_selected, int32
 int mdx_gbam_kept_bound_tagged(struct mdx_gbam *g, int32_t tag_bytes, int64_t *bytes);
 int mdx_gbam_write_kept_tagged(struct mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, const char *group_tag, const char *score_tag,
                                uint8_t *out, int64_t out_cap, int64_t *out_len, int64_t *n_written, int64_t *raw_bytes, int64_t *clash);
+/* --write-index: the BAI index (SAM specification 5.2) of the file those members make, from what the run has on the device — no
+ * second inflate of the output.  The rule is csrc/mdx_kept_index.h: extents by the CIGAR, reg2bin, one chunk per maximal run
+ * of consecutive written records with the same (tid, bin), the linear index's minima; nothing is merged, so the index is a
+ * function of the written file alone.
+ *   mdx_gbam_kept_index     right behind mdx_gbam_write_kept / _tagged of the view handed out last (anything else:
+ *                           MDX_ERR_STATE; a call that failed does not count).  stream_base = the uncompressed bytes all
+ *                           earlier slabs wrote (the sum of their *raw_bytes): every offset that comes back is stream_base + the
+ *                           record's offset in this slab's stream, and the caller turns the few of them into virtual file
+ *                           offsets with the members' compressed sizes (BSIZE).  *prev_tid / *prev_pos: the last written
+ *                           record in front of this slab (-1, -1: none), updated to this slab's last one.  runs (host, runs_cap
+ *                           entries; *n_written of the write always suffice, fewer than the slab has: MDX_ERR_ARG) receives
+ *                           *n_runs entries in file order: records [first, last) of the slab's written ones, bytes
+ *                           [ustart, uend) of the stream.  A slab's first run may continue the last run of the slab in
+ *                           front (equal tid and bin): joining them is the caller's.  The linear index is kept on the device
+ *                           across the calls.  A written record out of coordinate order against the written record before
+ *                           it (reason MDX_INDEX_UNSORTED), or one outside [0, min(LN, 2^29)] of a header sequence
+ *                           (MDX_INDEX_UNPLACEABLE): MDX_ERR_BAD_READ, *bad = the lowest such index of the slab
+ *                           (mdx_gbam_record_name gives its name), *reason says which; nothing comes back.  Dropped records are
+ *                           not looked at.  Nothing is launched for a slab without written records.
+ *   mdx_gbam_kept_index_linear  out[n] (host): one word per 16 KiB window of every header sequence in turn, n = the sum of
+ *                           ceil(LN / 16384) (*n_words, may be NULL; out NULL with n 0 asks for it alone): the lowest ustart
+ *                           of a written record that touches the window, all ones for an untouched one.  Once, behind the
+ *                           last slab.
+ * The handle owns the scratch and the linear index (190 k words for a 3 Gb genome); mdx_gbam_close releases them. */
+#define MDX_INDEX_UNSORTED 1
+#define MDX_INDEX_UNPLACEABLE 2
+typedef struct mdx_index_run {
+    int32_t tid;
+    uint32_t bin;
+    uint64_t ustart, uend;
+    uint32_t first, last;
+} mdx_index_run;
+int mdx_gbam_kept_index(struct mdx_gbam *g, int64_t stream_base, int32_t *prev_tid, int32_t *prev_pos, mdx_index_run *runs, int64_t runs_cap,
+                        int64_t *n_runs, int64_t *bad, int32_t *reason);
+int mdx_gbam_kept_index_linear(struct mdx_gbam *g, uint64_t *out, int64_t n, int64_t *n_words);
 /* mdx_mr_round: float("%.5f" % x) of rescale.py:275-276 for n MR sums (mr_raw of the rescale calls) on `threads` host threads —
  * the value printed with five decimals, read back, and narrowed to the 32 bits of an MR:f tag; NaN (a record written back
  * unchanged) gives 0. */

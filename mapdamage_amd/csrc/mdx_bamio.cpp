@@ -8,6 +8,7 @@
 #endif
 #include "mdx_filter.h"
 #include "mdx_kept_tags.h"
+#include "mdx_kept_index.h"
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
@@ -1561,6 +1562,14 @@ struct mdx_gbam {
     size_t view_rec_bytes = 0;
     uint64_t view_key_serial = 0;
     Buf kept_sizes, kept_off, kept_tiles, kept_sel, kept_stream;
+    // --write-index (mdx_gbam_kept_index): the views handed out so far and the one whose records the kept kernels laid out last
+    // (0: none), what they wrote of it; the dense list, the runs, the tile sums and the result words of the index kernels, and —
+    // for the handle's life — the header's lengths with each sequence's first window, and the linear index (all ones: untouched)
+    uint64_t view_serial = 0, kept_of_view = 0;
+    int64_t kept_written = 0;
+    Buf index_dense, index_runs, index_tiles, index_res, index_ref, index_linear;
+    std::vector<int64_t> index_ref_host;      // [n_ref] lengths, [n_ref] first windows
+    uint64_t index_windows = 0;
     bool reserve(Buf &b, size_t bytes) {
         if (bytes <= b.cap) return true;
         if (b.p) (void)hipFree(b.p);
@@ -2226,6 +2235,7 @@ static int gbam_half_b(mdx_gbam *g, mdx_gbam::Slab &s, mdx_batch *view, const in
     g->slabs_done++;
     g->view_reads = view->n_reads;
     g->view_rec_bytes = at - at_first;
+    g->view_serial++;
     (void)mdx_ctx_strata_key(g->ctx, nullptr, nullptr, nullptr, &g->view_key_serial);
     s.ready = false;
     return MDX_OK;
@@ -2509,7 +2519,8 @@ void mdx_gbam_close(mdx_gbam *g) {
     g->copy_stream = nullptr;
     rg_buffer_give(g->device, g->d_rg, g->d_rg_cap);
     if (g->d_filter_counts) (void)hipFree(g->d_filter_counts);
-    for (mdx_gbam::Buf *b : {&g->kept_sizes, &g->kept_off, &g->kept_tiles, &g->kept_sel, &g->kept_stream}) if (b->p) (void)hipFree(b->p);
+    for (mdx_gbam::Buf *b : {&g->kept_sizes, &g->kept_off, &g->kept_tiles, &g->kept_sel, &g->kept_stream, &g->index_dense, &g->index_runs,
+                             &g->index_tiles, &g->index_res, &g->index_ref, &g->index_linear}) if (b->p) (void)hipFree(b->p);
     for (int k = 0; k < 3; k++) pf_buffer_give(g->device, g->pf_buf[k], g->pf_cap[k]);
     lap("device");
     // (unmapping the file — a few hundred thousand touched pages — is 3-4 ms of an 8 M-record file's 63; done behind the
@@ -2708,6 +2719,7 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
     if (!g || !out_len || !n_written || !raw_bytes || out_cap < 0 || (out_cap > 0 && !out)) return MDX_ERR_ARG;
     *out_len = 0; *n_written = 0; *raw_bytes = 0;
     if (clash) *clash = -1;
+    g->kept_of_view = 0;                 // (mdx_gbam_kept_index: valid behind a call that laid the view's records out)
     const char *const fn = group_tag || score_tag ? "mdx_gbam_write_kept_tagged: " : "mdx_gbam_write_kept: ";
     try {
         const bool tagged = group_tag || score_tag;
@@ -2745,7 +2757,7 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
             }
         }
         const int64_t n = g->view_reads;
-        if (n == 0) return MDX_OK;
+        if (n == 0) { g->kept_of_view = g->view_serial; g->kept_written = 0; return MDX_OK; }
         if (n > 0xFFFFFFFFll) return MDX_ERR_ARG;
         if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
         hipStream_t st = g->stream;
@@ -2787,7 +2799,7 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
             g->error = "record " + std::to_string(at) + " of the slab is to be written and has a tag named like one to be added already";
             return MDX_ERR_BAD_READ;
         }
-        if (total[0] == 0) return MDX_OK;
+        if (total[0] == 0) { g->kept_of_view = g->view_serial; g->kept_written = 0; return MDX_OK; }
         if (tagged)
             mdx_k_gbam_kept_gather_tagged((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
                                           (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, tg, st);
@@ -2798,6 +2810,7 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
         rc = bgzf_deflate_impl(st, g->device, nullptr, (const uint8_t *)g->kept_stream.p, (int64_t)total[1], out, out_cap, out_len);
         if (rc != MDX_OK) { g->error = std::string(fn) + "the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
         *n_written = (int64_t)total[0]; *raw_bytes = (int64_t)total[1];
+        g->kept_of_view = g->view_serial; g->kept_written = (int64_t)total[0];
         return MDX_OK;
     } catch (const std::exception &e) {
         g->error = std::string(fn) + e.what();
@@ -2807,6 +2820,109 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
 int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
                         int64_t *n_written, int64_t *raw_bytes) {
     return mdx_gbam_write_kept_tagged(g, group_selected, n_groups, nullptr, nullptr, out, out_cap, out_len, n_written, raw_bytes, nullptr);
+}
+
+// --write-index (include/mdx.h; the rule: mdx_kept_index.h): the runs of equal (tid, bin) among the records the last
+// mdx_gbam_write_kept / _tagged call laid out, and the linear index's minima, from the sizes and offsets that call left on the
+// device and the view's tid, pos and CIGAR columns.  Four launches behind the write on the context's stream, the result words
+// (32 bytes) and then the runs copied back; the handle owns the scratch.  Nothing runs for a slab without written records.
+int mdx_gbam_kept_index(mdx_gbam *g, int64_t stream_base, int32_t *prev_tid, int32_t *prev_pos, mdx_index_run *runs, int64_t runs_cap,
+                        int64_t *n_runs, int64_t *bad, int32_t *reason) {
+    if (!g || !prev_tid || !prev_pos || !n_runs || stream_base < 0 || runs_cap < 0 || (runs_cap > 0 && !runs)) return MDX_ERR_ARG;
+    *n_runs = 0;
+    if (bad) *bad = -1;
+    if (reason) *reason = 0;
+    const char *const fn = "mdx_gbam_kept_index: ";
+    static_assert(sizeof(mdx_index_run) == sizeof(MdxIndexRun) && sizeof(MdxIndexRun) == 32, "the runs are copied as they are");
+    try {
+        if (g->kept_of_view == 0 || g->kept_of_view != g->view_serial) {
+            g->error = std::string(fn) + "no mdx_gbam_write_kept of the view handed out last (write the view first, and nothing else in between)";
+            return MDX_ERR_STATE;
+        }
+        const int64_t n = g->view_reads, nw = g->kept_written;
+        if (nw == 0) return MDX_OK;
+        if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
+        hipStream_t st = g->stream;
+        mdx_gbam::Slab &s = g->slab[g->view_slab];
+        int rc = MDX_OK;
+        auto ok = [&](hipError_t e) { if (e != hipSuccess) { rc = MDX_ERR_HIP; g->error = std::string(fn) + hipGetErrorString(e); (void)hipGetLastError(); } return e == hipSuccess; };
+        const std::vector<int64_t> &len = g->hs->head.ref_lengths;
+        const size_t n_ref = len.size();
+        if (!g->index_linear.p) {
+            // once per handle: the header's lengths, each sequence's first window, the linear index untouched
+            g->index_ref_host.assign(2 * n_ref, 0);
+            uint64_t w = 0;
+            for (size_t i = 0; i < n_ref; i++) {
+                g->index_ref_host[i] = len[i];
+                g->index_ref_host[n_ref + i] = (int64_t)w;
+                w += mdx_index_windows(len[i]);
+            }
+            g->index_windows = w;
+            if (!g->reserve(g->index_ref, 16 * n_ref + 16) || !g->reserve(g->index_linear, 8 * (size_t)w + 8)) return MDX_ERR_HIP;
+            if (!ok(hipMemcpyAsync(g->index_ref.p, g->index_ref_host.data(), 16 * n_ref, hipMemcpyHostToDevice, st)) ||
+                !ok(hipMemsetAsync(g->index_linear.p, 0xFF, 8 * (size_t)w + 8, st))) { (void)hipFree(g->index_linear.p); g->index_linear = mdx_gbam::Buf{}; return rc; }
+        }
+        const size_t n_tiles = ((size_t)nw + (size_t)mdx_k_gbam_kept_tile() - 1) / (size_t)mdx_k_gbam_kept_tile();
+        const size_t rec_tiles = ((size_t)n + (size_t)mdx_k_gbam_kept_tile() - 1) / (size_t)mdx_k_gbam_kept_tile();
+        const size_t cap = (size_t)std::min<int64_t>(runs_cap, nw);
+        if (!g->reserve(g->index_dense, (size_t)nw * 32 + 64) || !g->reserve(g->index_runs, (size_t)nw * sizeof(MdxIndexRun)) ||
+            !g->reserve(g->index_tiles, (2 * n_tiles + 2) * 16) || !g->reserve(g->index_res, sizeof(MdxKeptIndexResult))) return MDX_ERR_HIP;
+        MdxKeptIndex d{};
+        char *p = (char *)g->index_dense.p;
+        d.end = (int64_t *)p; d.ustart = (unsigned long long *)(p + (size_t)nw * 8);
+        d.tid = (int32_t *)(p + (size_t)nw * 16); d.pos = d.tid + nw;
+        d.index = (uint32_t *)(d.pos + nw); d.bytes = d.index + nw;
+        MdxKeptIndexResult res{~0ull, 0ull, *prev_tid, *prev_pos};
+        if (!ok(hipMemcpyAsync(g->index_res.p, &res, sizeof(res), hipMemcpyHostToDevice, st))) return rc;
+        char *tiles = (char *)g->index_tiles.p;
+        // (the kept kernels' tile bases: behind their tile sums, mdx_gbam_write_kept_tagged)
+        const void *kept_tile_base = (const char *)g->kept_tiles.p + rec_tiles * 16;
+        mdx_k_gbam_kept_index((const uint32_t *)g->kept_sizes.p, (const unsigned long long *)g->kept_off.p, kept_tile_base, (const int32_t *)s.tid.p,
+                              (const int32_t *)s.pos.p, (const uint32_t *)s.cigar_off.p, (const uint32_t *)s.cigar.p, (uint32_t)n, (uint32_t)nw,
+                              (uint64_t)stream_base, d, *prev_tid, *prev_pos, (int32_t)n_ref, (const int64_t *)g->index_ref.p,
+                              (const uint64_t *)g->index_ref.p + n_ref, (unsigned long long *)g->index_linear.p, tiles, tiles + n_tiles * 16,
+                              (MdxIndexRun *)g->index_runs.p, (uint64_t)cap, (MdxKeptIndexResult *)g->index_res.p, st);
+        if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(&res, g->index_res.p, sizeof(res), hipMemcpyDeviceToHost, st)) ||
+            !ok(hipStreamSynchronize(st))) return rc;
+        if (res.fail != ~0ull) {
+            const int64_t at = (int64_t)(res.fail >> 2);
+            const int why = (int)(res.fail & 3u);
+            if (bad) *bad = at;
+            if (reason) *reason = why;
+            g->error = "record " + std::to_string(at) + " of the slab is to be written and " +
+                       (why == (int)MDX_INDEX_UNSORTED ? "lies in front of the written record before it: the index needs coordinate order"
+                                                      : "does not lie inside its reference sequence's first 2^29 bases: BAI cannot place it");
+            return MDX_ERR_BAD_READ;
+        }
+        if (res.n_runs > (unsigned long long)runs_cap) {
+            g->error = std::string(fn) + "the slab has " + std::to_string(res.n_runs) + " runs, the caller's array holds " + std::to_string(runs_cap);
+            return MDX_ERR_ARG;
+        }
+        if (res.n_runs > 0 && (!ok(hipMemcpyAsync(runs, g->index_runs.p, (size_t)res.n_runs * sizeof(MdxIndexRun), hipMemcpyDeviceToHost, st)) ||
+                               !ok(hipStreamSynchronize(st)))) return rc;
+        *n_runs = (int64_t)res.n_runs;
+        *prev_tid = res.last_tid; *prev_pos = res.last_pos;
+        return MDX_OK;
+    } catch (const std::exception &e) {
+        g->error = std::string(fn) + e.what();
+        return MDX_ERR_ARG;
+    }
+}
+
+// the linear index of all mdx_gbam_kept_index calls so far: one word per 16 KiB window of every header sequence in turn
+// (sum of ceil(LN / 16384) words: *n_words), the lowest stream offset of a written record that touches it, all ones for none
+int mdx_gbam_kept_index_linear(mdx_gbam *g, uint64_t *out, int64_t n, int64_t *n_words) {
+    if (!g || n < 0 || (n > 0 && !out)) return MDX_ERR_ARG;
+    uint64_t w = 0;
+    for (int64_t l : g->hs->head.ref_lengths) w += mdx_index_windows(l);
+    if (n_words) *n_words = (int64_t)w;
+    if (!out && n == 0) return MDX_OK;
+    if ((uint64_t)n != w) { g->error = "mdx_gbam_kept_index_linear: the header's sequences have " + std::to_string(w) + " windows, not " + std::to_string(n); return MDX_ERR_ARG; }
+    if (!g->index_linear.p) { std::fill(out, out + n, ~(uint64_t)0); return MDX_OK; }
+    if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
+    if (n > 0 && (hipMemcpyAsync(out, g->index_linear.p, (size_t)n * 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+                  hipStreamSynchronize(g->stream) != hipSuccess)) { (void)hipGetLastError(); g->error = "mdx_gbam_kept_index_linear: the copy failed"; return MDX_ERR_HIP; }
+    return MDX_OK;
 }
 
 // One call per slab of a --rescale-only pass on the device (rescale.py:285-365): the view mdx_gbam_next handed out last (it

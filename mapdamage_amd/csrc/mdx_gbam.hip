@@ -731,3 +731,113 @@ void mdx_k_gbam_kept_gather_tagged(const uint8_t *unc, const uint32_t *rec_off, 
     if (n_rec == 0) return;
     hipLaunchKernelGGL(gbam_kept_gather_tagged_kernel, dim3((n_rec + 31) / 32), dim3(256), 0, s, unc, rec_off, sizes, offsets, n_rec, out, tg);
 }
+
+// ---- the BAI index of that output stream (--write-index; host side: mdx_gbam_kept_index; the rule: mdx_kept_index.h), from the
+// sizes and offsets the kept kernels left and the view's tid, pos and CIGAR columns, in uncompressed stream coordinates
+// (stream_base + offsets[r]: monotone in the virtual offsets the host makes of the few results).  Four launches, no block waits
+// for another one:
+//   gbam_index_dense_kernel   a lane per record of the view: a written record's rank is the tile's count of written records in
+//                             front (the kept kernels' tile_base) plus a block scan of sizes != 0; (tid, pos, end, index in the
+//                             slab, start offset, bytes) go to place `rank` of a dense list
+//   gbam_index_check_kernel   a lane per written record j against j - 1 (record 0: against the last written record of the slabs
+//                             in front, the caller's): placeable, in order — the lowest offending slab index and its reason by one
+//                             64-bit atomicMin —, the linear index — a 64-bit atomicMin per window that j - 1 does not cover: in
+//                             sorted input thousands of consecutive records share a window, and one of them touches it —, and per
+//                             tile the number of records that begin a run of equal (tid, bin)
+//   gbam_kept_tiles_kernel    the scan of those counts (the kept kernels' one block)
+//   gbam_index_runs_kernel    a lane per written record: the head of a run writes the run's tid, bin, start and first rank, the
+//                             last record of a run its end and the rank behind it
+#include "mdx_kept_index.h"
+namespace {
+struct IndexRecord { int32_t tid, pos; int64_t end; };
+__device__ __forceinline__ IndexRecord index_record(const MdxKeptIndex &d, u32 j) { return IndexRecord{d.tid[j], d.pos[j], d.end[j]}; }
+__device__ __forceinline__ u32 index_bin(const IndexRecord &a) { return mdx_reg2bin((u32)a.pos, (u32)a.end); }
+// does record j (0 < j) begin a run?
+__device__ __forceinline__ bool index_head(const MdxKeptIndex &d, u32 j) {
+    const IndexRecord a = index_record(d, j - 1), b = index_record(d, j);
+    return a.tid != b.tid || index_bin(a) != index_bin(b);
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_index_dense_kernel(const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                                    const ulonglong2 *__restrict__ tile_base, const int32_t *__restrict__ tid,
+                                                                    const int32_t *__restrict__ pos, const u32 *__restrict__ cigar_off,
+                                                                    const u32 *__restrict__ cigar, u32 n_rec, u32 n_written, u64 stream_base,
+                                                                    MdxKeptIndex d) {
+    __shared__ u64 sh[KEPT_TILE];
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    const u32 sz = r < n_rec ? sizes[r] : 0u;
+    const u64 incl = kept_block_scan(sz ? 1ull : 0ull, sh);
+    if (sz == 0u) return;
+    const u64 j = tile_base[blockIdx.x].x + incl - 1ull;
+    if (j >= (u64)n_written) return;               // (cannot be: the list holds what the same sizes counted)
+    const u32 c0 = cigar_off[r];
+    d.tid[j] = tid[r]; d.pos[j] = pos[r];
+    d.end[j] = mdx_record_end(pos[r], cigar + c0, cigar_off[r + 1] - c0);
+    d.index[j] = r;
+    d.ustart[j] = stream_base + offsets[r];
+    d.bytes[j] = sz;
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_index_check_kernel(MdxKeptIndex d, u32 n_written, int32_t prev_tid, int32_t prev_pos, int32_t n_ref,
+                                                                    const int64_t *__restrict__ ref_len, const u64 *__restrict__ ref_win,
+                                                                    unsigned long long *__restrict__ linear, ulonglong2 *__restrict__ tile_sum,
+                                                                    MdxKeptIndexResult *__restrict__ res) {
+    const u32 j = blockIdx.x * KEPT_TILE + threadIdx.x;
+    u32 head = 0;
+    if (j < n_written) {
+        const IndexRecord b = index_record(d, j);
+        const IndexRecord a = j ? index_record(d, j - 1) : IndexRecord{prev_tid, prev_pos, 0};
+        const bool placeable = mdx_index_placeable(b.tid, b.pos, b.end, n_ref, ref_len);
+        const bool ordered = mdx_index_in_order(a.tid, a.pos, b.tid, b.pos);
+        if (!placeable || !ordered)
+            atomicMin(&res->fail, (unsigned long long)d.index[j] << 2 | (ordered ? MDX_INDEX_UNPLACEABLE : MDX_INDEX_UNSORTED));
+        head = j == 0u || a.tid != b.tid || index_bin(a) != index_bin(b);
+        if (placeable) {
+            // (placeable: every window of the record lies inside its sequence's part of the array)
+            int64_t w = b.pos >> MDX_BAI_LINEAR_SHIFT;
+            const int64_t w1 = (b.end - 1) >> MDX_BAI_LINEAR_SHIFT;
+            if (j && a.tid == b.tid) { const int64_t covered = (a.end - 1) >> MDX_BAI_LINEAR_SHIFT; if (covered >= w) w = covered + 1; }
+            const unsigned long long at = d.ustart[j];
+            unsigned long long *__restrict__ mine = linear + ref_win[b.tid];
+            for (; w <= w1; w++) atomicMin(mine + w, at);
+        }
+        if (j == n_written - 1u) { res->last_tid = b.tid; res->last_pos = b.pos; }
+    }
+    kept_tile_pair(head, tile_sum);
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_index_runs_kernel(MdxKeptIndex d, u32 n_written, const ulonglong2 *__restrict__ tile_base,
+                                                                   u32 n_tiles, MdxIndexRun *__restrict__ runs, u64 cap,
+                                                                   MdxKeptIndexResult *__restrict__ res) {
+    __shared__ u64 sh[KEPT_TILE];
+    const u32 j = blockIdx.x * KEPT_TILE + threadIdx.x;
+    const bool in = j < n_written;
+    const bool head = in && (j == 0u || index_head(d, j));
+    const u64 incl = kept_block_scan(head ? 1ull : 0ull, sh);
+    if (j == 0u) res->n_runs = tile_base[n_tiles].x;
+    if (!in) return;
+    const u64 k = tile_base[blockIdx.x].x + incl - 1ull;          // the run record j belongs to
+    if (k >= cap) return;
+    if (head) {
+        const IndexRecord b = index_record(d, j);
+        runs[k].tid = b.tid; runs[k].bin = index_bin(b); runs[k].ustart = d.ustart[j]; runs[k].first = j;
+    }
+    if (j == n_written - 1u || index_head(d, j + 1u)) { runs[k].uend = d.ustart[j] + d.bytes[j]; runs[k].last = j + 1u; }
+}
+}  // namespace
+
+void mdx_k_gbam_kept_index(const uint32_t *sizes, const unsigned long long *offsets, const void *kept_tile_base, const int32_t *tid,
+                           const int32_t *pos, const uint32_t *cigar_off, const uint32_t *cigar, uint32_t n_rec, uint32_t n_written,
+                           uint64_t stream_base, const MdxKeptIndex &d, int32_t prev_tid, int32_t prev_pos, int32_t n_ref, const int64_t *ref_len,
+                           const uint64_t *ref_win, unsigned long long *linear, void *tile_sum, void *tile_base, MdxIndexRun *runs,
+                           uint64_t runs_cap, MdxKeptIndexResult *res, hipStream_t s) {
+    if (n_rec == 0 || n_written == 0) return;
+    const uint32_t rec_tiles = (n_rec + KEPT_TILE - 1) / KEPT_TILE, n_tiles = (n_written + KEPT_TILE - 1) / KEPT_TILE;
+    hipLaunchKernelGGL(gbam_index_dense_kernel, dim3(rec_tiles), dim3(KEPT_TILE), 0, s, sizes, offsets, (const ulonglong2 *)kept_tile_base, tid, pos,
+                       cigar_off, cigar, n_rec, n_written, (u64)stream_base, d);
+    hipLaunchKernelGGL(gbam_index_check_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, d, n_written, prev_tid, prev_pos, n_ref, ref_len,
+                       (const u64 *)ref_win, linear, (ulonglong2 *)tile_sum, res);
+    hipLaunchKernelGGL(gbam_kept_tiles_kernel, dim3(1), dim3(KEPT_SCAN_ROUND), 0, s, (const ulonglong2 *)tile_sum, n_tiles, (ulonglong2 *)tile_base);
+    hipLaunchKernelGGL(gbam_index_runs_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, d, n_written, (const ulonglong2 *)tile_base, n_tiles, runs,
+                       (u64)runs_cap, res);
+}

@@ -578,6 +578,35 @@ void mdx_k_gbam_kept_offsets_tagged(const uint8_t *unc, const uint32_t *rec_off,
 void mdx_k_gbam_kept_gather_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets,
                                    uint32_t n_rec, uint8_t *out, const MdxKeptTags &tg, hipStream_t s);
 
+// ... and the BAI index of that stream (--write-index; host side: mdx_gbam_kept_index; the rule: mdx_kept_index.h).  MdxKeptIndex:
+// the dense list of the slab's written records (n_written entries each); MdxIndexRun: a maximal run of written records with
+// the same (tid, bin) — ranks [first, last) of the list, stream offsets [ustart, uend) — as the caller gets it (include/mdx.h
+// mdx_index_run has the same layout); MdxKeptIndexResult: what comes back beside the runs (fail: ~0, or the lowest offending
+// slab index << 2 | MDX_INDEX_UNSORTED / _UNPLACEABLE; last_tid / last_pos: the slab's last written record).
+// mdx_k_gbam_kept_index: sizes / offsets / kept_tile_base as mdx_k_gbam_kept_offsets left them, the view's columns, the
+// header's lengths and each sequence's first word in `linear` (ref_win), tile_sum / tile_base for n_written records.
+struct MdxKeptIndex {
+    int32_t *tid, *pos;
+    int64_t *end;
+    uint32_t *index, *bytes;
+    unsigned long long *ustart;
+};
+struct MdxIndexRun {
+    int32_t tid;
+    uint32_t bin;
+    unsigned long long ustart, uend;
+    uint32_t first, last;
+};
+struct MdxKeptIndexResult {
+    unsigned long long fail, n_runs;
+    int32_t last_tid, last_pos;
+};
+void mdx_k_gbam_kept_index(const uint32_t *sizes, const unsigned long long *offsets, const void *kept_tile_base, const int32_t *tid,
+                           const int32_t *pos, const uint32_t *cigar_off, const uint32_t *cigar, uint32_t n_rec, uint32_t n_written,
+                           uint64_t stream_base, const MdxKeptIndex &d, int32_t prev_tid, int32_t prev_pos, int32_t n_ref, const int64_t *ref_len,
+                           const uint64_t *ref_win, unsigned long long *linear, void *tile_sum, void *tile_base, MdxIndexRun *runs,
+                           uint64_t runs_cap, MdxKeptIndexResult *res, hipStream_t s);
+
 // ---- GPU-side SAM text decode (mdx_gsam.hip; host side: mdx_gsam_* in mdx_samio.cpp)
 // why a slab is given up (status[0] of the kernels; status[1] = the lowest line of the slab that gave a reason)
 enum {

@@ -22,7 +22,7 @@ from .engine import BadReadError, DamageEngine, MdxError
 from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
-from .sam import SAM_BGZF, SAM_GZIP, BAMError, KeptTagClash
+from .sam import SAM_BGZF, SAM_GZIP, BAMError, KeptIndexError, KeptTagClash
 from .statistics import check_table_and_warn_if_dmg_freq_is_low
 
 _LOG_FORMAT = "%(asctime)s %(name)s %(levelname)s %(message)s"
@@ -229,6 +229,11 @@ def build_parser():
     g.add_argument("--tag-pmd-score", default=None, metavar="TAG",
                    help="with --write-kept --by-pmd-score: append TAG:f to every written record, its PMD score (the run's "
                         "fixed-point score as the nearest float32), so that the file can be split at any threshold afterwards")
+    g.add_argument("--write-index", action="store_true",
+                   help="with --write-kept: also write the BAI index of that file, BAM.bai, from the offsets and coordinates the "
+                        "run has on the device — what `samtools index BAM` behind the run would make by inflating the file "
+                        "again.  The written records must be in coordinate order and lie inside the first 2^29 bases of their "
+                        "reference sequences (BAI's limit; CSI is not written); the first one that does not ends the run")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -302,6 +307,8 @@ def _check_write_kept(parser, o):
         parser.error("--tag-pmd-score needs --by-pmd-score: the score is the one that run computes")
     if o.tag_group is not None and o.tag_group == o.tag_pmd_score:
         parser.error("--tag-group and --tag-pmd-score name the same tag, %s: a record has a tag once" % o.tag_group)
+    if getattr(o, "write_index", False) and o.write_kept is None:
+        parser.error("--write-index needs --write-kept: it indexes the file that option writes")
     if o.write_kept is None:
         return
     if o.rescale_only or o.stats_only:
@@ -850,6 +857,14 @@ class _KeptOutput:
         self.n_groups = len(options.strata[0]) if self.groups is not None or tagged else 0
         self.stream, self.folder = stream, options.folder
         self.records = self.raw_bytes = 0
+        # (--write-index: PATH.bai, the name samtools looks for, under a temporary name of its own until the BAM is in place)
+        self.index = None
+        if getattr(options, "write_index", False):
+            from .bai import BaiAssembler
+            self.index = BaiAssembler(stream.header.lengths)
+            self.index_path = Path(str(self.path) + ".bai")
+            self.index_tmp = self.index_path.with_name("%s.%d.tmp" % (self.index_path.name, os.getpid()))
+            self.index_prev = (-1, -1)
         self.writer = BgzfWriter(self.tmp, engine=engine)
         try:
             self.writer.write(bam_header_bytes(stream.header))
@@ -862,21 +877,33 @@ class _KeptOutput:
         view's."""
         self.writer.flush()             # (the one output array is the writer thread's until its write is done)
         members, n, raw = self.stream.write_kept(view, self.groups, self.n_groups, self.group_tag, self.score_tag)
+        if self.index is not None and n:
+            from .bai import member_sizes
+            runs, self.index_prev = self.stream.kept_index(self.raw_bytes, self.index_prev, n)
+            self.index.add_slab(self.raw_bytes, self.writer.bytes_handed, member_sizes(members), raw, runs)
         self.records += n
         self.raw_bytes += raw
         if len(members):
             self.writer.write_members(members)
 
     def commit(self, logger):
+        index = None
+        if self.index is not None:
+            index = self.index.finish(self.stream.kept_index_linear())
+            self.index_tmp.write_bytes(index)
         self.writer.close()             # (the queued writes, then the end-of-file marker)
         self.writer = None
         os.replace(self.tmp, self.path)
+        if index is not None:
+            os.replace(self.index_tmp, self.index_path)
         which = "all" if self.groups is None else ",".join(str(g) for g in self.groups)
         tags = ["%s:S group" % self.group_tag] if self.group_tag is not None else []
         tags += ["%s:f PMD score" % self.score_tag] if self.score_tag is not None else []
         logger.info("Wrote %d records to %s (groups: %s)%s", self.records, self.path, which, "; tags: " + ", ".join(tags) if tags else "")
         (self.folder / "write_kept.tsv").write_text("path\tgroups\trecords\tuncompressed_bytes\n%s\t%s\t%d\t%d\n"
                                                     % (self.path, which, self.records, self.raw_bytes))
+        if index is not None:
+            logger.info("Wrote index %s (%d references with records, %d chunks)", self.index_path, self.index.n_references, self.index.n_chunks)
 
     def _remove(self):
         if self.writer is not None:
@@ -885,10 +912,11 @@ class _KeptOutput:
             except Exception:
                 pass
             self.writer = None
-        try:
-            self.tmp.unlink()
-        except OSError:
-            pass
+        for tmp in (self.tmp,) + ((self.index_tmp,) if self.index is not None else ()):
+            try:
+                tmp.unlink()
+            except OSError:
+                pass
 
     def __enter__(self):
         return self
@@ -1030,8 +1058,9 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
         engine.close()
         return tables, None
-    except KeptTagClash:
-        # (--tag-group / --tag-pmd-score: a record has the tag already — the run's error, no other decoder would do better)
+    except (KeptTagClash, KeptIndexError):
+        # (--tag-group / --tag-pmd-score: a record has the tag already; --write-index: a written record out of order or out of
+        # BAI's reach — the run's error, no other decoder would do better)
         engine.close()
         raise
     except GpuDecodeUnsupported as error:
@@ -1162,6 +1191,13 @@ def main(argv):
                            record_filter=options.record_filter,
                            sam_header_only=options.gpu_decode and _device_path_applies(options, ranks.world))
         reflengths = reader.get_references()
+        if options.write_index:
+            too_long = [(name, int(length)) for name, length in zip(reader.handle.header.references, reader.handle.header.lengths)
+                        if int(length) > 1 << 29]
+            if too_long:
+                logger.error("--write-index: reference sequence %s has %d bases, and BAI cannot address a position behind 2^29 = "
+                             "536870912; CSI, the index format that can, is not written", *too_long[0])
+                return 1
         if not is_plain_gzip(options.ref):
             # (pysam.FastaFile indexes a file that has no index, main.py:115; a bgzip-compressed one gets .fai and .gzi)
             try:
@@ -1225,7 +1261,7 @@ def main(argv):
 
         try:
             tables, carry = _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages) if options.gpu_decode else (None, None)
-        except KeptTagClash as error:
+        except (KeptTagClash, KeptIndexError) as error:
             logger.error("%s", error)
             return 1
         if tables is None and options.write_kept is not None:

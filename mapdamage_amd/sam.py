@@ -402,6 +402,9 @@ class BgzfWriter:
         self._tail = b""
         self._pending = deque()
         self._max_pending = max_pending
+        # (engine: the members' bytes handed to the file so far, whether its thread has written them or not — where the
+        # next ``write_members`` will lie in the file)
+        self.bytes_handed = 0
 
     def _drain(self, keep):
         """Write the finished blocks at the head of the queue; wait for the oldest ones while more than ``keep`` are queued."""
@@ -418,6 +421,7 @@ class BgzfWriter:
         if self._engine is not None:
             if len(view):
                 members = self._engine.bgzf_deflate(view)
+                self.bytes_handed += len(memoryview(members.data).cast("B"))
                 self._pending.append(self._pool.submit(self._out.write, members.data))
                 while len(self._pending) > 2:           # (two pieces' members waiting for the disk at most)
                     self._pending.popleft().result()
@@ -435,6 +439,7 @@ class BgzfWriter:
     def write_members(self, members):
         """Append finished BGZF members (the device's: ``GpuBamStream.rescale_slab``) as they are."""
         assert not self._tail
+        self.bytes_handed += len(memoryview(members).cast("B"))
         self._pending.append(self._pool.submit(self._out.write, memoryview(members)))
         while len(self._pending) > 2:
             self._pending.popleft().result()
@@ -793,6 +798,51 @@ class GpuBamStream:
             raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
         return out[:out_len.value], int(n_written.value), int(raw_bytes.value)
 
+    def kept_index(self, stream_base, prev, n_written):
+        """The index entries of the records the last ``write_kept`` of this view wrote (include/mdx.h ``mdx_gbam_kept_index``;
+        the rule: csrc/mdx_kept_index.h): ``(runs, prev)`` — ``runs`` a ``bai.RUN_DTYPE`` array, the maximal runs of written
+        records with the same (tid, bin) in file order, their bytes as offsets of the uncompressed stream, ``stream_base`` (the
+        raw bytes of all earlier slabs) + the offset in this slab's; ``prev`` = ``(tid, pos)`` of the last written record in
+        front of the slab (``(-1, -1)``: none), returned as this slab's last.  ``n_written``: what ``write_kept`` returned.  A
+        written record out of coordinate order or outside its reference sequence: ``KeptIndexError`` with its index in the
+        slab and its name.  ``MdxError`` -3 unless the call comes right behind ``write_kept`` of the view handed out last."""
+        import ctypes
+        from .bai import RUN_DTYPE
+        runs = np.zeros(max(1, int(n_written)), RUN_DTYPE)
+        tid, pos = ctypes.c_int32(int(prev[0])), ctypes.c_int32(int(prev[1]))
+        n_runs, bad, reason = ctypes.c_int64(0), ctypes.c_int64(-1), ctypes.c_int32(0)
+        fn = self._lib.mdx_gbam_kept_index
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        rc = fn(self._g, ctypes.c_int64(int(stream_base)), ctypes.byref(tid), ctypes.byref(pos), ctypes.c_void_p(runs.ctypes.data),
+                ctypes.c_int64(int(n_written)), ctypes.byref(n_runs), ctypes.byref(bad), ctypes.byref(reason))
+        if rc == -6 and bad.value >= 0:
+            name = ctypes.create_string_buffer(256)
+            self._lib.mdx_gbam_record_name(self._g, ctypes.c_int64(bad.value), name, 256)
+            raise KeptIndexError(bad.value, name.value.decode(errors="replace"), reason.value)
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        return runs[:n_runs.value], (int(tid.value), int(pos.value))
+
+    def kept_index_linear(self):
+        """The linear index all ``kept_index`` calls of this stream left on the device (``mdx_gbam_kept_index_linear``): one
+        uint64 per 16 KiB window of every header sequence in turn, the lowest stream offset of a written record that touches
+        it, all ones for an untouched window."""
+        import ctypes
+        fn = self._lib.mdx_gbam_kept_index_linear
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p], ctypes.c_int
+        words = ctypes.c_int64(0)
+        rc = fn(self._g, None, ctypes.c_int64(0), ctypes.byref(words))
+        out = np.zeros(max(1, words.value), np.uint64)
+        if rc == 0:
+            rc = fn(self._g, ctypes.c_void_p(out.ctypes.data), ctypes.c_int64(words.value), None)
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        return out[:words.value]
+
     def fixups(self):
         """BGZF blocks whose guessed first record was not where the chain of the records in front of it ended (rescanned
         from the right offset: the result is exact either way)."""
@@ -1043,6 +1093,21 @@ class KeptTagClash(Exception):
         super().__init__("Read: %s already has a tag named %s; the run appends such a tag to every record it writes "
                          "(choose another name)" % (name, " or ".join(tags)))
         self.index, self.name, self.tags = int(index), name, list(tags)
+
+
+class KeptIndexError(Exception):
+    """``GpuBamStream.kept_index``: a record that is written cannot be indexed (MDX_ERR_BAD_READ, ``code`` -6) — ``reason``
+    1: it lies in front of the written record before it, 2: it does not lie inside the first 2^29 bases of a header sequence.
+    ``index``: the record's index in its slab, ``name``: its read name."""
+    code = -6
+    UNSORTED, UNPLACEABLE = 1, 2
+
+    def __init__(self, index, name, reason):
+        why = ("lies in front of the written record before it; an index needs the written records in coordinate order (sort the "
+               "input first)" if int(reason) == self.UNSORTED else
+               "does not lie inside its reference sequence, or ends behind base 2^29, which BAI cannot address")
+        super().__init__("Read: %s is to be written and %s" % (name, why))
+        self.index, self.name, self.reason = int(index), name, int(reason)
 
 
 class BamStream:

@@ -7,15 +7,19 @@ one BAM, then three commands timed as cold processes, each under a time limit of
   --tags adds two more:
   pmd_all     `--by-pmd-score --pmd-thresholds 3 --write-kept pmd_all.bam`                               every counted record
   pmd_tagged  the same with `--tag-group XG --tag-pmd-score DS`                                          ... with its two tags
+  --index instead: the records in coordinate order (synth's sort=True), and the legs
+  plain, kept as above, and
+  kept_index  `--write-kept kept_index.bam --write-index`                                                ... and its BAI index
 
 The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
 times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
 (write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost, pmd_tagged - pmd_all that
-of the tags (12 bytes a record, the score column, the walk over every written record's tags).  --parent-root DIR: a
+of the tags (12 bytes a record, the score column, the walk over every written record's tags), kept_index - kept that of the
+index (four launches and two small copies per slab, the file's assembly on the host).  --parent-root DIR: a
 built checkout of the parent commit; `plain` is then also timed there, in the same alternation — a difference between the two
 beyond the spread means the option-less path has changed.  One JSON line on stdout.
 
-    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags]"""
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index]"""
 import argparse
 import json
 import os
@@ -48,6 +52,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
     ap.add_argument("--tags", action="store_true", help="also time --by-pmd-score --write-kept with and without --tag-group / --tag-pmd-score")
+    ap.add_argument("--index", action="store_true", help="coordinate-sorted records; time --write-kept with and without --write-index")
     args = ap.parse_args()
     import numpy as np
 
@@ -58,7 +63,12 @@ def main():
         ref = synth.make_genome()
         bam, fa = os.path.join(work, "x.bam"), os.path.join(work, "x.fa")
         t0 = time.perf_counter()
-        batch = synth.config3_batch(ref, args.reads, seed=args.seed, with_qual=True)
+        if args.index:
+            # (config-3's records — synth.config3_batch — in coordinate order)
+            batch = synth.make_reads(ref, args.reads, args.seed, read_len=100, paired=True, frac_softclip=0.10, frac_ins=0.04, frac_del=0.04,
+                                     frac_skip=0.002, frac_hardclip=0.001, contigs=[0, 1], with_qual=True, sort=True)
+        else:
+            batch = synth.config3_batch(ref, args.reads, seed=args.seed, with_qual=True)
         sam.write_bam(bam, batch, ref.names, ref.lengths, [{"ID": "rg1", "SM": "synthetic", "LB": "lib1"}],
                       rg_of_record=["rg1"] * args.reads)
         fasta.write_fasta(fa, ref)
@@ -69,6 +79,9 @@ def main():
         base = [sys.executable, "-m", "mapdamage_amd", "-i", bam, "-r", fa, "--no-stats", "--log-level", "DEBUG"]
         legs = [("plain", ROOT, []), ("kept", ROOT, ["--write-kept", os.path.join(work, "kept.bam")]),
                 ("pmd", ROOT, ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept", os.path.join(work, "pmd.bam"), "--write-groups", "1"])]
+        if args.index:
+            legs = legs[:2] + [("kept_index", ROOT, ["--write-kept", os.path.join(work, "kept_index.bam"), "--write-index"])]
+            result["sorted"] = True
         if args.tags:
             pmd_all = ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept"]
             legs += [("pmd_all", ROOT, pmd_all + [os.path.join(work, "pmd_all.bam")]),
@@ -100,8 +113,17 @@ def main():
                 path, groups, records, raw = open(tsv).read().splitlines()[1].split("\t")
                 result[name].update(groups=groups, records_written=int(records), uncompressed_bytes=int(raw), file_bytes=os.path.getsize(path))
         if status == 0:
-            for name in ("kept", "pmd"):
+            for name in ("kept",) if args.index else ("kept", "pmd"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            if args.index:
+                result["kept_index_minus_kept_s"] = round(result["kept_index"]["median_s"] - result["kept"]["median_s"], 3)
+                bai = os.path.join(work, "kept_index.bam.bai")
+                result["kept_index"]["index_bytes"] = os.path.getsize(bai) if os.path.exists(bai) else None
+                line = [ln for ln in open(os.path.join(work, "kept_index", "Runtime_log.txt")).read().splitlines() if "Wrote index" in ln]
+                result["kept_index"]["log"] = line[-1].split(" (", 1)[1].rstrip(")") if line else None
+                same_file = open(os.path.join(work, "kept.bam"), "rb").read() == open(os.path.join(work, "kept_index.bam"), "rb").read()
+                if not same_file or result["kept_index"]["index_bytes"] is None:
+                    result["error"] = "kept_index.bam differs from kept.bam, or no index was written"
             if args.tags:
                 result["pmd_tagged_minus_pmd_all_s"] = round(result["pmd_tagged"]["median_s"] - result["pmd_all"]["median_s"], 3)
                 extra = result["pmd_tagged"]["uncompressed_bytes"] - result["pmd_all"]["uncompressed_bytes"]
