@@ -97,6 +97,11 @@ const Rccl *rccl() {
 }
 }  // namespace
 
+// the kinds of groups a context can hold, and for a refusal what each is called and the call that sets it
+enum StrataKind { STRATA_NONE, STRATA_TID, STRATA_REGIONS, STRATA_DAMAGE, STRATA_PMD };
+static const struct { const char *label, *setter; } kStrataKinds[] = {
+    {"no", "none"}, {"tid", "mdx_set_strata"}, {"region", "mdx_set_strata_regions"}, {"damage", "mdx_set_strata_damage"}, {"PMD", "mdx_set_strata_pmd"}};
+
 struct mdx_ctx {
     void *comm = nullptr;      // ncclComm_t
     bool comm_owned = false;
@@ -153,34 +158,32 @@ struct mdx_ctx {
     const void *libsort_checked = nullptr;   // the batch's own blob (mdx_batch::libsort) whose signature was read back last
     uint64_t libsort_checked_sig = 0;        // ... and that signature
     DevBuf ml_partials;    // ... and the plan of a launch over several libraries: which library a pool of blocks counts (MdxTabArgs::ml_plan)
-    // strata (mdx_set_strata): cfg.nlib = libraries x n_groups tables, a record's table lib * n_groups + group_of_tid[tid]
-    int n_groups = 0;              // 0: not stratified
-    int32_t *d_group_of_tid = nullptr;
-    unsigned long long *d_strata_kept = nullptr;   // [cfg.nlib]: the records the flag filter kept, per stratum
-    int strata_n_contig = 0;
-    // ... or (mdx_set_strata_regions) the group of the first interval the record overlaps: one allocation, resident for the
-    // context's life — [iv_off n_contig + 1][iv_start][iv_end][iv_group]
-    void *d_regions = nullptr;
-    MdxRegions regions = {};
-    // ... or (mdx_set_strata_damage) from the record's own terminal substitutions: none, 5p, 3p, both
-    int damage_positions = 0;      // > 0: damage strata, the terminal columns looked at
-    int damage_single_stranded = 0;
-    // ... or (mdx_set_strata_pmd) from the record's post-mortem damage score: the number of thresholds it reaches
-    int pmd_n_thresholds = 0;      // > 0: PMD strata
-    int pmd_single_stranded = 0;
-    int64_t pmd_thresholds[MDX_PMD_MAX_THRESHOLDS] = {};
-    int32_t *d_pmd_terms = nullptr;            // [2][MDX_PMD_Z][MDX_PMD_QCOLS]
-    unsigned long long *d_pmd_hist = nullptr;  // [libraries][MDX_PMD_BINS] and one word: the kept records scored without qualities
-    DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
-    const uint16_t *strata_key_flag = nullptr;   // ... the flag column and n_reads of the batch it was made for (mdx_gbam_write_kept
-    int64_t strata_key_n = 0;                    // writes chosen groups of the view it was handed only behind that view's launch)
-    uint64_t strata_key_serial = 0;              // ... and how many batches have been keyed so far
-    // (mdx_strata_pmd_keep_scores) the PMD key kernel also leaves every record's score, as the float of a score tag: the column
-    // of the batch keyed last, and the strata_key_serial it belongs to (0: none — nothing keyed since the switch, or the last
-    // batch brought its buckets and was not keyed)
-    bool pmd_keep_scores = false;
-    DevBuf pmd_scores;
-    uint64_t pmd_scores_serial = 0;
+    // strata: cfg.nlib = libraries x n_groups tables, a record's table lib * n_groups + its group.  A context has one kind of
+    // groups (begin_strata), and everything that depends on the kind switches on `kind`.
+    struct Strata {
+        StrataKind kind = STRATA_NONE;
+        int n_groups = 0;              // 0: not stratified
+        unsigned long long *d_strata_kept = nullptr;   // [cfg.nlib]: the records the flag filter kept, per stratum
+        int32_t *d_group_of_tid = nullptr;     // STRATA_TID: the group of the record's sequence, group_of_tid[tid]
+        int strata_n_contig = 0;               // STRATA_TID, STRATA_REGIONS: the sequences the setter named
+        void *d_regions = nullptr;             // STRATA_REGIONS: the group of the first interval the record overlaps — one allocation,
+        MdxRegions regions = {};               // [iv_off n_contig + 1][iv_start][iv_end][iv_group], and the pointers into it
+        int damage_positions = 0, damage_single_stranded = 0;   // STRATA_DAMAGE: none, 5p, 3p, both by the terminal columns looked at
+        int pmd_n_thresholds = 0, pmd_single_stranded = 0;      // STRATA_PMD: the number of thresholds the record's score reaches
+        int64_t pmd_thresholds[MDX_PMD_MAX_THRESHOLDS] = {};
+        int32_t *d_pmd_terms = nullptr;            // [2][MDX_PMD_Z][MDX_PMD_QCOLS]
+        unsigned long long *d_pmd_hist = nullptr;  // [libraries][MDX_PMD_BINS] and one word: the kept records scored without qualities
+        DevBuf strata_key;             // the key column of the batch being launched (the caller's lib column is not rewritten)
+        const uint16_t *strata_key_flag = nullptr;   // ... the flag column and n_reads of the batch it was made for (mdx_gbam_write_kept
+        int64_t strata_key_n = 0;                    // writes chosen groups of the view it was handed only behind that view's launch)
+        uint64_t strata_key_serial = 0;              // ... and how many batches have been keyed so far
+        // (mdx_strata_pmd_keep_scores) the PMD key kernel also leaves every record's score, as the float of a score tag: the column
+        // of the batch keyed last, and the strata_key_serial it belongs to (0: none — nothing keyed since the switch, or the last
+        // batch brought its buckets and was not keyed)
+        bool pmd_keep_scores = false;
+        DevBuf pmd_scores;
+        uint64_t pmd_scores_serial = 0;
+    } strata;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -231,16 +234,30 @@ int64_t lgd_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * c->cfg.l
 int64_t mis_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * c->cfg.length * MDX_N_MIS_COLS; }
 int64_t comp_words(const mdx_ctx *c) { return (int64_t)c->cfg.nlib * 4 * (c->cfg.length + c->cfg.around) * 4; }
 
-size_t pmd_hist_words(const mdx_ctx *c) { return (size_t)(c->cfg.nlib / (c->pmd_n_thresholds + 1)) * MDX_PMD_BINS + 1; }
+size_t pmd_hist_words(const mdx_ctx *c) { return (size_t)(c->cfg.nlib / (c->strata.pmd_n_thresholds + 1)) * MDX_PMD_BINS + 1; }
 
 int zero_accumulators(mdx_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(c->d_raw, 0, (size_t)c->dims.w_total * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_lgd_dense, 0, (size_t)lgd_words(c) * 8 * c->lgd_copies, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_n_lgd_over, 0, 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, 8, c->stream));
-    if (c->d_strata_kept) HIP_TRY(c, hipMemsetAsync(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8, c->stream));
-    if (c->d_pmd_hist) HIP_TRY(c, hipMemsetAsync(c->d_pmd_hist, 0, pmd_hist_words(c) * 8, c->stream));
+    if (c->strata.d_strata_kept) HIP_TRY(c, hipMemsetAsync(c->strata.d_strata_kept, 0, (size_t)c->cfg.nlib * 8, c->stream));
+    if (c->strata.d_pmd_hist) HIP_TRY(c, hipMemsetAsync(c->strata.d_pmd_hist, 0, pmd_hist_words(c) * 8, c->stream));
     return MDX_OK;
+}
+
+// what the damage and the PMD key read of the device batch b and of the context's reference (MdxDamageKey, MdxPmdKey)
+template <class Key>
+Key key_args(const mdx_ctx *c, const mdx_batch *b) {
+    Key k{};
+    k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
+    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos;
+    k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off; k.seq = b->seq;
+    k.seq_packed = b->seq_format != MDX_SEQ_ASCII;
+    k.ref = c->d_ref + 256;   // (kRefPad)
+    k.contig_off = c->d_contig_off; k.n_contig = c->n_contig;
+    k.n_libraries = c->cfg.nlib / c->strata.n_groups;
+    return k;
 }
 
 }  // namespace
@@ -399,8 +416,8 @@ void mdx_destroy(mdx_ctx *c) {
     c->lowq.release();
     c->libsort.release();
     c->libsort_scratch.release();
-    c->strata_key.release();
-    c->pmd_scores.release();
+    c->strata.strata_key.release();
+    c->strata.pmd_scores.release();
     c->ml_partials.release();
     c->rs_part.release();
     c->rs_lists.release();
@@ -410,7 +427,7 @@ void mdx_destroy(mdx_ctx *c) {
         if (c->pin_done[i]) (void)hipEventDestroy(c->pin_done[i]);
     }
     void *ptrs[] = {c->d_ref, c->d_ref4, c->d_contig_off, c->d_raw, c->d_lgd_dense, c->d_lgd_over,
-                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->d_group_of_tid, c->d_regions, c->d_strata_kept, c->d_pmd_terms, c->d_pmd_hist};
+                    c->d_n_lgd_over, c->d_err, c->d_partials, c->d_lut, c->d_term, c->d_subs, c->d_tile_ctr, c->strata.d_group_of_tid, c->strata.d_regions, c->strata.d_strata_kept, c->strata.d_pmd_terms, c->strata.d_pmd_hist};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -573,71 +590,75 @@ static uint64_t libsort_signature(int64_t n, int64_t n_cigar, int64_t n_bases, i
     for (uint64_t v : {(uint64_t)n, (uint64_t)n_cigar, (uint64_t)n_bases, (uint64_t)nlib | (uint64_t)n_groups << 32}) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xBF58476D1CE4E5B9ull; }
     return h | 1ull;
 }
-// A stratified context (mdx_set_strata, mdx_set_strata_regions, mdx_set_strata_damage): *out = the device batch b with the key column — library x
-// groups + group of the record's sequence, of the first region it overlaps, or of the damage its ends show — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the
-// stream; valid until the next such call).  count: the kept records are added to the context's counts per stratum.
 // The PMD key (mdx_set_strata_pmd) of the device batch b into `key` (null: none is written), its kept records counted per
 // stratum (count) and into the score histogram (hist).
 // (MDX_PMD_LANE=1 in the environment: the trivial kernel, a lane per record; MDX_PMD_NO_LDS=1: the cooperative kernel with every
 // term read from global memory — for A/B runs, read at every call)
 static int pmd_key(mdx_ctx *c, const mdx_batch *b, uint16_t *key, float *score, bool count, bool hist) {
-    if (!c->d_ref) return fail(c, MDX_ERR_STATE, "PMD strata (mdx_set_strata_pmd) read the reference: mdx_set_reference has not been called");
     const char *e = getenv("MDX_PMD_LANE"), *e2 = getenv("MDX_PMD_NO_LDS");
     const int form = e && *e && *e != '0' ? 1 : e2 && *e2 && *e2 != '0' ? 2 : 0;
-    MdxPmdKey k{};
-    k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
-    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos;
-    k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off; k.seq = b->seq; k.qual = b->qual;
-    k.seq_packed = b->seq_format != MDX_SEQ_ASCII;
-    k.ref = c->d_ref + 256;   // (kRefPad)
-    k.contig_off = c->d_contig_off; k.n_contig = c->n_contig;
-    k.n_libraries = c->cfg.nlib / c->n_groups;
-    k.n_thresholds = c->pmd_n_thresholds; k.single_stranded = c->pmd_single_stranded;
-    k.terms = c->d_pmd_terms;
-    for (int t = 0; t < c->pmd_n_thresholds; t++) k.thresholds[t] = c->pmd_thresholds[t];
-    mdx_k_strata_pmd_key(k, key, score, count ? c->d_strata_kept : nullptr, hist ? c->d_pmd_hist : nullptr, form, c->stream);
+    MdxPmdKey k = key_args<MdxPmdKey>(c, b);
+    k.qual = b->qual;
+    k.n_thresholds = c->strata.pmd_n_thresholds; k.single_stranded = c->strata.pmd_single_stranded;
+    k.terms = c->strata.d_pmd_terms;
+    for (int t = 0; t < c->strata.pmd_n_thresholds; t++) k.thresholds[t] = c->strata.pmd_thresholds[t];
+    mdx_k_strata_pmd_key(k, key, score, count ? c->strata.d_strata_kept : nullptr, hist ? c->strata.d_pmd_hist : nullptr, form, c->stream);
     HIP_TRY(c, hipGetLastError());
     return MDX_OK;
 }
 
+// damage and PMD strata key a batch by what its records show against the reference: refused before mdx_set_reference
+static int strata_needs_reference(mdx_ctx *c, const char *who) {
+    if ((c->strata.kind != STRATA_DAMAGE && c->strata.kind != STRATA_PMD) || c->d_ref) return MDX_OK;
+    return fail(c, MDX_ERR_STATE, std::string(who) + ": " + kStrataKinds[c->strata.kind].label + " strata (" + kStrataKinds[c->strata.kind].setter +
+                                      ") key the batch by a rule that reads the reference; call mdx_set_reference first");
+}
+
+// A stratified context: *out = the device batch b with the key column — library x groups + the group its kind's rule gives
+// the record — in place of its lib column, made by a small kernel into the context's scratch column (enqueued on the stream;
+// valid until the next such call).  count: the kept records are added to the context's counts per stratum.
 static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool count) {
     *out = *b;
-    if (c->n_groups <= 0 || b->n_reads == 0) return MDX_OK;
-    HIP_TRY(c, c->strata_key.reserve((size_t)b->n_reads * 2 + 64));
+    if (c->strata.kind == STRATA_NONE || b->n_reads == 0) return MDX_OK;
+    HIP_TRY(c, c->strata.strata_key.reserve((size_t)b->n_reads * 2 + 64));
+    uint16_t *const key = (uint16_t *)c->strata.strata_key.p;
+    unsigned long long *const kept = count ? c->strata.d_strata_kept : nullptr;
+    const int n_libraries = c->cfg.nlib / c->strata.n_groups;
     bool scored = false;
-    if (c->pmd_n_thresholds > 0) {
+    switch (c->strata.kind) {
+    case STRATA_PMD: {
         // (mdx_strata_pmd_keep_scores: the scores of this batch beside its keys)
-        if (c->pmd_keep_scores) HIP_TRY(c, c->pmd_scores.reserve((size_t)b->n_reads * 4 + 64));
-        scored = c->pmd_keep_scores;
-        const int rc = pmd_key(c, b, (uint16_t *)c->strata_key.p, scored ? (float *)c->pmd_scores.p : nullptr, count, count);
-        if (rc != MDX_OK) return rc;
-    } else if (c->damage_positions > 0) {
+        if (c->strata.pmd_keep_scores) HIP_TRY(c, c->strata.pmd_scores.reserve((size_t)b->n_reads * 4 + 64));
+        scored = c->strata.pmd_keep_scores;
+        if (const int rc = pmd_key(c, b, key, scored ? (float *)c->strata.pmd_scores.p : nullptr, count, count); rc != MDX_OK) return rc;
+        break;
+    }
+    case STRATA_DAMAGE: {
         // (the key reads the batch as the caller brings it — under --min-basequal the mask from the nibbles of a MDX_SEQ_4BITQ
         // column, else from the qualities or the caller's bitmap of them, as the launch's own fold would take it)
-        if (!c->d_ref) return fail(c, MDX_ERR_STATE, "damage strata (mdx_set_strata_damage) read the reference: mdx_set_reference has not been called");
-        MdxDamageKey k{};
-        k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
-        k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos;
-        k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off; k.seq = b->seq;
-        k.seq_packed = b->seq_format != MDX_SEQ_ASCII; k.seq_folded = b->seq_format == MDX_SEQ_4BITQ;
+        MdxDamageKey k = key_args<MdxDamageKey>(c, b);
+        k.seq_folded = b->seq_format == MDX_SEQ_4BITQ;
         k.minqual = c->cfg.minqual;
         k.qual = c->cfg.minqual > 0 ? b->qual : nullptr;
         k.lowq = c->cfg.minqual > 0 && b->qual && b->seq_format == MDX_SEQ_4BIT ? b->lowq : nullptr;
-        k.ref = c->d_ref + 256;   // (kRefPad)
-        k.contig_off = c->d_contig_off; k.n_contig = c->n_contig;
-        k.n_libraries = c->cfg.nlib / c->n_groups;
-        k.positions = c->damage_positions; k.single_stranded = c->damage_single_stranded;
-        mdx_k_strata_damage_key(k, (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
-    } else if (c->d_regions)
-        mdx_k_strata_region_key(b->n_reads, b->flag, b->lib, b->tid, b->pos, b->cigar_off, b->cigar, b->n_cigar, c->regions, c->n_groups,
-                                c->cfg.nlib / c->n_groups, (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
-    else
-        mdx_k_strata_key(b->n_reads, b->flag, b->lib, b->tid, c->d_group_of_tid, c->strata_n_contig, c->n_groups, c->cfg.nlib / c->n_groups,
-                         (uint16_t *)c->strata_key.p, count ? c->d_strata_kept : nullptr, c->stream);
+        k.positions = c->strata.damage_positions; k.single_stranded = c->strata.damage_single_stranded;
+        mdx_k_strata_damage_key(k, key, kept, c->stream);
+        break;
+    }
+    case STRATA_REGIONS:
+        mdx_k_strata_region_key(b->n_reads, b->flag, b->lib, b->tid, b->pos, b->cigar_off, b->cigar, b->n_cigar, c->strata.regions, c->strata.n_groups,
+                                n_libraries, key, kept, c->stream);
+        break;
+    case STRATA_TID:
+        mdx_k_strata_key(b->n_reads, b->flag, b->lib, b->tid, c->strata.d_group_of_tid, c->strata.strata_n_contig, c->strata.n_groups, n_libraries, key, kept,
+                         c->stream);
+        break;
+    case STRATA_NONE: break;
+    }
     HIP_TRY(c, hipGetLastError());
-    out->lib = (const uint16_t *)c->strata_key.p;
-    c->strata_key_flag = b->flag; c->strata_key_n = b->n_reads; c->strata_key_serial++;
-    c->pmd_scores_serial = scored ? c->strata_key_serial : 0;
+    out->lib = key;
+    c->strata.strata_key_flag = b->flag; c->strata.strata_key_n = b->n_reads; c->strata.strata_key_serial++;
+    c->strata.pmd_scores_serial = scored ? c->strata.strata_key_serial : 0;
     return MDX_OK;
 }
 
@@ -646,7 +667,7 @@ static int strata_view(mdx_ctx *c, const mdx_batch *b, mdx_batch *out, bool coun
 static int build_libsort(mdx_ctx *c, const mdx_batch *b, void *blob) {
     MdxLibSort ls;
     mdx_k_libsort_layout(blob, b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, &ls);
-    const uint64_t sig = libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->n_groups);
+    const uint64_t sig = libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->strata.n_groups);
     HIP_TRY(c, hipMemcpyAsync((char *)blob + 8, &sig, 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, c->libsort_scratch.reserve(mdx_k_libsort_scratch_bytes(b->n_reads, c->cfg.nlib)));
     mdx_k_libsort(b->n_reads, b->n_cigar, b->n_bases, b->flag, b->lib, b->tid, b->pos, b->tlen, b->cigar_off, b->cigar, b->seq_off, b->seq,
@@ -659,11 +680,8 @@ int mdx_batch_upload(mdx_ctx *c, const mdx_batch *h, mdx_batch *dv) {
     int rc = check_batch(c, h);
     if (rc != MDX_OK) return rc;
     if (!dv) return MDX_ERR_ARG;
-    // (PMD strata, damage strata: the resident batch is bucketed by a key that reads the reference)
-    if (c->pmd_n_thresholds > 0 && !c->d_ref)
-        return fail(c, MDX_ERR_STATE, "mdx_batch_upload: a context with mdx_set_strata_pmd buckets the batch by a key that reads the reference; call mdx_set_reference first");
-    if (c->damage_positions > 0 && !c->d_ref)
-        return fail(c, MDX_ERR_STATE, "mdx_batch_upload: a context with mdx_set_strata_damage buckets the batch by a key that reads the reference; call mdx_set_reference first");
+    // (the resident batch is bucketed by its key)
+    if ((rc = strata_needs_reference(c, "mdx_batch_upload")) != MDX_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     std::memset(dv, 0, sizeof(*dv));
     dv->n_reads = h->n_reads; dv->n_cigar = h->n_cigar; dv->n_bases = h->n_bases;
@@ -785,21 +803,26 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
     // A stratified context: the launches read the key column in place of the batch's lib column — all of them but the launch
     // over a batch that brings its own columns bucketed by stratum, which reads neither
     mdx_batch b_key;
-    if (c->n_groups > 0) {
-        if (fuse) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
-        if (c->damage_positions == 0 && c->pmd_n_thresholds == 0 && c->strata_n_contig != c->n_contig)
-            return fail(c, MDX_ERR_ARG, std::string(c->d_regions ? "mdx_set_strata_regions" : "mdx_set_strata") + " named " + std::to_string(c->strata_n_contig) + " sequences, the reference has " +
-                                        std::to_string(c->n_contig));
+    if (c->strata.kind != STRATA_NONE) {
+        switch (c->strata.kind) {      // (never with fuse: tabulate_rescale_impl refuses a stratified context)
+        case STRATA_TID: case STRATA_REGIONS:
+            if (c->strata.strata_n_contig != c->n_contig)
+                return fail(c, MDX_ERR_ARG, std::string(kStrataKinds[c->strata.kind].setter) + " named " + std::to_string(c->strata.strata_n_contig) +
+                                            " sequences, the reference has " + std::to_string(c->n_contig));
+            break;
+        default:
+            if ((rc = strata_needs_reference(c, "mdx_tabulate")) != MDX_OK) return rc;
+        }
         if (!(ml && b_in->libsort)) {
             rc = strata_view(c, b_in, &b_key, true);
             if (rc != MDX_OK) return rc;
             b_in = &b_key;
-        } else if (c->pmd_n_thresholds > 0) {
+        } else if (c->strata.kind == STRATA_PMD) {
             // (a batch that brings its buckets is not keyed again — their sizes are the kept counts —, but its scores are not
             // in the histogram yet: the key kernel over the batch's own columns, for the histogram alone)
             rc = pmd_key(c, b_in, nullptr, nullptr, false, true);
             if (rc != MDX_OK) return rc;
-            c->pmd_scores_serial = 0;   // (the score column is another batch's)
+            c->strata.pmd_scores_serial = 0;   // (the score column is another batch's)
         }
     }
     c->counted = true;
@@ -988,7 +1011,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
                     c->libsort_checked = blob;
                     c->libsort_checked_sig = sig;
                 }
-                if (c->libsort_checked_sig != libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->n_groups))
+                if (c->libsort_checked_sig != libsort_signature(b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, c->strata.n_groups))
                     return fail(c, MDX_ERR_ARG, "mdx_batch::libsort was built for another batch or a context with another number of libraries: "
                                                 "upload the batch with the context that tabulates it, whole");
             }
@@ -1004,7 +1027,7 @@ static int tabulate_impl(mdx_ctx *c, const mdx_batch *b_in, const MdxFuse *fuse,
             MdxLibSort ls;
             mdx_k_libsort_layout(const_cast<void *>(blob), b->n_reads, b->n_cigar, b->n_bases, c->cfg.nlib, &ls);
             // (strata, a batch that brings its buckets: their sizes are the kept records per stratum — no key kernel has counted them)
-            if (c->n_groups > 0 && b->libsort && lo == 0) mdx_k_strata_kept_from_sort(ls.lib_start, c->cfg.nlib, c->d_strata_kept, c->stream);
+            if (c->strata.n_groups > 0 && b->libsort && lo == 0) mdx_k_strata_kept_from_sort(ls.lib_start, c->cfg.nlib, c->strata.d_strata_kept, c->stream);
             a.flag = ls.flag; a.tid = ls.tid; a.pos = ls.pos; a.tlen = ls.tlen;
             a.cigar_off = ls.cigar_off; a.cigar = ls.cigar; a.seq_off = ls.seq_off; a.seq = ls.seq;
             a.perm = ls.perm; a.lib_start = ls.lib_start; a.sort_bad = ls.bad;
@@ -1333,31 +1356,41 @@ int mdx_reset(mdx_ctx *c) {
     return MDX_OK;
 }
 
+// What every mdx_set_strata* call does behind its own argument checks: the context's tables are libraries x n_groups, nothing
+// is counted yet, and it holds no other kind of groups (the same kind again replaces the earlier setting); then the stream is
+// idle and the kept counts exist.  The context is unstratified until the caller sets kind and n_groups at its end.
+static int begin_strata(mdx_ctx *c, StrataKind kind, int n_groups) {
+    const std::string who = std::string(kStrataKinds[kind].setter + 4) + ": ";
+    if (c->cfg.nlib % n_groups != 0)
+        return fail(c, MDX_ERR_ARG, who + "the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of " + std::to_string(n_groups) +
+                                    " groups (create it with nlib = libraries x groups)");
+    if (c->counted) return fail(c, MDX_ERR_STATE, who + "records have been counted already (mdx_reset first)");
+    if (c->strata.kind != STRATA_NONE && c->strata.kind != kind)
+        return fail(c, MDX_ERR_STATE, who + "the context has " + kStrataKinds[c->strata.kind].label + " strata (" + kStrataKinds[c->strata.kind].setter +
+                                      "); a context has one kind");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!c->strata.d_strata_kept) {
+        HIP_TRY(c, hipMalloc((void **)&c->strata.d_strata_kept, (size_t)c->cfg.nlib * 8));
+        HIP_TRY(c, hipMemset(c->strata.d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
+    }
+    c->strata.kind = STRATA_NONE;
+    c->strata.n_groups = 0;
+    return MDX_OK;
+}
+
 int mdx_set_strata(mdx_ctx *c, int32_t n_groups, const int32_t *group_of_tid, int32_t n_contig) {
     if (!c) return MDX_ERR_ARG;
     if (n_groups < 1 || n_contig < 1 || !group_of_tid) return fail(c, MDX_ERR_ARG, "set_strata: bad arguments");
-    if (c->cfg.nlib % n_groups != 0)
-        return fail(c, MDX_ERR_ARG, "set_strata: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of " +
-                                    std::to_string(n_groups) + " groups (create it with nlib = libraries x groups)");
     for (int32_t t = 0; t < n_contig; t++)
         if (group_of_tid[t] < 0 || group_of_tid[t] >= n_groups)
             return fail(c, MDX_ERR_ARG, "set_strata: the group of sequence " + std::to_string(t) + " is outside [0, n_groups)");
-    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata: records have been counted already (mdx_reset first)");
-    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata: the context has region strata (mdx_set_strata_regions); a context has one kind");
-    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata: the context has damage strata (mdx_set_strata_damage); a context has one kind");
-    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_group_of_tid) { (void)hipFree(c->d_group_of_tid); c->d_group_of_tid = nullptr; }
-    c->n_groups = 0;
-    HIP_TRY(c, hipMalloc((void **)&c->d_group_of_tid, (size_t)n_contig * 4));
-    HIP_TRY(c, hipMemcpy(c->d_group_of_tid, group_of_tid, (size_t)n_contig * 4, hipMemcpyHostToDevice));
-    if (!c->d_strata_kept) {
-        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
-        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
-    }
-    c->n_groups = n_groups;
-    c->strata_n_contig = n_contig;
+    if (const int rc = begin_strata(c, STRATA_TID, n_groups); rc != MDX_OK) return rc;
+    if (c->strata.d_group_of_tid) { (void)hipFree(c->strata.d_group_of_tid); c->strata.d_group_of_tid = nullptr; }
+    HIP_TRY(c, hipMalloc((void **)&c->strata.d_group_of_tid, (size_t)n_contig * 4));
+    HIP_TRY(c, hipMemcpy(c->strata.d_group_of_tid, group_of_tid, (size_t)n_contig * 4, hipMemcpyHostToDevice));
+    c->strata.strata_n_contig = n_contig;
+    c->strata.kind = STRATA_TID; c->strata.n_groups = n_groups;
     return MDX_OK;
 }
 
@@ -1365,9 +1398,6 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
                            const int32_t *iv_end, const int32_t *iv_group, int32_t rest_group) {
     if (!c) return MDX_ERR_ARG;
     if (n_groups < 1 || n_contig < 1 || !iv_off) return fail(c, MDX_ERR_ARG, "set_strata_regions: bad arguments");
-    if (c->cfg.nlib % n_groups != 0)
-        return fail(c, MDX_ERR_ARG, "set_strata_regions: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of " +
-                                    std::to_string(n_groups) + " groups (create it with nlib = libraries x groups)");
     if (rest_group < 0 || rest_group >= n_groups) return fail(c, MDX_ERR_ARG, "set_strata_regions: rest_group is outside [0, n_groups)");
     if (iv_off[0] != 0) return fail(c, MDX_ERR_ARG, "set_strata_regions: iv_off[0] is not 0");
     for (int32_t t = 0; t < n_contig; t++)
@@ -1385,56 +1415,34 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
             if (iv_group[k] < 0 || iv_group[k] >= n_groups)
                 return fail(c, MDX_ERR_ARG, which + "has group " + std::to_string(iv_group[k]) + ", outside [0, n_groups)");
         }
-    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_regions: records have been counted already (mdx_reset first)");
-    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has tid strata (mdx_set_strata); a context has one kind");
-    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has damage strata (mdx_set_strata_damage); a context has one kind");
-    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata_regions: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_regions) { (void)hipFree(c->d_regions); c->d_regions = nullptr; }
-    c->n_groups = 0;
+    if (const int rc = begin_strata(c, STRATA_REGIONS, n_groups); rc != MDX_OK) return rc;
+    if (c->strata.d_regions) { (void)hipFree(c->strata.d_regions); c->strata.d_regions = nullptr; }
     const size_t off_bytes = ((size_t)(n_contig + 1) * 8 + 15) & ~(size_t)15, col_bytes = ((size_t)n_iv * 4 + 15) & ~(size_t)15;
-    HIP_TRY(c, hipMalloc(&c->d_regions, off_bytes + 3 * col_bytes + 64));
-    char *p = (char *)c->d_regions;
+    HIP_TRY(c, hipMalloc(&c->strata.d_regions, off_bytes + 3 * col_bytes + 64));
+    char *p = (char *)c->strata.d_regions;
     HIP_TRY(c, hipMemcpy(p, iv_off, (size_t)(n_contig + 1) * 8, hipMemcpyHostToDevice));
     const int32_t *cols[3] = {iv_start, iv_end, iv_group};
     for (int k = 0; k < 3 && n_iv > 0; k++)
         HIP_TRY(c, hipMemcpy(p + off_bytes + k * col_bytes, cols[k], (size_t)n_iv * 4, hipMemcpyHostToDevice));
-    c->regions.iv_off = (const int64_t *)p;
-    c->regions.iv_start = (const int32_t *)(p + off_bytes);
-    c->regions.iv_end = (const int32_t *)(p + off_bytes + col_bytes);
-    c->regions.iv_group = (const int32_t *)(p + off_bytes + 2 * col_bytes);
-    c->regions.rest_group = rest_group;
-    c->regions.n_contig = n_contig;
-    if (!c->d_strata_kept) {
-        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
-        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
-    }
-    c->n_groups = n_groups;
-    c->strata_n_contig = n_contig;
+    c->strata.regions.iv_off = (const int64_t *)p;
+    c->strata.regions.iv_start = (const int32_t *)(p + off_bytes);
+    c->strata.regions.iv_end = (const int32_t *)(p + off_bytes + col_bytes);
+    c->strata.regions.iv_group = (const int32_t *)(p + off_bytes + 2 * col_bytes);
+    c->strata.regions.rest_group = rest_group;
+    c->strata.regions.n_contig = n_contig;
+    c->strata.strata_n_contig = n_contig;
+    c->strata.kind = STRATA_REGIONS; c->strata.n_groups = n_groups;
     return MDX_OK;
 }
 
 int mdx_set_strata_damage(mdx_ctx *c, int32_t positions, int32_t single_stranded) {
     if (!c) return MDX_ERR_ARG;
-    if (c->cfg.nlib % 4 != 0)
-        return fail(c, MDX_ERR_ARG, "set_strata_damage: the context's " + std::to_string(c->cfg.nlib) +
-                                    " tables are no multiple of the 4 groups none, 5p, 3p, both (create it with nlib = libraries x 4)");
     if (positions < 1 || positions > c->cfg.length)
         return fail(c, MDX_ERR_ARG, "set_strata_damage: " + std::to_string(positions) + " terminal positions are outside [1, length = " +
                                     std::to_string(c->cfg.length) + "]");
-    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_damage: records have been counted already (mdx_reset first)");
-    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has tid strata (mdx_set_strata); a context has one kind");
-    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has region strata (mdx_set_strata_regions); a context has one kind");
-    if (c->pmd_n_thresholds > 0) return fail(c, MDX_ERR_STATE, "set_strata_damage: the context has PMD strata (mdx_set_strata_pmd); a context has one kind");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    if (!c->d_strata_kept) {
-        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
-        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
-    }
-    c->n_groups = 4;
-    c->damage_positions = positions;
-    c->damage_single_stranded = single_stranded ? 1 : 0;
+    if (const int rc = begin_strata(c, STRATA_DAMAGE, 4); rc != MDX_OK) return rc;    // none, 5p, 3p, both
+    c->strata.damage_positions = positions; c->strata.damage_single_stranded = single_stranded ? 1 : 0;
+    c->strata.kind = STRATA_DAMAGE; c->strata.n_groups = 4;
     return MDX_OK;
 }
 
@@ -1446,91 +1454,74 @@ int mdx_set_strata_pmd(mdx_ctx *c, int32_t n_thresholds, const int64_t *threshol
     for (int t = 1; t < n_thresholds; t++)
         if (thresholds_fx[t] <= thresholds_fx[t - 1])
             return fail(c, MDX_ERR_ARG, "set_strata_pmd: threshold " + std::to_string(t) + " is not above the one before it (strictly increasing)");
-    if (c->cfg.nlib % (n_thresholds + 1) != 0)
-        return fail(c, MDX_ERR_ARG, "set_strata_pmd: the context's " + std::to_string(c->cfg.nlib) + " tables are no multiple of the " +
-                                    std::to_string(n_thresholds + 1) + " groups of " + std::to_string(n_thresholds) + " thresholds (create it with nlib = libraries x groups)");
     if (c->cfg.minqual > 0)
         return fail(c, MDX_ERR_ARG, "set_strata_pmd: the context has a --min-basequal (cfg.minqual " + std::to_string(c->cfg.minqual) +
                                     "): the decoders fold its mask into SEQ and may drop the quality column the score reads");
-    if (c->counted) return fail(c, MDX_ERR_STATE, "set_strata_pmd: records have been counted already (mdx_reset first)");
-    if (c->d_group_of_tid) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has tid strata (mdx_set_strata); a context has one kind");
-    if (c->d_regions) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has region strata (mdx_set_strata_regions); a context has one kind");
-    if (c->damage_positions > 0) return fail(c, MDX_ERR_STATE, "set_strata_pmd: the context has damage strata (mdx_set_strata_damage); a context has one kind");
+    if (const int rc = begin_strata(c, STRATA_PMD, n_thresholds + 1); rc != MDX_OK) return rc;    // a group per number of thresholds reached
+    const size_t term_bytes = (size_t)2 * MDX_PMD_Z * MDX_PMD_QCOLS * 4;
+    if (!c->strata.d_pmd_terms) HIP_TRY(c, hipMalloc((void **)&c->strata.d_pmd_terms, term_bytes));
+    HIP_TRY(c, hipMemcpy(c->strata.d_pmd_terms, terms, term_bytes, hipMemcpyHostToDevice));
+    // (the histogram's size follows the groups: a second call with another number of thresholds gets another one)
+    if (c->strata.d_pmd_hist) { (void)hipFree(c->strata.d_pmd_hist); c->strata.d_pmd_hist = nullptr; }
+    c->strata.pmd_n_thresholds = n_thresholds; c->strata.pmd_single_stranded = single_stranded ? 1 : 0;
+    for (int t = 0; t < n_thresholds; t++) c->strata.pmd_thresholds[t] = thresholds_fx[t];
+    HIP_TRY(c, hipMalloc((void **)&c->strata.d_pmd_hist, pmd_hist_words(c) * 8));
+    HIP_TRY(c, hipMemset(c->strata.d_pmd_hist, 0, pmd_hist_words(c) * 8));
+    c->strata.kind = STRATA_PMD; c->strata.n_groups = n_thresholds + 1;
+    return MDX_OK;
+}
+
+// what the context's strata hold on the device, behind everything enqueued
+static int strata_read(mdx_ctx *c, void *dst, const void *src, size_t bytes) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!c->d_strata_kept) {
-        HIP_TRY(c, hipMalloc((void **)&c->d_strata_kept, (size_t)c->cfg.nlib * 8));
-        HIP_TRY(c, hipMemset(c->d_strata_kept, 0, (size_t)c->cfg.nlib * 8));
-    }
-    const size_t term_bytes = (size_t)2 * MDX_PMD_Z * MDX_PMD_QCOLS * 4;
-    if (!c->d_pmd_terms) HIP_TRY(c, hipMalloc((void **)&c->d_pmd_terms, term_bytes));
-    HIP_TRY(c, hipMemcpy(c->d_pmd_terms, terms, term_bytes, hipMemcpyHostToDevice));
-    // (the histogram's size follows the groups: a second call with another number of thresholds gets another one)
-    if (c->d_pmd_hist) { (void)hipFree(c->d_pmd_hist); c->d_pmd_hist = nullptr; }
-    c->n_groups = n_thresholds + 1;
-    c->pmd_n_thresholds = n_thresholds;
-    c->pmd_single_stranded = single_stranded ? 1 : 0;
-    for (int t = 0; t < n_thresholds; t++) c->pmd_thresholds[t] = thresholds_fx[t];
-    HIP_TRY(c, hipMalloc((void **)&c->d_pmd_hist, pmd_hist_words(c) * 8));
-    HIP_TRY(c, hipMemset(c->d_pmd_hist, 0, pmd_hist_words(c) * 8));
+    if (bytes > 0) HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
 int mdx_strata_pmd_keep_scores(mdx_ctx *c, int32_t on) {
     if (!c) return MDX_ERR_ARG;
-    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_keep_scores: the context has no PMD strata (mdx_set_strata_pmd)");
-    c->pmd_keep_scores = on != 0;
-    c->pmd_scores_serial = 0;
+    if (c->strata.kind != STRATA_PMD) return fail(c, MDX_ERR_STATE, "strata_pmd_keep_scores: the context has no PMD strata (mdx_set_strata_pmd)");
+    c->strata.pmd_keep_scores = on != 0;
+    c->strata.pmd_scores_serial = 0;
     return MDX_OK;
 }
 
 int mdx_strata_pmd_scores(mdx_ctx *c, float *out, int64_t n) {
     if (!c || n < 0 || (n > 0 && !out)) return MDX_ERR_ARG;
-    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the context has no PMD strata (mdx_set_strata_pmd)");
-    if (!c->pmd_keep_scores) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the scores are not kept (mdx_strata_pmd_keep_scores)");
-    if (c->pmd_scores_serial == 0 || c->pmd_scores_serial != c->strata_key_serial)
+    if (c->strata.kind != STRATA_PMD) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the context has no PMD strata (mdx_set_strata_pmd)");
+    if (!c->strata.pmd_keep_scores) return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the scores are not kept (mdx_strata_pmd_keep_scores)");
+    if (c->strata.pmd_scores_serial == 0 || c->strata.pmd_scores_serial != c->strata.strata_key_serial)
         return fail(c, MDX_ERR_STATE, "strata_pmd_scores: the batch tabulated last was not keyed (none yet, or a resident batch that brought its buckets)");
-    if (n != c->strata_key_n)
-        return fail(c, MDX_ERR_ARG, "strata_pmd_scores: n " + std::to_string(n) + ", the batch keyed last has " + std::to_string(c->strata_key_n) + " records");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (n > 0) HIP_TRY(c, hipMemcpy(out, c->pmd_scores.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    if (n != c->strata.strata_key_n)
+        return fail(c, MDX_ERR_ARG, "strata_pmd_scores: n " + std::to_string(n) + ", the batch keyed last has " + std::to_string(c->strata.strata_key_n) + " records");
+    return strata_read(c, out, c->strata.pmd_scores.p, (size_t)n * 4);
 }
 
 int mdx_strata_pmd_histogram(mdx_ctx *c, uint64_t *hist) {
     if (!c || !hist) return MDX_ERR_ARG;
-    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_histogram: the context has no PMD strata (mdx_set_strata_pmd)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(hist, c->d_pmd_hist, (pmd_hist_words(c) - 1) * 8, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    if (c->strata.kind != STRATA_PMD) return fail(c, MDX_ERR_STATE, "strata_pmd_histogram: the context has no PMD strata (mdx_set_strata_pmd)");
+    return strata_read(c, hist, c->strata.d_pmd_hist, (pmd_hist_words(c) - 1) * 8);
 }
 
 int mdx_strata_pmd_unqualified(mdx_ctx *c, uint64_t *n) {
     if (!c || !n) return MDX_ERR_ARG;
-    if (c->pmd_n_thresholds <= 0) return fail(c, MDX_ERR_STATE, "strata_pmd_unqualified: the context has no PMD strata (mdx_set_strata_pmd)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(n, c->d_pmd_hist + (pmd_hist_words(c) - 1), 8, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    if (c->strata.kind != STRATA_PMD) return fail(c, MDX_ERR_STATE, "strata_pmd_unqualified: the context has no PMD strata (mdx_set_strata_pmd)");
+    return strata_read(c, n, c->strata.d_pmd_hist + (pmd_hist_words(c) - 1), 8);
 }
 
-int mdx_strata_groups(const mdx_ctx *c) { return c ? c->n_groups : 0; }
+int mdx_strata_groups(const mdx_ctx *c) { return c ? c->strata.n_groups : 0; }
 
 int mdx_strata_kept(mdx_ctx *c, uint64_t *kept) {
     if (!c || !kept) return MDX_ERR_ARG;
-    if (c->n_groups <= 0) return fail(c, MDX_ERR_STATE, "strata_kept: mdx_set_strata has not been called");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(kept, c->d_strata_kept, (size_t)c->cfg.nlib * 8, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    if (c->strata.n_groups <= 0) return fail(c, MDX_ERR_STATE, "strata_kept: mdx_set_strata has not been called");
+    return strata_read(c, kept, c->strata.d_strata_kept, (size_t)c->cfg.nlib * 8);
 }
 int mdx_lgd_copies(const mdx_ctx *c) { return c ? c->lgd_copies : 0; }
 
 int64_t mdx_merged_words(const mdx_ctx *c) {
     if (!c) return 0;
-    const int64_t g = c->n_groups > 0 ? c->n_groups : 1;
+    const int64_t g = c->strata.n_groups > 0 ? c->strata.n_groups : 1;
     return (mis_words(c) + comp_words(c) + lgd_words(c)) / g + 2;
 }
 
@@ -1556,7 +1547,7 @@ int mdx_finish_merged(mdx_ctx *c, const uint64_t *d_tables, uint64_t *d_merged) 
     if (!c || !d_tables || !d_merged) return MDX_ERR_ARG;
     if (d_tables == d_merged) return fail(c, MDX_ERR_ARG, "finish_merged: the merged block needs a buffer of its own");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
-    const int g = c->n_groups > 0 ? c->n_groups : 1;
+    const int g = c->strata.n_groups > 0 ? c->strata.n_groups : 1;
     mdx_k_merge_strata((const unsigned long long *)d_tables, (unsigned long long *)d_merged, c->cfg.nlib / g, g,
                        (int64_t)4 * c->cfg.length * MDX_N_MIS_COLS, (int64_t)4 * (c->cfg.length + c->cfg.around) * 4,
                        (int64_t)4 * c->cfg.lgd_max, c->stream);
@@ -1617,17 +1608,17 @@ void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, 
 int mdx_ctx_minqual(const mdx_ctx *c) { return c ? c->cfg.minqual : -1; }
 
 int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const uint16_t **flag, int64_t *n_reads, uint64_t *serial) {
-    if (serial) *serial = c ? c->strata_key_serial : 0;
-    if (!c || c->n_groups <= 0) return 0;
-    if (key) *key = (const uint16_t *)c->strata_key.p;
-    if (flag) *flag = c->strata_key_flag;
-    if (n_reads) *n_reads = c->strata_key_n;
-    return c->n_groups;
+    if (serial) *serial = c ? c->strata.strata_key_serial : 0;
+    if (!c || c->strata.n_groups <= 0) return 0;
+    if (key) *key = (const uint16_t *)c->strata.strata_key.p;
+    if (flag) *flag = c->strata.strata_key_flag;
+    if (n_reads) *n_reads = c->strata.strata_key_n;
+    return c->strata.n_groups;
 }
 
 const float *mdx_ctx_strata_scores(const mdx_ctx *c, uint64_t *serial) {
-    if (serial) *serial = c ? c->pmd_scores_serial : 0;
-    return c && c->pmd_scores_serial != 0 ? (const float *)c->pmd_scores.p : nullptr;
+    if (serial) *serial = c ? c->strata.pmd_scores_serial : 0;
+    return c && c->strata.pmd_scores_serial != 0 ? (const float *)c->strata.pmd_scores.p : nullptr;
 }
 
 int mdx_ctx_stream(mdx_ctx *c, void **stream, int *device) {
@@ -1807,7 +1798,7 @@ static int tabulate_rescale_impl(mdx_ctx *c, const mdx_batch *b_in, const int32_
     // one pass over one resident batch: the tables and, from the same columns in HBM, the rescaled qualities
     int rc = check_batch(c, b_in);
     if (rc != MDX_OK) return rc;
-    if (c->n_groups > 0) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
+    if (c->strata.n_groups > 0) return fail(c, MDX_ERR_ARG, "the fused tabulate-and-rescale calls count one library: not on a context with mdx_set_strata");
     // (the fused kernel copies the quality column in 16-byte units: both columns at the same 16-byte phase — true of any two
     // device allocations; patch mode: no second column)
     const bool args_ok = c->d_ref && c->d_lut && b_in->qual && d_mtid && d_mpos && d_mr_raw && d_status &&

@@ -1,5 +1,5 @@
 // Damage strata (mdx_set_strata_damage): a record's group from the substitutions its own ends show.  Plain C++, one record
-// per call — strata_damage_key_kernel (mdx_libsort.hip) gives every lane one; the host compiles the same lines for the rule's
+// per call — the damage rule of strata_key_kernel (mdx_strata.hip) gives every lane one; the host compiles the same lines for the rule's
 // CPU test (tests/test_terminal_damage.py).
 //
 // group = (5p-damaged ? 1 : 0) + (3p-damaged ? 2 : 0), where an end is damaged if statistics.py:22-35, as main.py:185-212

@@ -354,6 +354,7 @@ void mdx_k_reduce_partials(const uint32_t *partials, unsigned long long *raw, un
 void mdx_k_ml_plan(const uint32_t *lib_start, int lib_lo, int nlib, int T, int grid, void *plan, hipStream_t s);
 
 // ---- bucketing a batch's records by library (mdx_libsort.hip), for the packed kernel's launches over several libraries
+#define LS_LDS_LIBS 4096     // libraries (mdx_strata.hip: strata) whose counts / places a block keeps in the LDS (beyond: global memory)
 struct MdxLibSort {
     unsigned long long *bad; // min over index << 8 | code of the kept records whose library is not below nlib (~0: none): they have
                              // no place, and every launch over the bucketed columns reports the first of them (MdxTabArgs::sort_bad)
@@ -378,17 +379,14 @@ void mdx_k_libsort(int64_t n, int64_t n_cigar, int64_t n_bases, const uint16_t *
 void mdx_k_finalize(const unsigned long long *raw, const unsigned long long *lgd_dense,
                     const unsigned long long *n_lgd_over, MdxDims d, int lgd_copies, unsigned long long *out,
                     hipStream_t s);
-// ---- strata (mdx_set_strata; mdx_libsort.hip): the table index of a record in a context of n_libraries x n_groups tables,
-// key[i] = lib[i] * n_groups + group_of_tid[tid[i]] — 0xFFFF where the library is not below n_libraries (no or unknown read
-// group: the tabulation kernels report it if they count the record); a tid outside [0, n_contig) takes group 0 (the kernels
-// report that one too)
-// kept[key] += 1 for every record the flag filter keeps (kept == null: the key only); mdx_k_strata_kept_from_sort: the same
-// counts from the buckets of a batch sorted by stratum
+// ---- strata (mdx_strata.hip, where the rules are told in full): the table index of a record in a context of n_libraries x
+// n_groups tables, key[i] = lib[i] * n_groups + group — 0xFFFF where the library is not below n_libraries (the tabulation
+// kernels report it if they count the record) —, and kept[key] += 1 for every record the flag filter keeps (kept == null:
+// the key only).  The group: of the record's sequence (mdx_set_strata; a tid outside [0, n_contig): group 0) ...
 void mdx_k_strata_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *group_of_tid, int n_contig,
                       int n_groups, int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
-// region strata (mdx_set_strata_regions): the group is that of the first interval of the record's sequence that shares a base
-// with [pos, pos + max(1, reference bases of the CIGAR)), rest_group where none does or tid is outside [0, n_contig).  The
-// intervals (device) of sequence t are iv_off[t] .. iv_off[t + 1], sorted and disjoint.  CIGAR offsets are clamped to n_cigar.
+// ... of the first interval (device; those of sequence t are iv_off[t] .. iv_off[t + 1], sorted and disjoint) that shares a base
+// with the record, rest_group where none does (mdx_set_strata_regions) ...
 struct MdxRegions {
     const int64_t *iv_off;       // [n_contig + 1]
     const int32_t *iv_start, *iv_end, *iv_group;
@@ -397,22 +395,18 @@ struct MdxRegions {
 void mdx_k_strata_region_key(int64_t n, const uint16_t *flag, const uint16_t *lib, const int32_t *tid, const int32_t *pos,
                              const uint32_t *cigar_off, const uint32_t *cigar, int64_t n_cigar, const MdxRegions &r, int n_groups,
                              int n_libraries, uint16_t *key, unsigned long long *kept, hipStream_t s);
-// damage strata (mdx_set_strata_damage): four groups from the record's own alignment against the resident reference —
-// none, 5p, 3p, both: an end is damaged if MisincorporationRates.update (statistics.py:22-35) would add to C>T (5p) or G>A
-// (3p; C>T with single_stranded) at an index below `positions`.  The batch in any of its three SEQ forms; qual / lowq are
-// read under a minqual for the forms that do not carry the mask; a tid or a window outside the reference is group none.
-// (MdxDamageKey and the rule itself: mdx_damage_key.h)
+// ... none, 5p, 3p or both by the damage the record's own ends show against the resident reference (mdx_set_strata_damage;
+// MdxDamageKey and the rule: mdx_damage_key.h) ...
 #include "mdx_damage_key.h"
 void mdx_k_strata_damage_key(const MdxDamageKey &a, uint16_t *key, unsigned long long *kept, hipStream_t s);
-// PMD strata (mdx_set_strata_pmd): the group from the record's post-mortem damage score, summed in fixed point over its whole
-// alignment against the resident reference, with its qualities (MdxPmdKey and the rule itself: mdx_pmd_key.h).  The batch
-// with an ASCII or MDX_SEQ_4BIT column.  kept [libraries x groups] and hist [libraries x MDX_PMD_BINS + 1] may be null, and so
-// may key (a launch for the histogram alone).  form: 0 the cooperative kernel with part of the term table in the LDS; for
+// ... or the number of thresholds the record's post-mortem damage score reaches (mdx_set_strata_pmd; MdxPmdKey and the rule:
+// mdx_pmd_key.h).  kept [libraries x groups], hist [libraries x MDX_PMD_BINS + 1], key and score (the float of every record's
+// score as a score tag holds it) may be null.  form: 0 the cooperative kernel with part of the term table in the LDS; for
 // measurements 1 the trivial kernel, a lane per record, and 2 the cooperative one with every term from global memory.
 #include "mdx_pmd_key.h"
-// score (null: none): the float of every record's score as a score tag holds it (mdx_pmd_tag_bits, mdx_kept_tags.h).
 void mdx_k_strata_pmd_key(const MdxPmdKey &a, uint16_t *key, float *score, unsigned long long *kept, unsigned long long *hist, int form,
                           hipStream_t s);
+// the same counts from the buckets of a batch sorted by stratum
 void mdx_k_strata_kept_from_sort(const uint32_t *lib_start, int n_strata, unsigned long long *kept, hipStream_t s);
 // a canonical block of n_libraries x n_groups tables (w_mis, w_comp, w_lgd words per table; two tail words) -> the block of
 // n_libraries tables, the groups of each library summed

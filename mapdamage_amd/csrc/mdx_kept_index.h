@@ -5,7 +5,7 @@
 // The rule (SAM specification 5.2 and 5.3; what hts_idx_push records before its finishing compaction):
 //   which      only written records count: sizes[r] != 0 after mdx_kept_bytes (mdx_kept.h), tagged or not.
 //   extent     a written record occupies [pos, end), end = pos + max(1, the reference bases its CIGAR consumes): M D N = X
-//              consume (htslib's bam_endpos; strata_region_key_kernel states the same rule).
+//              consume (htslib's bam_endpos; RegionRule of mdx_strata.hip states the same rule).
 //   bin        reg2bin(pos, end), end exclusive: levels of 2^26, 2^23, 2^20, 2^17 and 2^14 bases at offsets 1, 9, 73, 585, 4681.
 //   placeable  0 <= tid < n_ref, pos >= 0, end <= LN[tid], end <= 2^29; any other written record fails the call.
 //   order      consecutive written records a, b (across slabs too): tid_a < tid_b, or tid_a == tid_b and pos_a <= pos_b; the

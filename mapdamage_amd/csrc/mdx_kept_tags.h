@@ -1,6 +1,6 @@
 // --write-kept with --tag-group / --tag-pmd-score (mdx_gbam_write_kept_tagged): what a written record looks like when the run
 // appends its group and its PMD score to it, and the walk over a record's own tags that finds a name already taken.
-// Plain C++, one record per call — the tagged sizes and gather kernels (mdx_gbam.hip), strata_pmd_key_kernel (mdx_libsort.hip:
+// Plain C++, one record per call — the tagged sizes and gather kernels (mdx_gbam.hip), strata_pmd_key_kernel (mdx_strata.hip:
 // the score's bits) and gbam_write_back_kernel (the MR tag of --rescale-only: the same walk) compile these lines for the
 // device; the host compiles them for the rule's CPU test (tests/test_write_tags.py) and under the sanitizers.
 //

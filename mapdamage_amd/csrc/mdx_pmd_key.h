@@ -1,5 +1,5 @@
 // PMD strata (mdx_set_strata_pmd): a record's post-mortem damage score (Skoglund et al. 2014, PNAS 111:2229) in fixed point,
-// and its group among the thresholds.  Plain C++, one record per call — strata_pmd_key_kernel (mdx_libsort.hip) spreads a record's
+// and its group among the thresholds.  Plain C++, one record per call — strata_pmd_key_kernel (mdx_strata.hip) spreads a record's
 // columns over a group of lanes (mdx_pmd_walk4, four columns to a lane and step), its trivial form gives every lane one record (mdx_pmd_score); the host compiles the same lines for the rule's CPU test (tests/test_pmd.py).
 //
 // The rule, in the record's TRUE alignment (not the tables' strings, which an N operation misaligns):

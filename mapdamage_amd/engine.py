@@ -299,8 +299,7 @@ class DamageEngine:
             raise ValueError("%d libraries x %d reference groups = %d tables; the 16-bit library column names at most %d"
                              % (len(self.base_libraries), len(self.groups or [None]), n_tables, self.MAX_TABLES))
         self._lib = load_library()
-        self._strata_set = False
-        self._pmd = False
+        self.strata_kind = None        # "reference", "regions", "damage" or "pmd" once a set_strata* call succeeded (groupings.KINDS)
         self.libraries = [lib for lib in self.base_libraries for _ in (self.groups or [None])]
         self.length, self.around, self.minqual, self.lgd_max = length, around, minqual, lgd_max
         self.lgd_over_cap = lgd_over_cap
@@ -358,7 +357,7 @@ class DamageEngine:
             raise ValueError("set_strata: the engine was made without groups")
         m = np.ascontiguousarray(group_of_tid, dtype=np.int32)
         self._check(self._lib.mdx_set_strata(self._ctx, ctypes.c_int32(len(self.groups)), _ptr(m), ctypes.c_int32(m.shape[0])))
-        self._strata_set = True
+        self.strata_kind = "reference"
 
     def set_strata_regions(self, iv_off, iv_start, iv_end, iv_group, rest_group=None):
         """The group of a record from a set of regions (include/mdx.h ``mdx_set_strata_regions``): the intervals of sequence
@@ -376,7 +375,7 @@ class DamageEngine:
         rest = len(self.groups) - 1 if rest_group is None else int(rest_group)
         self._check(self._lib.mdx_set_strata_regions(self._ctx, ctypes.c_int32(len(self.groups)), ctypes.c_int32(off.shape[0] - 1),
                                                      _ptr(off), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ctypes.c_int32(rest)))
-        self._strata_set = True
+        self.strata_kind = "regions"
 
     DAMAGE_GROUPS = ["none", "5p", "3p", "both"]
 
@@ -388,7 +387,7 @@ class DamageEngine:
         if self.groups != self.DAMAGE_GROUPS:
             raise ValueError("set_strata_damage: the engine must be made with groups=%r" % (self.DAMAGE_GROUPS,))
         self._check(self._lib.mdx_set_strata_damage(self._ctx, ctypes.c_int32(int(positions)), ctypes.c_int32(1 if single_stranded else 0)))
-        self._strata_set = True
+        self.strata_kind = "damage"
 
     def set_strata_pmd(self, thresholds, model=(0.3, 0.01, 0.001), single_stranded=False, keep_scores=False):
         """The group of a record from its post-mortem damage score (include/mdx.h ``mdx_set_strata_pmd``; the rule is
@@ -406,8 +405,7 @@ class DamageEngine:
         terms = np.ascontiguousarray(pmd.term_table(*model), np.int32)
         self._check(self._lib.mdx_set_strata_pmd(self._ctx, ctypes.c_int32(len(ts)), _ptr(fx), _ptr(terms),
                                                  ctypes.c_int32(1 if single_stranded else 0)))
-        self._strata_set = True
-        self._pmd = True
+        self.strata_kind = "pmd"
         if keep_scores:
             self.keep_pmd_scores(True)
 
@@ -429,7 +427,7 @@ class DamageEngine:
     @property
     def pmd_strata(self):
         """The engine's strata are those of ``set_strata_pmd``: ``finish()`` brings the score histogram."""
-        return self._pmd
+        return self.strata_kind == "pmd"
 
     def pmd_histogram(self):
         """uint64 [base libraries][82]: the kept records of each library by their score (``mdx_strata_pmd_histogram``; bin
@@ -640,14 +638,14 @@ class DamageEngine:
     def _finish_strata(self):
         """The block of all strata and — summed on the device, ``mdx_finish_merged_host`` — the block of the libraries."""
         from .tables import StratifiedTables, unpack_words
-        if not self._strata_set:
+        if self.strata_kind is None:
             raise ValueError("finish: set_strata has not been called")
         if self.comm_size:
             raise ValueError("finish of a stratified engine with a communicator attached: reduce the block "
                              "(finish_allreduce) and split it with tables.StratifiedTables.from_block")
         strata = self._finish_block()
         out = StratifiedTables.from_block(strata, self.base_libraries, self.groups, self.strata_kept())
-        if self._pmd:
+        if self.pmd_strata:
             out.pmd_hist, out.pmd_unqualified = self.pmd_histogram(), self.pmd_unqualified()
         merged = np.zeros(int(self._lib.mdx_merged_words(self._ctx)), np.uint64)
         self._check(self._lib.mdx_finish_merged_host(self._ctx, _ptr(merged)))

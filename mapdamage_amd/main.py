@@ -12,13 +12,13 @@ import re
 import sys
 import time
 from pathlib import Path
-from typing import NamedTuple
 
 import numpy as np
 
-from . import __version__
+from . import __version__, groupings
 from .batch import mark_unmaskable
 from .engine import BadReadError, DamageEngine, MdxError
+from .groupings import PmdScore, TerminalDamage        # noqa: F401  (where callers import them from)
 from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
@@ -217,8 +217,7 @@ def build_parser():
                         "-n N.  The tables and logs are what the run writes without the option; write_kept.tsv gives the records "
                         "and bytes written.  Not a reference option: mapdamage/config.py has none")
     g.add_argument("--write-groups", default=None, metavar="I[,I...]",
-                   help="with --write-kept in a run that has groups (--by-reference, --reference-groups, --regions, --region-groups, "
-                        "--by-terminal-damage, --by-pmd-score): write only the records of the groups with these indices of "
+                   help="with --write-kept in a run that has groups (" + groupings.OPTION_LIST + "): write only the records of the groups with these indices of "
                         "groups.tsv, for all libraries — `--by-pmd-score --pmd-thresholds 3 --write-groups 1` is what `pmdtools "
                         "--threshold 3` would have written (default: every counted record)")
     g.add_argument("--tag-group", default=None, metavar="TAG",
@@ -281,14 +280,11 @@ def check_write_groups(groups, n_groups):
 
 def _check_write_kept(parser, o):
     """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score."""
-    has_groups = bool(o.by_reference or o.reference_groups or o.regions or o.region_groups or o.by_terminal_damage
-                      or o.by_pmd_score)
     if o.write_groups is not None:
         if o.write_kept is None:
             parser.error("--write-groups needs --write-kept: it chooses the groups whose records that file receives")
-        if not has_groups:
-            parser.error("--write-groups needs a run with groups: one of --by-reference, --reference-groups, --regions, "
-                         "--region-groups, --by-terminal-damage, --by-pmd-score")
+        if not o.grouping_options:
+            parser.error("--write-groups needs a run with groups: one of " + groupings.OPTION_LIST)
         try:
             o.write_groups = parse_write_groups(o.write_groups)
         except ValueError as error:
@@ -300,9 +296,8 @@ def _check_write_kept(parser, o):
             parser.error("%s needs --write-kept: it tags the records that file receives" % option)
         if not re.fullmatch(r"[A-Za-z][A-Za-z0-9]", tag):
             parser.error("%s %s: a tag is two characters, [A-Za-z][A-Za-z0-9]" % (option, tag))
-    if o.tag_group is not None and not has_groups:
-        parser.error("--tag-group needs a run with groups: one of --by-reference, --reference-groups, --regions, "
-                     "--region-groups, --by-terminal-damage, --by-pmd-score")
+    if o.tag_group is not None and not o.grouping_options:
+        parser.error("--tag-group needs a run with groups: one of " + groupings.OPTION_LIST)
     if o.tag_pmd_score is not None and not o.by_pmd_score:
         parser.error("--tag-pmd-score needs --by-pmd-score: the score is the one that run computes")
     if o.tag_group is not None and o.tag_group == o.tag_pmd_score:
@@ -363,28 +358,24 @@ def parse_args(argv):
     if o.record_filter.active and (o.rescale_only or o.stats_only):
         parser.error("--min-mapq / --require-flags / --exclude-flags / --min-read-length / --max-read-length belong to the "
                      "tabulation pass; neither --rescale-only nor --stats-only counts records")
-    if (o.pmd_thresholds is not None or o.pmd_model is not None) and not o.by_pmd_score:
-        parser.error("--pmd-thresholds / --pmd-model need --by-pmd-score")
-    if o.by_pmd_score:
-        from . import pmd
-        if o.by_reference or o.reference_groups or o.regions or o.region_groups or o.by_terminal_damage:
-            parser.error("--by-pmd-score and --by-reference / --reference-groups / --regions / --region-groups / "
-                         "--by-terminal-damage exclude each other: a run has one kind of groups")
+    # A run has one kind of groups (groupings.KINDS).  (--stats-only: see Kind.ignored_by_stats_only)
+    live = [kind for kind in groupings.KINDS if not (o.stats_only and kind.ignored_by_stats_only)]
+    o.grouping_options = [option for kind in groupings.KINDS for option in kind.given(o)]
+    for kind in live:
+        if kind.given(o, kind.companions) and not kind.given(o):
+            parser.error("%s need%s %s" % (" / ".join(kind.companions), "s" if len(kind.companions) == 1 else "", " or ".join(kind.options)))
+    kind = next((kind for kind in live if kind.given(o)), None)
+    if kind is not None:
+        if len(o.grouping_options) > 1:
+            parser.error("%s exclude each other: a run has one kind of groups, chosen by one of %s"
+                         % (" and ".join(o.grouping_options), groupings.OPTION_LIST))
         if o.rescale_only or o.stats_only:
-            parser.error("--by-pmd-score belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
-        if o.minqual > 0:
-            parser.error("--by-pmd-score cannot be combined with -Q / --min-basequal: the score weighs every base by its "
-                         "quality, and under --min-basequal the decoders fold the mask into the bases and may drop the "
-                         "quality column")
+            parser.error("%s belong%s to the tabulation pass; %s counts nothing"
+                         % (" / ".join(kind.options), "s" if len(kind.options) == 1 else "", "--rescale-only" if o.rescale_only else "--stats-only"))
         try:
-            o.pmd_thresholds = pmd.check_thresholds(
-                [float(t) for t in ("3" if o.pmd_thresholds is None else o.pmd_thresholds).split(",")])
-            model = [float(v) for v in ("0.3,0.01,0.001" if o.pmd_model is None else o.pmd_model).split(",")]
-            if len(model) != 3:
-                raise ValueError("--pmd-model takes three numbers: p,C,pi")
-            o.pmd_model = pmd.check_model(*model)
+            kind.prepare(o)
         except ValueError as error:
-            parser.error("--by-pmd-score: %s" % error)
+            parser.error(str(error))
     _check_write_kept(parser, o)
     if o.stats_only:
         if not o.folder:
@@ -393,30 +384,6 @@ def parse_args(argv):
             parser.error("--stats-only needs dnacomp_genome.csv in the folder, or --reference to make it from")
         o.no_stats = False
         return o
-    if o.by_reference and o.reference_groups:
-        parser.error("--by-reference and --reference-groups exclude each other")
-    if (o.by_reference or o.reference_groups) and o.rescale_only:
-        parser.error("--by-reference / --reference-groups belong to the tabulation pass; --rescale-only counts nothing")
-    if o.regions and o.region_groups:
-        parser.error("--regions and --region-groups exclude each other")
-    if (o.regions or o.region_groups) and (o.by_reference or o.reference_groups):
-        parser.error("--regions / --region-groups and --by-reference / --reference-groups exclude each other: a run has one "
-                     "kind of groups")
-    if (o.regions or o.region_groups) and o.rescale_only:
-        parser.error("--regions / --region-groups belong to the tabulation pass; --rescale-only counts nothing")
-    if o.only_regions and not (o.regions or o.region_groups):
-        parser.error("--only-regions needs --regions or --region-groups")
-    if o.by_terminal_damage and (o.by_reference or o.reference_groups or o.regions or o.region_groups):
-        parser.error("--by-terminal-damage and --by-reference / --reference-groups / --regions / --region-groups exclude each "
-                     "other: a run has one kind of groups")
-    if o.by_terminal_damage and o.rescale_only:
-        parser.error("--by-terminal-damage belongs to the tabulation pass; --rescale-only counts nothing")
-    if o.terminal_positions is not None and not o.by_terminal_damage:
-        parser.error("--terminal-positions needs --by-terminal-damage")
-    if o.by_terminal_damage:
-        o.terminal_positions = 1 if o.terminal_positions is None else o.terminal_positions
-        if o.terminal_positions > o.length:
-            parser.error("--terminal-positions must not be greater than --length: the tables hold no position beyond it")
     if o.rescale_only and not o.folder:
         parser.error("--folder required when using --rescale-only")
     if not o.filename:
@@ -543,14 +510,14 @@ def _group_has_data(folder):
 
 
 def bayesian_estimates(options, logger, ref=None, n_contig=0, device=0):
-    """The estimate of the folder's tables and of every group directory beside them (by_reference/<index>,
-    by_region/<index>, by_damage/<index>, by_pmd/<index>), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
+    """The estimate of the folder's tables and of every group directory beside them (<a kind's directory>/<index>:
+    groupings.KINDS), all chains in one launch: mapdamage/rscript.py:70-100 without R.  Returns the exit code."""
     from .stats import StatsError, estimate_folders
     start = time.time()
     try:
         acgt = _base_frequencies(options, ref, n_contig, device)
         folders, chains = [options.folder], [options.stats_chain]
-        for sub in ("by_reference", "by_region", "by_damage", "by_pmd"):
+        for sub in (kind.directory for kind in groupings.KINDS):
             if not (options.folder / sub / "groups.tsv").is_file():
                 continue
             index = 0
@@ -569,6 +536,14 @@ def bayesian_estimates(options, logger, ref=None, n_contig=0, device=0):
         return 1
     logger.debug("Bayesian estimates made in %f seconds", time.time() - start)
     return 0
+
+
+def _sum_words(words, device):
+    """uint64 words summed over the ranks (``device``: where the backend wants them; None: the host)."""
+    import torch
+    from .distributed import allreduce_words
+    words = torch.from_numpy(np.ascontiguousarray(words, np.uint64).view(np.int64).copy())
+    return allreduce_words(words if device is None else words.to(device)).cpu().numpy().view(np.uint64)
 
 
 class _Ranks:
@@ -625,22 +600,12 @@ class _Ranks:
         split by group, with the kept reads per stratum summed over the ranks as well."""
         if engine.groups is None:
             return block
-        import torch
-        from .distributed import allreduce_words
         from .tables import StratifiedTables
-        kept = torch.from_numpy(engine.strata_kept().view(np.int64).copy())
-        if device is not None:
-            kept = kept.to(device)
-        kept = allreduce_words(kept).cpu().numpy().view(np.uint64)
-        out = StratifiedTables.from_block(block, engine.base_libraries, engine.groups, kept)
-        if engine.pmd_strata:
-            # (--by-pmd-score: the score histogram and the records scored without qualities, summed as the kept reads are)
-            words = np.concatenate([engine.pmd_histogram().reshape(-1), np.array([engine.pmd_unqualified()], np.uint64)])
-            words = torch.from_numpy(words.view(np.int64).copy())
-            if device is not None:
-                words = words.to(device)
-            words = allreduce_words(words).cpu().numpy().view(np.uint64)
-            out.pmd_hist, out.pmd_unqualified = words[:-1].reshape(len(engine.base_libraries), -1), int(words[-1])
+        out = StratifiedTables.from_block(block, engine.base_libraries, engine.groups, _sum_words(engine.strata_kept(), device))
+        kind = groupings.BY_NAME[engine.strata_kind]
+        words = kind.rank_words(engine)
+        if words is not None:
+            kind.take_rank_words(out, _sum_words(words, device))
         return out
 
     def sum_counts(self, counts):
@@ -649,11 +614,7 @@ class _Ranks:
         if self.world == 1:
             return counts
         import torch
-        from .distributed import allreduce_words
-        words = torch.from_numpy(counts.view(np.int64).copy())
-        if self.backend == "nccl":
-            words = words.to(torch.device("cuda", self.device))
-        return allreduce_words(words).cpu().numpy().view(np.uint64)
+        return _sum_words(counts, torch.device("cuda", self.device) if self.backend == "nccl" else None)
 
     def close(self):
         if self.world > 1:
@@ -674,59 +635,22 @@ def launch_command(argv, gpus):
             "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "mapdamage_amd"] + keep
 
 
-class TerminalDamage(NamedTuple):
-    """What --by-terminal-damage hands to ``DamageEngine.set_strata_damage``."""
-    positions: int
-    single_stranded: bool
-
-
-class PmdScore(NamedTuple):
-    """What --by-pmd-score hands to ``DamageEngine.set_strata_pmd``."""
-    thresholds: tuple
-    model: tuple
-    single_stranded: bool
-
-
 def reference_strata(options, references, lengths=None):
-    """(group names, group_of_tid) of --by-reference / --reference-groups over the header's sequences, (group names,
-    tables.Regions) of --regions / --region-groups (``lengths``: the sequences' lengths), (group names, TerminalDamage) of
-    --by-terminal-damage, (group names, PmdScore) of --by-pmd-score, or None."""
-    from .tables import Regions, groups_by_reference, parse_reference_groups, parse_regions
-    if getattr(options, "by_pmd_score", False):
-        from .pmd import group_names
-        return group_names(options.pmd_thresholds), PmdScore(tuple(options.pmd_thresholds), tuple(options.pmd_model),
-                                                             bool(options.single_stranded))
-    if getattr(options, "by_terminal_damage", False):
-        return list(DamageEngine.DAMAGE_GROUPS), TerminalDamage(options.terminal_positions, bool(options.single_stranded))
-    if options.by_reference:
-        return groups_by_reference(references)
-    if options.reference_groups:
-        return parse_reference_groups(Path(options.reference_groups).read_text(), references)
-    bed = getattr(options, "regions", None) or getattr(options, "region_groups", None)
-    if bed:
-        names, *columns = parse_regions(Path(bed).read_text(), references, lengths, named=not options.regions)
-        return names, Regions(*columns, [int(x) for x in lengths])
-    return None
+    """(group names, payload) of the run's kind of groups (``groupings.KINDS``: what the kind's ``apply`` hands the engine)
+    from the options and the header's sequences and their ``lengths``, or None."""
+    kind = groupings.kind_of(options)
+    return None if kind is None else kind.payload(options, references, lengths)
 
 
 def _make_engine(options, libraries, device):
-    """The run's engine; with --by-reference / --reference-groups / --regions / --region-groups / --by-terminal-damage /
-    --by-pmd-score one table set per (library, group) — the input routes hand it the same batches either way."""
-    from .tables import Regions
+    """The run's engine; with a grouping option one table set per (library, group) — the input routes hand it the same
+    batches either way."""
     strata = getattr(options, "strata", None)
     engine = DamageEngine(libraries, options.length, options.around, options.minqual, device=device,
                           groups=None if strata is None else strata[0])
     if strata is not None:
         try:
-            if isinstance(strata[1], PmdScore):
-                engine.set_strata_pmd(strata[1].thresholds, strata[1].model, strata[1].single_stranded,
-                                      keep_scores=getattr(options, "tag_pmd_score", None) is not None)
-            elif isinstance(strata[1], TerminalDamage):
-                engine.set_strata_damage(strata[1].positions, strata[1].single_stranded)
-            elif isinstance(strata[1], Regions):
-                engine.set_strata_regions(strata[1].iv_off, strata[1].iv_start, strata[1].iv_end, strata[1].iv_group)
-            else:
-                engine.set_strata(strata[1])
+            groupings.kind_of(options).apply(engine, strata[1], options)
         except Exception:
             engine.close()
             raise
@@ -1224,17 +1148,13 @@ def main(argv):
         libraries = reader.get_libraries()
         try:
             options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
+            if options.write_groups is not None:
+                check_write_groups(options.write_groups, len(options.strata[0]))
         except (ValueError, OSError) as error:
             logger.error("%s", error)
             return 1
-        if options.write_groups is not None:
-            try:
-                check_write_groups(options.write_groups, len(options.strata[0]))
-            except ValueError as error:
-                logger.error("%s", error)
-                return 1
         if options.strata is not None:
-            kind = "PMD score" if options.by_pmd_score else "terminal damage" if options.by_terminal_damage else "regions" if options.regions or options.region_groups else "reference sequences"
+            kind = groupings.kind_of(options).label
             logger.info("Tabulating %d groups of %s x %d libraries in one pass", len(options.strata[0]), kind, len(libraries))
             if len(options.strata[0]) * len(libraries) > DamageEngine.MAX_TABLES:
                 logger.error("%d groups of %s x %d libraries: more than the %d tables a run can keep",
@@ -1283,32 +1203,8 @@ def main(argv):
         if not first:
             return 0
         if options.strata is not None:
-            # the three usual files from the sum over the groups, and by_reference/ beside them
-            if options.by_pmd_score:
-                from .pmd import groups_text, scores_text
-                tables.write(options.folder, subdir="by_pmd",
-                             groups_text=groups_text(tables.groups, [tables.group_kept(g) for g in range(len(tables.groups))]))
-                (options.folder / "by_pmd" / "scores.tsv").write_text(scores_text(tables.libraries, tables.pmd_hist))
-                if tables.pmd_unqualified:
-                    logger.info("PMD scores: %d records without PHRED scores were scored with a base error of 0",
-                                tables.pmd_unqualified)
-                tables = tables.merged
-            elif options.by_terminal_damage:
-                tables.write(options.folder, subdir="by_damage", groups_text=tables.damage_groups_text())
-                (options.folder / "by_damage" / "conditional.tsv").write_text(tables.conditional_text(options.strata[1].single_stranded))
-                tables = tables.merged
-            elif options.regions or options.region_groups:
-                from .tables import region_groups_text
-                r, ng = options.strata[1], len(options.strata[0])
-                text = region_groups_text(options.strata[0], r.iv_start, r.iv_end, r.iv_group, r.lengths,
-                                          [tables.group_kept(g) for g in range(ng)])
-                # (--only-regions: the usual files from the named groups alone, summed on the host; by_region/ keeps '*')
-                usual = tables.sum_of_groups(range(ng - 1)) if options.only_regions else None
-                tables.write(options.folder, subdir="by_region", groups_text=text, usual=usual)
-                tables = tables.merged if usual is None else usual
-            else:
-                tables.write(options.folder, options.strata[1])
-                tables = tables.merged
+            # the three usual files from the sum over the groups, and the kind's directory beside them
+            tables = groupings.kind_of(options).write(tables, options, options.strata, logger)
         else:
             tables.write(options.folder)
         if options.freq_files:

@@ -356,13 +356,11 @@ class StratifiedTables:
             out.write("%d\t%s\t%d\t%d\n" % (g, name, int(n_seq[g]), self.group_kept(g)))
         return out.getvalue()
 
-    def damage_groups_text(self):
-        """``by_damage/groups.tsv``: index, group name, kept reads."""
-        out = io.StringIO()
-        out.write("Index\tGroup\tReads\n")
-        for g, name in enumerate(self.groups):
-            out.write("%d\t%s\t%d\n" % (g, name, self.group_kept(g)))
-        return out.getvalue()
+    def kept_groups_text(self):
+        """``by_damage/groups.tsv``, ``by_pmd/groups.tsv``: index, group name, kept reads."""
+        from .pmd import groups_text
+        return groups_text(self.groups, [self.group_kept(g) for g in range(len(self.groups))])
+    damage_groups_text = kept_groups_text
 
     def conditional_text(self, single_stranded=False):
         """``by_damage/conditional.tsv`` of a run stratified by terminal damage (groups ``none, 5p, 3p, both``): the

@@ -27,7 +27,7 @@ from tests.util import oracle_tableset
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STRATA_KEY_PER = 4096           # csrc/mdx_libsort.hip: the records of one block of the key kernel
+STRATA_KEY_PER = 4096           # csrc/mdx_strata.hip: the records of one block of the key kernel
 THS3 = (0.0, 1.5, 3.0)
 
 
@@ -222,7 +222,7 @@ def test_the_kernels_kept_for_measurements_give_the_same(monkeypatch, knob):
 # ---------------------------------------------------------------------- 3. more strata and bins than the LDS counts
 @pytest.mark.parametrize("name,nl", [("2100 libraries", 2100), ("60 libraries", 60)])
 def test_more_strata_and_bins_than_the_lds_counts(name, nl):
-    """2 100 libraries x 2 groups = 4 200 strata (csrc/mdx_libsort.hip LS_LDS_LIBS = 4 096): kept reads and histogram
+    """2 100 libraries x 2 groups = 4 200 strata (csrc/mdx_internal.h LS_LDS_LIBS = 4 096): kept reads and histogram
     through global atomics; 60 libraries: 4 921 histogram words (PMD_HIST_LDS = 4 096) beside strata counted in the LDS."""
     _, b, _, ths, _ = inputs()[name]
     libs = [("S%d" % i, "L") for i in range(nl)]

@@ -197,7 +197,7 @@ def test_deep_search():
 
 # ---------------------------------------------------------------------- 4. more strata than the key kernel counts in the LDS
 def test_more_strata_than_the_lds_counts():
-    """2 libraries x 2 100 groups = 4 200 strata (csrc/mdx_libsort.hip LS_LDS_LIBS = 4 096): the kept records are counted
+    """2 libraries x 2 100 groups = 4 200 strata (csrc/mdx_internal.h LS_LDS_LIBS = 4 096): the kept records are counted
     with global atomics."""
     from mapdamage_amd.engine import DamageEngine
     ng = 2100

@@ -196,6 +196,30 @@ def test_fewer_pools_than_strata(monkeypatch):
     check(got, *want130())
 
 
+def test_more_strata_than_the_lds_counts():
+    """2 libraries x 2 100 groups = 4 200 strata (csrc/mdx_internal.h LS_LDS_LIBS = 4 096): the tid key counts the kept
+    records with global atomics.  5 000 records are two blocks of the key kernel (csrc/mdx_strata.hip STRATA_KEY_PER =
+    4 096), the second one partial."""
+    from mapdamage_amd.engine import DamageEngine
+    ng, libs = 2100, libraries(2)
+    group_of_tid = np.array([0, ng - 1, 1000, 17, ng - 2])
+    b = batch5().slice(0, 5000)
+    b.lib[:] = b.lib % 2
+    filtered = (b.flag & 0xF04) != 0
+    assert 10 < int(filtered.sum()) < b.n // 2 and filtered[4096:].any() and not filtered[4096:].all()
+    want = np.bincount((b.lib.astype(np.int64) * ng + group_of_tid[b.tid])[~filtered], minlength=2 * ng).astype(np.uint64)
+    assert np.count_nonzero(want) == 10
+    with DamageEngine(libs, 70, A, 0, lgd_max=1024, groups=["g%d" % i for i in range(ng)]) as eng:
+        eng.set_strata(group_of_tid)
+        eng.set_reference(genome5())
+        eng.tabulate(b, packed=True)
+        eng.sync()
+        np.testing.assert_array_equal(eng.strata_kept(), want)
+        got = eng.finish()
+    np.testing.assert_array_equal(got.kept, want)
+    assert_tables_equal(got.merged, oracle_tableset(genome5(), b, libs, 70, A, 0, 1024))
+
+
 # ---------------------------------------------------------------------- 4. memory
 def _free(device=0):
     import torch
@@ -248,6 +272,37 @@ def test_a_kept_record_without_read_group_is_a_bad_read(packed):
         with pytest.raises(BadReadError) as err:
             eng.tabulate(b, packed=packed)
         assert err.value.read_index == int(kept[1234])
+
+
+def _setters():
+    """name -> a call of that setter on an engine of four tables that returns its code: four groups of every kind."""
+    from mapdamage_amd import pmd
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)                    # noqa: E731
+    tid = np.array([0, 1, 2, 3, 0], np.int32)
+    off, start, end, group = np.array([0, 1, 1, 1, 1, 1], np.int64), np.array([10], np.int32), np.array([20], np.int32), np.array([0], np.int32)
+    fx, terms = np.array([pmd.threshold_fx(t) for t in (0.0, 1.0, 2.0)], np.int64), np.ascontiguousarray(pmd.term_table(), np.int32)
+    return {"mdx_set_strata": lambda e: e._lib.mdx_set_strata(e._ctx, 4, ptr(tid), 5),
+            "mdx_set_strata_regions": lambda e: e._lib.mdx_set_strata_regions(e._ctx, 4, 5, ptr(off), ptr(start), ptr(end), ptr(group), 3),
+            "mdx_set_strata_damage": lambda e: e._lib.mdx_set_strata_damage(e._ctx, 1, 0),
+            "mdx_set_strata_pmd": lambda e: e._lib.mdx_set_strata_pmd(e._ctx, 3, ptr(fx), ptr(terms), 0)}
+
+
+@pytest.mark.parametrize("first", ["mdx_set_strata", "mdx_set_strata_regions", "mdx_set_strata_damage", "mdx_set_strata_pmd"])
+def test_a_context_has_one_kind_of_strata(first):
+    """On a fresh context kind A is set; every other setter is a state error that names A's setter, and A again is allowed.
+    (No record is counted, no kernel launched.)"""
+    from mapdamage_amd.engine import DamageEngine
+    from mapdamage_amd import layout as L
+    setters = _setters()
+    with DamageEngine(libraries(1), 70, A, 0, groups=["a", "b", "c", "d"]) as eng:
+        assert setters[first](eng) == 0 and eng._lib.mdx_strata_groups(eng._ctx) == 4
+        for other, call in setters.items():
+            if other != first:
+                assert call(eng) == L.MDX_ERR_STATE, other
+                message = eng._lib.mdx_last_error(eng._ctx).decode()
+                assert "(%s)" % first in message and "one kind" in message, (other, message)
+                assert eng._lib.mdx_strata_groups(eng._ctx) == 4
+        assert setters[first](eng) == 0 and eng._lib.mdx_strata_groups(eng._ctx) == 4
 
 
 def test_argument_and_state_errors():

@@ -260,7 +260,7 @@ def test_hand_made_records(form, minqual):
 
 # ---------------------------------------------------------------------- 3. more strata than the key kernel counts in the LDS
 def test_more_strata_than_the_lds_counts():
-    """1 100 libraries x 4 groups = 4 400 strata (csrc/mdx_libsort.hip LS_LDS_LIBS = 4 096): the kept records are counted
+    """1 100 libraries x 4 groups = 4 400 strata (csrc/mdx_internal.h LS_LDS_LIBS = 4 096): the kept records are counted
     with global atomics.  (--length 20 and a short length histogram: 4 400 tables come back to the host.)"""
     nl, length, lgd_max = 1100, 20, 512
     b = D.grid_batch().slice(0, 3000)
