@@ -673,6 +673,30 @@ typedef struct mdx_index_run {
 int mdx_gbam_kept_index(struct mdx_gbam *g, int64_t stream_base, int32_t *prev_tid, int32_t *prev_pos, mdx_index_run *runs, int64_t runs_cap,
                         int64_t *n_runs, int64_t *bad, int32_t *reason);
 int mdx_gbam_kept_index_linear(struct mdx_gbam *g, uint64_t *out, int64_t n, int64_t *n_words);
+/* --mask-ends: the written records handed on with the damaged ends of their molecules masked — base N, quality 0 — in the
+ * same pass (not a reference option; what `bam trimBam` or `pmdtools --adjustbaseq` behind the run would have done).  The rule
+ * is csrc/mdx_kept_mask.h: windows of k5 / k3 query bases (SEQ without its terminal soft clips, gaps not counted) at the
+ * molecule's 5' and 3' ends — a reverse-strand record's 5' end is its stored right end —, and what a window selects:
+ *   MDX_MASK_ALL          every base of it;
+ *   MDX_MASK_TRANSITIONS  the 5' window a stored T (reverse strand: A), the 3' window a stored A (reverse strand: T), with
+ *                         single_stranded what the 5' window selects;
+ *   MDX_MASK_MISMATCHES   those of them under which the resident reference (mdx_set_reference*) has the partner, C under T
+ *                         and G under A.
+ * No record changes its length, no tag (NM, MD) is touched: sizes, offsets, tags and index are what they are without.
+ *   mdx_gbam_set_kept_mask     the mask of every later mdx_gbam_write_kept / _tagged call of the handle: one kernel between
+ *                           the gather and the BGZF writer, in place on the handle's stream buffer — the slab's inflated
+ *                           records, which the tabulation and the index read, stay as the file has them.  k5, k3: 0..255;
+ *                           both 0 clears the mask (what and single_stranded are not looked at then).  Setting or clearing
+ *                           zeroes the counts.  MDX_ERR_ARG for a value out of range or an unknown `what`.  A write with
+ *                           MDX_MASK_MISMATCHES on a context without a resident reference: MDX_ERR_STATE, nothing launched.
+ *   mdx_gbam_kept_mask_counts  *records = the written records with at least one masked base, *bases = the masked bases
+ *                           (whatever they held before), summed over the writes since the mask was set; synchronous.
+ * Without a mask a write launches, copies and allocates nothing more than before. */
+#define MDX_MASK_ALL 0
+#define MDX_MASK_TRANSITIONS 1
+#define MDX_MASK_MISMATCHES 2
+int mdx_gbam_set_kept_mask(struct mdx_gbam *g, int32_t k5, int32_t k3, int32_t what, int32_t single_stranded);
+int mdx_gbam_kept_mask_counts(struct mdx_gbam *g, uint64_t *records, uint64_t *bases);
 /* mdx_mr_round: float("%.5f" % x) of rescale.py:275-276 for n MR sums (mr_raw of the rescale calls) on `threads` host threads —
  * the value printed with five decimals, read back, and narrowed to the 32 bits of an MR:f tag; NaN (a record written back
  * unchanged) gives 0. */

@@ -9,6 +9,7 @@
 #include "mdx_filter.h"
 #include "mdx_kept_tags.h"
 #include "mdx_kept_index.h"
+#include "mdx_kept_mask.h"
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
@@ -1568,6 +1569,10 @@ struct mdx_gbam {
     uint64_t view_serial = 0, kept_of_view = 0;
     int64_t kept_written = 0;
     Buf index_dense, index_runs, index_tiles, index_res, index_ref, index_linear;
+    // --mask-ends (mdx_gbam_set_kept_mask): the mask of the writes to come (k5 == k3 == 0: none) and the two words its kernel
+    // adds to, (masked records, masked bases) — allocated when a mask is first set
+    MdxKeptMask kept_mask{};
+    Buf kept_mask_counts;
     std::vector<int64_t> index_ref_host;      // [n_ref] lengths, [n_ref] first windows
     uint64_t index_windows = 0;
     bool reserve(Buf &b, size_t bytes) {
@@ -2520,7 +2525,7 @@ void mdx_gbam_close(mdx_gbam *g) {
     rg_buffer_give(g->device, g->d_rg, g->d_rg_cap);
     if (g->d_filter_counts) (void)hipFree(g->d_filter_counts);
     for (mdx_gbam::Buf *b : {&g->kept_sizes, &g->kept_off, &g->kept_tiles, &g->kept_sel, &g->kept_stream, &g->index_dense, &g->index_runs,
-                             &g->index_tiles, &g->index_res, &g->index_ref, &g->index_linear}) if (b->p) (void)hipFree(b->p);
+                             &g->index_tiles, &g->index_res, &g->index_ref, &g->index_linear, &g->kept_mask_counts}) if (b->p) (void)hipFree(b->p);
     for (int k = 0; k < 3; k++) pf_buffer_give(g->device, g->pf_buf[k], g->pf_cap[k]);
     lap("device");
     // (unmapping the file — a few hundred thousand touched pages — is 3-4 ms of an 8 M-record file's 63; done behind the
@@ -2756,6 +2761,13 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
                 }
             }
         }
+        // (--mask-ends: the mask of mdx_gbam_set_kept_mask; its mismatches look at the context's reference)
+        const bool masked = (g->kept_mask.k5 | g->kept_mask.k3) != 0u;
+        MdxKeptMask mask = g->kept_mask;
+        if (masked && mask.what == MDX_MASK_MISMATCHES && !mdx_ctx_reference(g->ctx, &mask.ref, &mask.contig_off, &mask.n_contig)) {
+            g->error = std::string(fn) + "a mask of mismatches on a context without a resident reference (mdx_set_reference first)";
+            return MDX_ERR_STATE;
+        }
         const int64_t n = g->view_reads;
         if (n == 0) { g->kept_of_view = g->view_serial; g->kept_written = 0; return MDX_OK; }
         if (n > 0xFFFFFFFFll) return MDX_ERR_ARG;
@@ -2806,6 +2818,9 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
         else
             mdx_k_gbam_kept_gather((const uint8_t *)s.unc.p, (const uint32_t *)s.rec_off.p, (const uint32_t *)g->kept_sizes.p,
                                    (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p, st);
+        if (masked)
+            mdx_k_gbam_kept_mask((const uint32_t *)g->kept_sizes.p, (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p,
+                                 mask, (unsigned long long *)g->kept_mask_counts.p, st);
         if (!ok(hipGetLastError())) return rc;
         rc = bgzf_deflate_impl(st, g->device, nullptr, (const uint8_t *)g->kept_stream.p, (int64_t)total[1], out, out_cap, out_len);
         if (rc != MDX_OK) { g->error = std::string(fn) + "the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
@@ -2820,6 +2835,41 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
 int mdx_gbam_write_kept(mdx_gbam *g, const uint8_t *group_selected, int32_t n_groups, uint8_t *out, int64_t out_cap, int64_t *out_len,
                         int64_t *n_written, int64_t *raw_bytes) {
     return mdx_gbam_write_kept_tagged(g, group_selected, n_groups, nullptr, nullptr, out, out_cap, out_len, n_written, raw_bytes, nullptr);
+}
+
+// --mask-ends (include/mdx.h; the rule: mdx_kept_mask.h): the mask of the handle's later writes, and the sums of its kernel's
+// counts since it was set
+int mdx_gbam_set_kept_mask(mdx_gbam *g, int32_t k5, int32_t k3, int32_t what, int32_t single_stranded) {
+    if (!g) return MDX_ERR_ARG;
+    const bool clear = k5 == 0 && k3 == 0;
+    if (!clear && !mdx_kept_mask_valid(k5, k3, what, single_stranded)) {
+        g->error = "mdx_gbam_set_kept_mask: k5 and k3 are 0..255, what is MDX_MASK_ALL, _TRANSITIONS or _MISMATCHES, single_stranded 0 or 1";
+        return MDX_ERR_ARG;
+    }
+    if (!clear || g->kept_mask_counts.p) {
+        if (hipSetDevice(g->device) != hipSuccess || !g->reserve(g->kept_mask_counts, 16)) return MDX_ERR_HIP;
+        // (behind the writes so far on the context's stream, in front of those to come)
+        if (hipMemsetAsync(g->kept_mask_counts.p, 0, 16, g->stream) != hipSuccess) {
+            (void)hipGetLastError(); g->error = "mdx_gbam_set_kept_mask: the counts could not be zeroed"; return MDX_ERR_HIP;
+        }
+    }
+    g->kept_mask = MdxKeptMask{};
+    if (!clear) {
+        g->kept_mask.k5 = (uint32_t)k5; g->kept_mask.k3 = (uint32_t)k3;
+        g->kept_mask.what = (uint32_t)what; g->kept_mask.single_stranded = (uint32_t)single_stranded;
+    }
+    return MDX_OK;
+}
+int mdx_gbam_kept_mask_counts(mdx_gbam *g, uint64_t *records, uint64_t *bases) {
+    if (!g || !records || !bases) return MDX_ERR_ARG;
+    uint64_t c[2] = {0, 0};
+    if (g->kept_mask_counts.p) {
+        if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
+        if (hipMemcpyAsync(c, g->kept_mask_counts.p, 16, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+            hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->error = "mdx_gbam_kept_mask_counts: the copy failed"; return MDX_ERR_HIP; }
+    }
+    *records = c[0]; *bases = c[1];
+    return MDX_OK;
 }
 
 // --write-index (include/mdx.h; the rule: mdx_kept_index.h): the runs of equal (tid, bin) among the records the last

@@ -1621,6 +1621,14 @@ const float *mdx_ctx_strata_scores(const mdx_ctx *c, uint64_t *serial) {
     return c && c->strata.pmd_scores_serial != 0 ? (const float *)c->strata.pmd_scores.p : nullptr;
 }
 
+int mdx_ctx_reference(const mdx_ctx *c, const uint8_t **ref, const int64_t **contig_off, int32_t *n_contig) {
+    if (!c || !c->d_ref || !c->d_contig_off || c->n_contig <= 0) return 0;
+    if (ref) *ref = c->d_ref + 256;   // (kRefPad)
+    if (contig_off) *contig_off = c->d_contig_off;
+    if (n_contig) *n_contig = c->n_contig;
+    return 1;
+}
+
 int mdx_ctx_stream(mdx_ctx *c, void **stream, int *device) {
     if (!c) return MDX_ERR_ARG;
     if (stream) *stream = (void *)c->stream;

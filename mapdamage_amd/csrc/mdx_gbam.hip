@@ -700,6 +700,43 @@ __global__ __launch_bounds__(256) void gbam_kept_gather_tagged_kernel(const u8 *
 }
 }  // namespace
 
+// ---- the ends of the written records masked in that stream (--mask-ends; host side: mdx_gbam_set_kept_mask; the rule:
+// mdx_kept_mask.h).  A lane per record of the view, behind the gather: a written record (sizes[r] != 0) lies at out + offsets[r],
+// its block_size field first and sizes[r] - 4 bytes behind it, tags included.  The lane reads the record's header and CIGAR and
+// the at most 2 x 255 bases at its ends — lines the gather has just written — whatever the record's length, so a record above
+// KEPT_WAVE_BYTES goes the same way.  Every store is a byte of the lane's own record: a SEQ byte's two nibbles belong to one
+// record, and the rule checks qual_at + l_seq against the record's bytes before its first store.  The slab's inflated buffer
+// is not touched.  The block's two counts go to the handle's words by two 64-bit atomics.
+#include "mdx_kept_mask.h"
+namespace {
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_mask_kernel(const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                                  u32 n_rec, u8 *out, MdxKeptMask m, unsigned long long *__restrict__ counts) {
+    __shared__ u64 sh_n[4], sh_b[4];
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    u32 masked = 0;
+    if (r < n_rec) {
+        const u32 sz = sizes[r];
+        if (sz > 4u) masked = mdx_kept_mask_record(out + offsets[r] + 4, sz - 4u, m);
+    }
+    u64 nn = masked ? 1ull : 0ull, bb = masked;
+    for (int o = 32; o > 0; o >>= 1) {
+        nn += (u64)__shfl_down((unsigned long long)nn, o);
+        bb += (u64)__shfl_down((unsigned long long)bb, o);
+    }
+    if ((threadIdx.x & 63u) == 0) { sh_n[threadIdx.x >> 6] = nn; sh_b[threadIdx.x >> 6] = bb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const u64 n = sh_n[0] + sh_n[1] + sh_n[2] + sh_n[3], b = sh_b[0] + sh_b[1] + sh_b[2] + sh_b[3];
+        if (n != 0ull) { atomicAdd(counts, (unsigned long long)n); atomicAdd(counts + 1, (unsigned long long)b); }
+    }
+}
+}  // namespace
+void mdx_k_gbam_kept_mask(const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec, uint8_t *out, const MdxKeptMask &m,
+                          unsigned long long *counts, hipStream_t s) {
+    if (n_rec == 0) return;
+    hipLaunchKernelGGL(gbam_kept_mask_kernel, dim3((n_rec + KEPT_TILE - 1) / KEPT_TILE), dim3(KEPT_TILE), 0, s, sizes, offsets, n_rec, out, m, counts);
+}
+
 int mdx_k_gbam_kept_tile() { return KEPT_TILE; }
 void mdx_k_gbam_kept_offsets(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint16_t *key, const uint8_t *selected,
                              uint32_t n_groups, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base, unsigned long long *offsets,

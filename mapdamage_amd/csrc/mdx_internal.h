@@ -477,6 +477,9 @@ extern "C" int mdx_ctx_strata_key(const mdx_ctx *c, const uint16_t **key, const 
 // the score column beside it (mdx_strata_pmd_keep_scores; device) and the *serial of the keyed batch it belongs to; null and 0
 // where the batch keyed last left none
 extern "C" const float *mdx_ctx_strata_scores(const mdx_ctx *c, uint64_t *serial);
+// the resident reference (device): base 0 of sequence 0 in MdxTabArgs::ref's encoding, the n_contig + 1 sums of the lengths;
+// returns 0, and writes nothing, where none is resident
+extern "C" int mdx_ctx_reference(const mdx_ctx *c, const uint8_t **ref, const int64_t **contig_off, int32_t *n_contig);
 extern "C" void mdx_ctx_scratch_give(mdx_ctx *c, void *arena, size_t cap, void *tables, void *stream, void *event);
 extern "C" void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, void **stream, void **event);
 
@@ -571,6 +574,13 @@ void mdx_k_gbam_kept_offsets_tagged(const uint8_t *unc, const uint32_t *rec_off,
                                     unsigned long long *offsets, uint32_t *clash, hipStream_t s);
 void mdx_k_gbam_kept_gather_tagged(const uint8_t *unc, const uint32_t *rec_off, const uint32_t *sizes, const unsigned long long *offsets,
                                    uint32_t n_rec, uint8_t *out, const MdxKeptTags &tg, hipStream_t s);
+
+// ... with the ends of the written records masked in place in that stream (--mask-ends; host side: mdx_gbam_set_kept_mask; the
+// rule and MdxKeptMask: mdx_kept_mask.h), behind either gather: out + offsets[r] for every r with sizes[r] != 0;
+// counts[0] += the records with a masked base, counts[1] += the masked bases (device)
+struct MdxKeptMask;
+void mdx_k_gbam_kept_mask(const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec, uint8_t *out, const MdxKeptMask &m,
+                          unsigned long long *counts, hipStream_t s);
 
 // ... and the BAI index of that stream (--write-index; host side: mdx_gbam_kept_index; the rule: mdx_kept_index.h).  MdxKeptIndex:
 // the dense list of the slab's written records (n_written entries each); MdxIndexRun: a maximal run of written records with

@@ -22,7 +22,7 @@ from .groupings import PmdScore, TerminalDamage        # noqa: F401  (where call
 from .fasta import compare_sequence_dicts, ensure_fasta_index, is_bgzf, is_plain_gzip, read_fasta_index, reference_for_bam
 from .layout import FLAG_FILTER
 from .reader import BAMReader, draw_uniform, is_stream
-from .sam import SAM_BGZF, SAM_GZIP, BAMError, KeptIndexError, KeptTagClash
+from .sam import MASK_WHAT, SAM_BGZF, SAM_GZIP, BAMError, KeptIndexError, KeptTagClash
 from .statistics import check_table_and_warn_if_dmg_freq_is_low
 
 _LOG_FORMAT = "%(asctime)s %(name)s %(levelname)s %(message)s"
@@ -233,6 +233,19 @@ def build_parser():
                         "run has on the device — what `samtools index BAM` behind the run would make by inflating the file "
                         "again.  The written records must be in coordinate order and lie inside the first 2^29 bases of their "
                         "reference sequences (BAI's limit; CSI is not written); the first one that does not ends the run")
+    g.add_argument("--mask-ends", default=None, metavar="K5[,K3]",
+                   help="with --write-kept: hand the written records on with the damaged ends of their molecules masked — base N, "
+                        "quality 0 — inside the first K5 query bases of the molecule's 5' end and the last K3 of its 3' end (one "
+                        "number: both; 0..255 each, not both 0).  A reverse-strand record's 5' end is its stored right end.  The "
+                        "windows count query bases (SEQ without its soft clips), not the tables' positions: gap columns are not "
+                        "counted.  No record changes its length and no tag (NM, MD) is touched, as `bam trimBam` leaves them; the "
+                        "tables, groups and tags are those of the reads as they are.  mask_ends.tsv gives the records and bases "
+                        "masked.  Not a reference option")
+    g.add_argument("--mask-what", choices=MASK_WHAT, default=None,
+                   help="with --mask-ends: `all` bases of the windows (the default); the `transitions` alone, T in the 5' window and "
+                        "A in the 3' window of the molecule's own strand (T in both with --single-stranded); or those of them that "
+                        "are `mismatches`, with C or G in the reference underneath — which keeps the true T and A, and with them the "
+                        "bias towards the reference that `transitions` does not have")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -278,8 +291,37 @@ def check_write_groups(groups, n_groups):
                              % (index, n_groups - 1, n_groups))
 
 
+def parse_mask_ends(text):
+    """--mask-ends, ``K5[,K3]``, as ``(k5, k3)``: one number means both ends.  ValueError for anything but one or two decimal
+    integers of 0..255 that are not both 0."""
+    entries = [entry.strip() for entry in str(text).split(",")]
+    if len(entries) > 2:
+        raise ValueError("%r has more than two numbers (K5[,K3])" % str(text))
+    values = []
+    for entry in entries:
+        if not re.fullmatch(r"[0-9]+", entry):
+            raise ValueError("%r is not a number of bases (K5[,K3], 0..255 each)" % entry)
+        if int(entry) > 255:
+            raise ValueError("%s is above 255 bases" % entry)
+        values.append(int(entry))
+    k5, k3 = values if len(values) == 2 else (values[0], values[0])
+    if k5 == 0 and k3 == 0:
+        raise ValueError("both ends are 0 bases: nothing to mask")
+    return k5, k3
+
+
 def _check_write_kept(parser, o):
-    """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score."""
+    """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score / --write-index / --mask-ends."""
+    if o.mask_what is not None and o.mask_ends is None:
+        parser.error("--mask-what needs --mask-ends: it says what the windows of that option select")
+    if o.mask_ends is not None:
+        if o.write_kept is None:
+            parser.error("--mask-ends needs --write-kept: it masks the records that file receives")
+        try:
+            o.mask_ends = parse_mask_ends(o.mask_ends)
+        except ValueError as error:
+            parser.error("--mask-ends: %s" % error)
+        o.mask_what = o.mask_what or "all"
     if o.write_groups is not None:
         if o.write_kept is None:
             parser.error("--write-groups needs --write-kept: it chooses the groups whose records that file receives")
@@ -789,6 +831,11 @@ class _KeptOutput:
             self.index_path = Path(str(self.path) + ".bai")
             self.index_tmp = self.index_path.with_name("%s.%d.tmp" % (self.index_path.name, os.getpid()))
             self.index_prev = (-1, -1)
+        # (--mask-ends: the stream masks every slab it writes from here on, and counts)
+        self.mask = getattr(options, "mask_ends", None)
+        if self.mask is not None:
+            self.mask_what, self.mask_single = options.mask_what, bool(options.single_stranded)
+            stream.set_kept_mask(self.mask[0], self.mask[1], self.mask_what, self.mask_single)
         self.writer = BgzfWriter(self.tmp, engine=engine)
         try:
             self.writer.write(bam_header_bytes(stream.header))
@@ -812,6 +859,7 @@ class _KeptOutput:
 
     def commit(self, logger):
         index = None
+        masked = self.stream.kept_mask_counts() if self.mask is not None else None
         if self.index is not None:
             index = self.index.finish(self.stream.kept_index_linear())
             self.index_tmp.write_bytes(index)
@@ -826,6 +874,12 @@ class _KeptOutput:
         logger.info("Wrote %d records to %s (groups: %s)%s", self.records, self.path, which, "; tags: " + ", ".join(tags) if tags else "")
         (self.folder / "write_kept.tsv").write_text("path\tgroups\trecords\tuncompressed_bytes\n%s\t%s\t%d\t%d\n"
                                                     % (self.path, which, self.records, self.raw_bytes))
+        if masked is not None:
+            logger.info("Masked %d bases in %d of %d written records (5p %d, 3p %d: %s)", masked[1], masked[0], self.records,
+                        self.mask[0], self.mask[1], self.mask_what)
+            (self.folder / "mask_ends.tsv").write_text("path\tk5\tk3\twhat\tsingle_stranded\trecords\tbases\n%s\t%d\t%d\t%s\t%d\t%d\t%d\n"
+                                                       % (self.path, self.mask[0], self.mask[1], self.mask_what, int(self.mask_single),
+                                                          masked[0], masked[1]))
         if index is not None:
             logger.info("Wrote index %s (%d references with records, %d chunks)", self.index_path, self.index.n_references, self.index.n_chunks)
 

@@ -798,6 +798,37 @@ class GpuBamStream:
             raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
         return out[:out_len.value], int(n_written.value), int(raw_bytes.value)
 
+    def set_kept_mask(self, k5, k3, what="all", single_stranded=False):
+        """The mask of every later ``write_kept`` of this stream (include/mdx.h ``mdx_gbam_set_kept_mask``; the rule:
+        csrc/mdx_kept_mask.h): the written records' bases inside the first ``k5`` query bases of the molecule's 5' end and the
+        last ``k3`` of its 3' end (0..255 each) become N with quality 0 — ``what``: ``all`` of them, the ``transitions`` (T at
+        the 5' end, A at the 3' end as the forward strand stores them; with ``single_stranded`` T at both), or those of them
+        that are ``mismatches`` against the engine's reference (C under T, G under A).  ``k5 == k3 == 0`` clears the mask.
+        Either way the counts start again at 0.  ValueError for an unknown ``what``, ``MdxError`` -1 for a value out of range."""
+        import ctypes
+        if what not in MASK_WHAT:
+            raise ValueError("what is one of %s, not %r" % (", ".join(MASK_WHAT), what))
+        fn = self._lib.mdx_gbam_set_kept_mask
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], ctypes.c_int
+        rc = fn(self._g, ctypes.c_int32(int(k5)), ctypes.c_int32(int(k3)), ctypes.c_int32(MASK_WHAT.index(what)),
+                ctypes.c_int32(1 if single_stranded else 0))
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+
+    def kept_mask_counts(self):
+        """``(records, bases)``: the written records with a masked base and the masked bases, summed over the ``write_kept``
+        calls since ``set_kept_mask`` (``mdx_gbam_kept_mask_counts``)."""
+        import ctypes
+        fn = self._lib.mdx_gbam_kept_mask_counts
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        records, bases = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = fn(self._g, ctypes.byref(records), ctypes.byref(bases))
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        return int(records.value), int(bases.value)
+
     def kept_index(self, stream_base, prev, n_written):
         """The index entries of the records the last ``write_kept`` of this view wrote (include/mdx.h ``mdx_gbam_kept_index``;
         the rule: csrc/mdx_kept_index.h): ``(runs, prev)`` — ``runs`` a ``bai.RUN_DTYPE`` array, the maximal runs of written
@@ -1082,6 +1113,9 @@ def sam_header(src):
 
 class GpuDecodeUnsupported(ValueError):
     """The file's layout is not one the GPU decode path takes (MDX_ERR_UNSUPPORTED)."""
+
+
+MASK_WHAT = ("all", "transitions", "mismatches")      # include/mdx.h MDX_MASK_*, by value (--mask-what)
 
 
 class KeptTagClash(Exception):

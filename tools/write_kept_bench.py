@@ -10,16 +10,19 @@ one BAM, then three commands timed as cold processes, each under a time limit of
   --index instead: the records in coordinate order (synth's sort=True), and the legs
   plain, kept as above, and
   kept_index  `--write-kept kept_index.bam --write-index`                                                ... and its BAI index
+  --mask-ends K5[,K3] instead: the legs plain, kept, and one per --mask-what,
+  mask_all, mask_transitions, mask_mismatches  `--write-kept mask_X.bam --mask-ends K5,K3 --mask-what X`   ... handed on masked
 
 The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
 times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
 (write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost, pmd_tagged - pmd_all that
 of the tags (12 bytes a record, the score column, the walk over every written record's tags), kept_index - kept that of the
-index (four launches and two small copies per slab, the file's assembly on the host).  --parent-root DIR: a
+index (four launches and two small copies per slab, the file's assembly on the host), mask_X - kept that of the mask (one
+launch per slab, in place in the stream; mask_ends.tsv gives the records and bases it masked).  --parent-root DIR: a
 built checkout of the parent commit; `plain` is then also timed there, in the same alternation — a difference between the two
 beyond the spread means the option-less path has changed.  One JSON line on stdout.
 
-    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index]"""
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index | --mask-ends K]"""
 import argparse
 import json
 import os
@@ -53,6 +56,7 @@ def main():
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
     ap.add_argument("--tags", action="store_true", help="also time --by-pmd-score --write-kept with and without --tag-group / --tag-pmd-score")
     ap.add_argument("--index", action="store_true", help="coordinate-sorted records; time --write-kept with and without --write-index")
+    ap.add_argument("--mask-ends", metavar="K5[,K3]", help="time --write-kept with and without --mask-ends K5[,K3], for each --mask-what")
     args = ap.parse_args()
     import numpy as np
 
@@ -82,6 +86,9 @@ def main():
         if args.index:
             legs = legs[:2] + [("kept_index", ROOT, ["--write-kept", os.path.join(work, "kept_index.bam"), "--write-index"])]
             result["sorted"] = True
+        if args.mask_ends:
+            legs = legs[:2] + [("mask_" + what, ROOT, ["--write-kept", os.path.join(work, "mask_%s.bam" % what), "--mask-ends", args.mask_ends,
+                                                       "--mask-what", what]) for what in ("all", "transitions", "mismatches")]
         if args.tags:
             pmd_all = ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept"]
             legs += [("pmd_all", ROOT, pmd_all + [os.path.join(work, "pmd_all.bam")]),
@@ -113,7 +120,7 @@ def main():
                 path, groups, records, raw = open(tsv).read().splitlines()[1].split("\t")
                 result[name].update(groups=groups, records_written=int(records), uncompressed_bytes=int(raw), file_bytes=os.path.getsize(path))
         if status == 0:
-            for name in ("kept",) if args.index else ("kept", "pmd"):
+            for name in ("kept",) if args.index or args.mask_ends else ("kept", "pmd"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
             if args.index:
                 result["kept_index_minus_kept_s"] = round(result["kept_index"]["median_s"] - result["kept"]["median_s"], 3)
@@ -124,6 +131,14 @@ def main():
                 same_file = open(os.path.join(work, "kept.bam"), "rb").read() == open(os.path.join(work, "kept_index.bam"), "rb").read()
                 if not same_file or result["kept_index"]["index_bytes"] is None:
                     result["error"] = "kept_index.bam differs from kept.bam, or no index was written"
+            if args.mask_ends:
+                for what in ("all", "transitions", "mismatches"):
+                    leg = result["mask_" + what]
+                    result["mask_%s_minus_kept_s" % what] = round(leg["median_s"] - result["kept"]["median_s"], 3)
+                    row = open(os.path.join(work, "mask_" + what, "mask_ends.tsv")).read().splitlines()[1].split("\t")
+                    leg.update(masked_records=int(row[5]), masked_bases=int(row[6]))
+                    if (leg["records_written"], leg["uncompressed_bytes"]) != (result["kept"]["records_written"], result["kept"]["uncompressed_bytes"]):
+                        result["error"] = "mask_%s.bam does not hold kept.bam's records and bytes" % what
             if args.tags:
                 result["pmd_tagged_minus_pmd_all_s"] = round(result["pmd_tagged"]["median_s"] - result["pmd_all"]["median_s"], 3)
                 extra = result["pmd_tagged"]["uncompressed_bytes"] - result["pmd_all"]["uncompressed_bytes"]
