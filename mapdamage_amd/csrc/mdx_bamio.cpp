@@ -2569,7 +2569,10 @@ static int bgzf_deflate_impl(hipStream_t st, int device, const uint8_t *data, co
     const int kBgzfBatch = 8192;
     // (buffers for as many members as this call has, never fewer than a fifth of a launch's — a process that writes a header
     // first and a gigabyte behind it allocates once)
-    const int batch = (int)std::min<int64_t>(std::max<int64_t>(total_members, kBgzfBatch / 4), kBgzfBatch);
+    int batch = (int)std::min<int64_t>(std::max<int64_t>(total_members, kBgzfBatch / 4), kBgzfBatch);
+    // (MDX_BGZF_BATCH=<n>, read on every call: exactly n members per launch, 1..8192 — the tests' way to a second launch and a
+    // short last one without half a gigabyte of input)
+    if (const char *e = std::getenv("MDX_BGZF_BATCH")) batch = (int)std::min<long>(std::max<long>(std::atol(e), 1), kBgzfBatch);
     const int pieces = mdx_k_bgzf_pieces();
     int rc = MDX_OK;
     auto ok = [&](hipError_t e) { if (e != hipSuccess) { rc = MDX_ERR_HIP; (void)hipGetLastError(); } return e == hipSuccess; };
