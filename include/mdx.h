@@ -697,6 +697,31 @@ int mdx_gbam_kept_index_linear(struct mdx_gbam *g, uint64_t *out, int64_t n, int
 #define MDX_MASK_MISMATCHES 2
 int mdx_gbam_set_kept_mask(struct mdx_gbam *g, int32_t k5, int32_t k3, int32_t what, int32_t single_stranded);
 int mdx_gbam_kept_mask_counts(struct mdx_gbam *g, uint64_t *records, uint64_t *bases);
+/* --calmd: every written record leaves with NM and MD recomputed against the resident reference (not a reference option;
+ * what `samtools calmd` behind the run would have done, by inflating, rewriting and deflating the file again).  The rule is
+ * csrc/mdx_kept_md.h: one walk over the record's operations gives the edit count and the MD string; the record keeps its fields
+ * and its tags in their order without every field named NM or MD, then NM (C, S or I: the smallest that holds it) and MD:Z
+ * follow, and block_size is the new length — a record may grow or shrink.  Computed from the bytes the file will hold: behind
+ * the mask of mdx_gbam_set_kept_mask, with the tags of mdx_gbam_write_kept_tagged in place.  A record the rule cannot follow
+ * (its CIGAR does not fill SEQ, it lies outside its sequence, its tags cannot be walked to its end, it has a CG:B tag, its MD
+ * would pass 2 * l_seq + 64 characters) is skipped: written byte for byte as it is.  The resident reference keeps no IUPAC
+ * letters: an ambiguity code of the FASTA appears in MD as N, and no base of a read matches it.
+ *   mdx_gbam_set_kept_md     on != 0: every later mdx_gbam_write_kept / _tagged call of the handle runs the stage — the new
+ *                           sizes, their scan, sixteen bytes back and a rewrite into a second stream buffer of the handle,
+ *                           which is what gets compressed; *raw_bytes is the new total, and mdx_gbam_kept_index behind the
+ *                           write describes the new stream.  0 switches it off.  Either way the counts start again at 0.  A
+ *                           write on a context without a resident reference (mdx_set_reference*): MDX_ERR_STATE, nothing
+ *                           launched.
+ *   mdx_gbam_kept_md_counts  out[0] = the written records recomputed, out[1] = those skipped, out[2] = those that had an NM or
+ *                           MD field (in tags that can be walked), summed over the writes since the stage was switched;
+ *                           synchronous.
+ *   mdx_gbam_kept_bound_md   mdx_gbam_kept_bound_tagged, and with md != 0 what the stage can add: a record grows by at most
+ *                           7 (NM:I) + 3 + (2 * l_seq + 64) + 1 bytes, and a recomputed record holds its SEQ and QUAL, so
+ *                           2 * l_seq <= 4 * block_size / 3 — 75 bytes per record of the view and four thirds of its bytes.
+ * Without the stage a write launches, copies and allocates nothing more than before. */
+int mdx_gbam_set_kept_md(struct mdx_gbam *g, int32_t on);
+int mdx_gbam_kept_md_counts(struct mdx_gbam *g, uint64_t out[3]);
+int mdx_gbam_kept_bound_md(struct mdx_gbam *g, int32_t tag_bytes, int32_t md, int64_t *bytes);
 /* mdx_mr_round: float("%.5f" % x) of rescale.py:275-276 for n MR sums (mr_raw of the rescale calls) on `threads` host threads —
  * the value printed with five decimals, read back, and narrowed to the 32 bits of an MR:f tag; NaN (a record written back
  * unchanged) gives 0. */

@@ -10,6 +10,7 @@
 #include "mdx_kept_tags.h"
 #include "mdx_kept_index.h"
 #include "mdx_kept_mask.h"
+#include "mdx_kept_md.h"
 #include "mdx_crc32.h"
 
 #include <fcntl.h>
@@ -1573,6 +1574,11 @@ struct mdx_gbam {
     // adds to, (masked records, masked bases) — allocated when a mask is first set
     MdxKeptMask kept_mask{};
     Buf kept_mask_counts;
+    // --calmd (mdx_gbam_set_kept_md): on for the writes to come; the stage's own sizes, offsets, tiles and stream — swapped
+    // with the kept kernels' behind every write that ran it, so that kept_* describe the stream that was written — and the
+    // three words its sizes kernel adds to (recomputed, skipped, had NM or MD), allocated when the stage is first switched on
+    bool kept_md = false;
+    Buf md_sizes, md_off, md_tiles, md_stream, kept_md_counts;
     std::vector<int64_t> index_ref_host;      // [n_ref] lengths, [n_ref] first windows
     uint64_t index_windows = 0;
     bool reserve(Buf &b, size_t bytes) {
@@ -2525,7 +2531,8 @@ void mdx_gbam_close(mdx_gbam *g) {
     rg_buffer_give(g->device, g->d_rg, g->d_rg_cap);
     if (g->d_filter_counts) (void)hipFree(g->d_filter_counts);
     for (mdx_gbam::Buf *b : {&g->kept_sizes, &g->kept_off, &g->kept_tiles, &g->kept_sel, &g->kept_stream, &g->index_dense, &g->index_runs,
-                             &g->index_tiles, &g->index_res, &g->index_ref, &g->index_linear, &g->kept_mask_counts}) if (b->p) (void)hipFree(b->p);
+                             &g->index_tiles, &g->index_res, &g->index_ref, &g->index_linear, &g->kept_mask_counts, &g->md_sizes, &g->md_off, &g->md_tiles,
+                             &g->md_stream, &g->kept_md_counts}) if (b->p) (void)hipFree(b->p);
     for (int k = 0; k < 3; k++) pf_buffer_give(g->device, g->pf_buf[k], g->pf_cap[k]);
     lap("device");
     // (unmapping the file — a few hundred thousand touched pages — is 3-4 ms of an 8 M-record file's 63; done behind the
@@ -2708,12 +2715,18 @@ int mdx_gbam_record_name(mdx_gbam *g, int64_t index, char *buf, int32_t cap) {
 // --write-kept (include/mdx.h): the capacity that suffices for mdx_gbam_write_kept on the view handed out last — its records'
 // inflated bytes (every one of them kept, stored members: 26 bytes each and a few for the stored blocks' headers) —, with
 // tag_bytes more for every record of the view where tags are appended (mdx_gbam_write_kept_tagged: 5, 7 or 12)
-int mdx_gbam_kept_bound_tagged(mdx_gbam *g, int32_t tag_bytes, int64_t *bytes) {
+// ... and, with md != 0, with what mdx_gbam_set_kept_md can add.  A record grows by at most 7 (NM:I) + 3 (MDZ) + 2 * l_seq + 64
+// (the string's cap, mdx_kept_md.h) + 1 (its NUL) = 2 * l_seq + 75 bytes.  Only a record whose SEQ and QUAL lie inside it is
+// recomputed: (l_seq + 1) / 2 + l_seq <= block_size, so 2 * l_seq <= 4 * block_size / 3, and the sum of the block sizes is
+// below the view's inflated bytes.  Hence the view grows by at most 75 * n_reads + 4 * bytes / 3 (rounded up).
+int mdx_gbam_kept_bound_md(mdx_gbam *g, int32_t tag_bytes, int32_t md, int64_t *bytes) {
     if (!g || !bytes || tag_bytes < 0 || tag_bytes > (int32_t)(MDX_KEPT_GROUP_TAG_BYTES + MDX_KEPT_SCORE_TAG_BYTES)) return MDX_ERR_ARG;
-    const int64_t b = (int64_t)g->view_rec_bytes + (int64_t)tag_bytes * g->view_reads;
+    int64_t b = (int64_t)g->view_rec_bytes + (int64_t)tag_bytes * g->view_reads;
+    if (md) b += (int64_t)MDX_MD_GROWTH(0) * g->view_reads + (4 * b + 2) / 3;
     *bytes = b + 64 * (b / 0xFF00) + 64;
     return MDX_OK;
 }
+int mdx_gbam_kept_bound_tagged(mdx_gbam *g, int32_t tag_bytes, int64_t *bytes) { return mdx_gbam_kept_bound_md(g, tag_bytes, 0, bytes); }
 int mdx_gbam_kept_bound(mdx_gbam *g, int64_t *bytes) { return mdx_gbam_kept_bound_tagged(g, 0, bytes); }
 
 // ... and the records the run counted (or those of the chosen groups among them) as BGZF members: sizes by the rule of
@@ -2771,6 +2784,12 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
             g->error = std::string(fn) + "a mask of mismatches on a context without a resident reference (mdx_set_reference first)";
             return MDX_ERR_STATE;
         }
+        // (--calmd: the stage of mdx_gbam_set_kept_md reads the context's reference)
+        MdxKeptMask md_ref{};
+        if (g->kept_md && !mdx_ctx_reference(g->ctx, &md_ref.ref, &md_ref.contig_off, &md_ref.n_contig)) {
+            g->error = std::string(fn) + "NM and MD are recomputed against the resident reference, and the context has none (mdx_set_reference first)";
+            return MDX_ERR_STATE;
+        }
         const int64_t n = g->view_reads;
         if (n == 0) { g->kept_of_view = g->view_serial; g->kept_written = 0; return MDX_OK; }
         if (n > 0xFFFFFFFFll) return MDX_ERR_ARG;
@@ -2824,6 +2843,27 @@ int mdx_gbam_write_kept_tagged(mdx_gbam *g, const uint8_t *group_selected, int32
         if (masked)
             mdx_k_gbam_kept_mask((const uint32_t *)g->kept_sizes.p, (const unsigned long long *)g->kept_off.p, (uint32_t)n, (uint8_t *)g->kept_stream.p,
                                  mask, (unsigned long long *)g->kept_mask_counts.p, st);
+        if (g->kept_md) {
+            // the stage's own sizes and scan on the stream as it stands, sixteen bytes back, its stream reserved by that total,
+            // the rewrite; then kept_* are the new stream's (mdx_gbam_kept_index reads them)
+            if (!g->reserve(g->md_sizes, (size_t)n * 4) || !g->reserve(g->md_off, (size_t)n * 8) || !g->reserve(g->md_tiles, (2 * n_tiles + 2) * 16))
+                return MDX_ERR_HIP;
+            char *md_tiles = (char *)g->md_tiles.p;
+            mdx_k_gbam_kept_md_offsets((const uint32_t *)g->kept_sizes.p, (const unsigned long long *)g->kept_off.p, (uint32_t)n,
+                                       (const uint8_t *)g->kept_stream.p, md_ref, (uint32_t *)g->md_sizes.p, md_tiles, md_tiles + n_tiles * 16,
+                                       (unsigned long long *)g->md_off.p, (unsigned long long *)g->kept_md_counts.p, st);
+            unsigned long long md_total[2] = {0, 0};
+            if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(md_total, md_tiles + 2 * n_tiles * 16, 16, hipMemcpyDeviceToHost, st)) ||
+                !ok(hipStreamSynchronize(st))) return rc;
+            if (md_total[0] != total[0]) { g->error = std::string(fn) + "the recomputed stream does not hold the records of the gathered one"; return MDX_ERR_ARG; }
+            if (!g->reserve(g->md_stream, (size_t)md_total[1] + 64)) return MDX_ERR_HIP;
+            mdx_k_gbam_kept_md_rewrite((const uint32_t *)g->kept_sizes.p, (const unsigned long long *)g->kept_off.p, (const uint32_t *)g->md_sizes.p,
+                                       (const unsigned long long *)g->md_off.p, (uint32_t)n, (const uint8_t *)g->kept_stream.p,
+                                       (uint8_t *)g->md_stream.p, md_ref, st);
+            std::swap(g->kept_sizes, g->md_sizes); std::swap(g->kept_off, g->md_off);
+            std::swap(g->kept_tiles, g->md_tiles); std::swap(g->kept_stream, g->md_stream);
+            total[1] = md_total[1];
+        }
         if (!ok(hipGetLastError())) return rc;
         rc = bgzf_deflate_impl(st, g->device, nullptr, (const uint8_t *)g->kept_stream.p, (int64_t)total[1], out, out_cap, out_len);
         if (rc != MDX_OK) { g->error = std::string(fn) + "the BGZF writer failed (output buffer below mdx_gbam_kept_bound?)"; return rc; }
@@ -2872,6 +2912,31 @@ int mdx_gbam_kept_mask_counts(mdx_gbam *g, uint64_t *records, uint64_t *bases) {
             hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->error = "mdx_gbam_kept_mask_counts: the copy failed"; return MDX_ERR_HIP; }
     }
     *records = c[0]; *bases = c[1];
+    return MDX_OK;
+}
+
+// --calmd (include/mdx.h; the rule: mdx_kept_md.h): the stage of the handle's later writes on or off, and the sums of its sizes
+// kernel's counts since it was last switched
+int mdx_gbam_set_kept_md(mdx_gbam *g, int32_t on) {
+    if (!g) return MDX_ERR_ARG;
+    if (on || g->kept_md_counts.p) {
+        if (hipSetDevice(g->device) != hipSuccess || !g->reserve(g->kept_md_counts, 24)) return MDX_ERR_HIP;
+        // (behind the writes so far on the context's stream, in front of those to come)
+        if (hipMemsetAsync(g->kept_md_counts.p, 0, 24, g->stream) != hipSuccess) {
+            (void)hipGetLastError(); g->error = "mdx_gbam_set_kept_md: the counts could not be zeroed"; return MDX_ERR_HIP;
+        }
+    }
+    g->kept_md = on != 0;
+    return MDX_OK;
+}
+int mdx_gbam_kept_md_counts(mdx_gbam *g, uint64_t out[3]) {
+    if (!g || !out) return MDX_ERR_ARG;
+    out[0] = out[1] = out[2] = 0;
+    if (g->kept_md_counts.p) {
+        if (hipSetDevice(g->device) != hipSuccess) return MDX_ERR_HIP;
+        if (hipMemcpyAsync(out, g->kept_md_counts.p, 24, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
+            hipStreamSynchronize(g->stream) != hipSuccess) { (void)hipGetLastError(); g->error = "mdx_gbam_kept_md_counts: the copy failed"; return MDX_ERR_HIP; }
+    }
     return MDX_OK;
 }
 

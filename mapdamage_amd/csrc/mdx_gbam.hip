@@ -737,6 +737,130 @@ void mdx_k_gbam_kept_mask(const uint32_t *sizes, const unsigned long long *offse
     hipLaunchKernelGGL(gbam_kept_mask_kernel, dim3((n_rec + KEPT_TILE - 1) / KEPT_TILE), dim3(KEPT_TILE), 0, s, sizes, offsets, n_rec, out, m, counts);
 }
 
+// ---- NM and MD of the written records recomputed (--calmd; host side: mdx_gbam_set_kept_md; the rule: mdx_kept_md.h), behind
+// the gather and the mask kernel: the stream they left is read, a second one written, and that one is compressed.  A record
+// may grow or shrink, so the stage has sizes and offsets of its own:
+//   gbam_kept_md_sizes_kernel    a lane per record of the view: a written record's new bytes by the rule — the walk over its tags
+//                                and the walk over its alignment, nothing stored but the size — into new_sizes[] (a dropped record
+//                                stays 0, a skipped one keeps its bytes), the tile's pair as gbam_kept_sizes_kernel leaves it,
+//                                and the block's three counts (recomputed, skipped, had NM or MD) by three 64-bit atomics
+//   gbam_kept_tiles_kernel, gbam_kept_offsets_kernel    the scan of the kept kernels, on the new sizes
+//   gbam_kept_md_rewrite_kernel  a tile of KEPT_TILE records per block, in two phases.  First a lane per record: the rule again
+//                                — the same bytes give the same plan —, this time with the new block_size, the NM field and the
+//                                MD string stored a byte at a time at their places in the new record, and the stretches of the
+//                                old record that the new one keeps (at most MDX_MD_SEGMENTS; a skipped record is one stretch,
+//                                its block_size field included) left in the LDS.  Then eight lanes per record, thirty-two
+//                                records per round, copy those stretches with kept_copy, the gather's wide loads and stores; a
+//                                stretch above KEPT_WAVE_BYTES is left by its eight lanes and taken by the whole wavefront
+//                                afterwards, as the gather takes a long record.
+// Stores: the first phase's lane writes [dst, dst + 4), the stretches beyond the third (bytes inside the kept part) and the new
+// record's last bytes; the second phase's lanes write the stretches, which lie between.  All of it is inside [dst, dst +
+// new_sizes[r]), the record's own part of the new stream by the scan of the very sizes the plan gives; the host reserves the
+// stream by the scan's total before this kernel is launched.  Loads stay inside the old record and the record's span of its
+// sequence (the rule checks pos + span against the sequence before the walk).
+#include "mdx_kept_md.h"
+namespace {
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_md_sizes_kernel(const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                                      u32 n_rec, const u8 *__restrict__ in, MdxKeptMask m,
+                                                                      u32 *__restrict__ new_sizes, ulonglong2 *__restrict__ tile_sum,
+                                                                      unsigned long long *__restrict__ counts) {
+    __shared__ u32 sh_c[3];
+    const u32 r = blockIdx.x * KEPT_TILE + threadIdx.x;
+    if (threadIdx.x < 3u) sh_c[threadIdx.x] = 0u;
+    __syncthreads();
+    u32 nsz = 0;
+    if (r < n_rec) {
+        const u32 sz = sizes[r];
+        nsz = sz;
+        if (sz != 0u) {
+            MdxKeptMdPlan pl;
+            bool had = false;
+            const bool done = sz > 4u && mdx_kept_md_plan(in + offsets[r] + 4, sz - 4u, m, &pl, &had);
+            if (done) nsz = pl.new_bs + 4u;
+            atomicAdd(&sh_c[done ? 0 : 1], 1u);
+            if (had) atomicAdd(&sh_c[2], 1u);
+        }
+        new_sizes[r] = nsz;
+    }
+    kept_tile_pair(nsz, tile_sum);                  // (a barrier inside: the counts are complete behind it)
+    if (threadIdx.x < 3u && sh_c[threadIdx.x] != 0u) atomicAdd(counts + threadIdx.x, (unsigned long long)sh_c[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(KEPT_TILE) void gbam_kept_md_rewrite_kernel(const u32 *__restrict__ sizes, const unsigned long long *__restrict__ offsets,
+                                                                        const u32 *__restrict__ new_sizes,
+                                                                        const unsigned long long *__restrict__ new_offsets, u32 n_rec,
+                                                                        const u8 *__restrict__ in, u8 *__restrict__ out, MdxKeptMask m) {
+    // per record of the tile: its stretches (offsets from the old record's block_size field) and how many
+    __shared__ u32 sh_at[MDX_MD_SEGMENTS][KEPT_TILE], sh_len[MDX_MD_SEGMENTS][KEPT_TILE];
+    __shared__ u8 sh_n[KEPT_TILE];
+    const u32 t = threadIdx.x, r0 = blockIdx.x * KEPT_TILE;
+    {
+        const u32 r = r0 + t;
+        u32 n_seg = 0;
+        const u32 sz = r < n_rec ? sizes[r] : 0u;
+        if (sz != 0u) {
+            const u8 *__restrict__ src = in + offsets[r];
+            u8 *__restrict__ dst = out + new_offsets[r];
+            MdxKeptMdPlan pl;
+            bool had = false;
+            // (the plan the sizes kernel made: the record's place in the new stream is of pl.new_bs + 4 bytes.  Were it not — it
+            // cannot be — the record would be dropped here rather than stored outside its place.)
+            if (sz > 4u && mdx_kept_md_plan(src + 4, sz - 4u, m, &pl, &had)) {
+                if (pl.new_bs + 4u == new_sizes[r]) {
+                    MdxKeptMdSeg seg[MDX_MD_SEGMENTS];
+                    n_seg = mdx_kept_md_segments(src + 4, sz - 4u, pl, seg, dst + 4);
+                    for (u32 k = 0; k < n_seg; k++) { sh_at[k][t] = seg[k].at + 4u; sh_len[k][t] = seg[k].len; }
+                    dst[0] = (u8)pl.new_bs; dst[1] = (u8)(pl.new_bs >> 8); dst[2] = (u8)(pl.new_bs >> 16); dst[3] = (u8)(pl.new_bs >> 24);
+                    const u32 kept = sz - 4u - pl.removed;
+                    mdx_kept_md_fields(src + 4, sz - 4u, m, pl, dst + 4 + kept);
+                }
+            } else if (new_sizes[r] == sz) {
+                n_seg = 1; sh_at[0][t] = 0u; sh_len[0][t] = sz;
+            }
+        }
+        sh_n[t] = (u8)n_seg;
+    }
+    __syncthreads();
+    const u32 j = t & 7u, lane = t & 63u;
+    for (u32 round = 0; round < KEPT_TILE / 32u; round++) {
+        const u32 q = round * 32u + (t >> 3), r = r0 + q;       // (q < KEPT_TILE; a record behind the view's last has no stretches)
+        const u32 n_seg = sh_n[q];
+        const u8 *__restrict__ src = n_seg ? in + offsets[r] : in;
+        u8 *__restrict__ dst = n_seg ? out + new_offsets[r] : out;
+        u32 to = n_seg ? sh_at[0][q] : 0u;                      // (the first stretch lands where it came from: byte 0 or 4)
+        for (u32 k = 0; k < MDX_MD_SEGMENTS; k++) {             // (every lane of the wavefront goes through every k: the ballot)
+            const u32 len = k < n_seg ? sh_len[k][q] : 0u, at = k < n_seg ? sh_at[k][q] : 0u;
+            if (len != 0u && len <= (u32)KEPT_WAVE_BYTES) kept_copy<8u>(src + at, dst + to, len, j);
+            unsigned long long big = __ballot(len > (u32)KEPT_WAVE_BYTES && j == 0u);
+            while (big) {
+                const int src_lane = __ffsll((long long)big) - 1;
+                big &= big - 1ull;
+                const u32 qb = (u32)__shfl((int)q, src_lane), tob = (u32)__shfl((int)to, src_lane), rb = r0 + qb;
+                kept_copy<64u>(in + offsets[rb] + sh_at[k][qb], out + new_offsets[rb] + tob, sh_len[k][qb], lane);
+            }
+            to += len;
+        }
+    }
+}
+}  // namespace
+void mdx_k_gbam_kept_md_offsets(const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec, const uint8_t *in, const MdxKeptMask &m,
+                                uint32_t *new_sizes, void *tile_sum, void *tile_base, unsigned long long *new_offsets, unsigned long long *counts,
+                                hipStream_t s) {
+    if (n_rec == 0) return;
+    const uint32_t n_tiles = (n_rec + KEPT_TILE - 1) / KEPT_TILE;
+    hipLaunchKernelGGL(gbam_kept_md_sizes_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, sizes, offsets, n_rec, in, m, new_sizes,
+                       (ulonglong2 *)tile_sum, counts);
+    hipLaunchKernelGGL(gbam_kept_tiles_kernel, dim3(1), dim3(KEPT_SCAN_ROUND), 0, s, (const ulonglong2 *)tile_sum, n_tiles, (ulonglong2 *)tile_base);
+    hipLaunchKernelGGL(gbam_kept_offsets_kernel, dim3(n_tiles), dim3(KEPT_TILE), 0, s, new_sizes, (const ulonglong2 *)tile_base, n_rec, new_offsets);
+}
+void mdx_k_gbam_kept_md_rewrite(const uint32_t *sizes, const unsigned long long *offsets, const uint32_t *new_sizes,
+                                const unsigned long long *new_offsets, uint32_t n_rec, const uint8_t *in, uint8_t *out, const MdxKeptMask &m,
+                                hipStream_t s) {
+    if (n_rec == 0) return;
+    hipLaunchKernelGGL(gbam_kept_md_rewrite_kernel, dim3((n_rec + KEPT_TILE - 1) / KEPT_TILE), dim3(KEPT_TILE), 0, s, sizes, offsets, new_sizes,
+                       new_offsets, n_rec, in, out, m);
+}
+
 int mdx_k_gbam_kept_tile() { return KEPT_TILE; }
 void mdx_k_gbam_kept_offsets(const uint8_t *unc, const uint32_t *rec_off, const uint16_t *flag, const uint16_t *key, const uint8_t *selected,
                              uint32_t n_groups, uint32_t n_rec, uint32_t *sizes, void *tile_sum, void *tile_base, unsigned long long *offsets,

@@ -582,6 +582,17 @@ struct MdxKeptMask;
 void mdx_k_gbam_kept_mask(const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec, uint8_t *out, const MdxKeptMask &m,
                           unsigned long long *counts, hipStream_t s);
 
+// ... with NM and MD of the written records recomputed (--calmd; host side: mdx_gbam_set_kept_md; the rule: mdx_kept_md.h), behind
+// the gather and the mask kernel.  _md_offsets: the new sizes of the records of the stream `in` (sizes, offsets: the kept
+// kernels'), their tile pairs, tile bases with the total behind them and 64-bit offsets, as mdx_k_gbam_kept_offsets leaves them;
+// counts[0..2] += recomputed, skipped, had NM or MD (device).  _md_rewrite: the records of `in` to `out`, which holds the new total.
+void mdx_k_gbam_kept_md_offsets(const uint32_t *sizes, const unsigned long long *offsets, uint32_t n_rec, const uint8_t *in, const MdxKeptMask &m,
+                                uint32_t *new_sizes, void *tile_sum, void *tile_base, unsigned long long *new_offsets, unsigned long long *counts,
+                                hipStream_t s);
+void mdx_k_gbam_kept_md_rewrite(const uint32_t *sizes, const unsigned long long *offsets, const uint32_t *new_sizes,
+                                const unsigned long long *new_offsets, uint32_t n_rec, const uint8_t *in, uint8_t *out, const MdxKeptMask &m,
+                                hipStream_t s);
+
 // ... and the BAI index of that stream (--write-index; host side: mdx_gbam_kept_index; the rule: mdx_kept_index.h).  MdxKeptIndex:
 // the dense list of the slab's written records (n_written entries each); MdxIndexRun: a maximal run of written records with
 // the same (tid, bin) — ranks [first, last) of the list, stream offsets [ustart, uend) — as the caller gets it (include/mdx.h

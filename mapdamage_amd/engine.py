@@ -39,7 +39,8 @@ EXPORTS = (
     "mdx_gbam_view_flags", "mdx_gbam_view_set_flags",
     "mdx_rescale_patches_device", "mdx_tabulate_rescale_patches_device", "mdx_rescale_expand_device", "mdx_mr_round", "mdx_batch_fold", "mdx_bgzf_deflate",
     "mdx_gbam_rescale_slab", "mdx_gbam_write_rescaled", "mdx_gbam_record_name", "mdx_gbam_kept_bound", "mdx_gbam_write_kept",
-    "mdx_gbam_kept_bound_tagged", "mdx_gbam_write_kept_tagged", "mdx_gbam_kept_index", "mdx_gbam_kept_index_linear", "mdx_gbam_set_kept_mask", "mdx_gbam_kept_mask_counts", "mdx_strata_pmd_keep_scores", "mdx_strata_pmd_scores",
+    "mdx_gbam_kept_bound_tagged", "mdx_gbam_write_kept_tagged", "mdx_gbam_kept_index", "mdx_gbam_kept_index_linear", "mdx_gbam_set_kept_mask", "mdx_gbam_kept_mask_counts",
+    "mdx_gbam_set_kept_md", "mdx_gbam_kept_md_counts", "mdx_gbam_kept_bound_md", "mdx_strata_pmd_keep_scores", "mdx_strata_pmd_scores",
     "mdx_fasta_index", "mdx_set_reference_fasta", "mdx_fasta_load_stats", "mdx_reference_fetch", "mdx_host_threads", "mdx_host_pool_threads", "mdx_warm",
     "mdx_source_open", "mdx_source_error", "mdx_source_is_stream", "mdx_source_peek", "mdx_source_read", "mdx_source_close",
     "mdx_bam_read_source", "mdx_bam_open_source", "mdx_gbam_open_source",

@@ -246,6 +246,14 @@ def build_parser():
                         "A in the 3' window of the molecule's own strand (T in both with --single-stranded); or those of them that "
                         "are `mismatches`, with C or G in the reference underneath — which keeps the true T and A, and with them the "
                         "bias towards the reference that `transitions` does not have")
+    g.add_argument("--calmd", action="store_true", default=False,
+                   help="with --write-kept: every written record leaves with NM and MD recomputed against the run's reference, as "
+                        "`samtools calmd` behind the run would — from the bytes the file will hold, so behind --mask-ends and with "
+                        "the tags of --tag-group / --tag-pmd-score in place.  Every NM and MD field a record had is removed, and "
+                        "NM (the smallest unsigned type) and MD:Z follow its other tags; a record the rule cannot follow (a CIGAR "
+                        "that does not fill SEQ, a place outside the reference, tags that cannot be walked, CG:B) is written as it "
+                        "is.  An ambiguity code of the reference appears in MD as N.  calmd.tsv gives the records recomputed and "
+                        "skipped.  Not a reference option")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -311,7 +319,8 @@ def parse_mask_ends(text):
 
 
 def _check_write_kept(parser, o):
-    """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score / --write-index / --mask-ends."""
+    """The argument errors of --write-kept / --write-groups / --tag-group / --tag-pmd-score / --write-index / --mask-ends /
+    --calmd."""
     if o.mask_what is not None and o.mask_ends is None:
         parser.error("--mask-what needs --mask-ends: it says what the windows of that option select")
     if o.mask_ends is not None:
@@ -322,6 +331,12 @@ def _check_write_kept(parser, o):
         except ValueError as error:
             parser.error("--mask-ends: %s" % error)
         o.mask_what = o.mask_what or "all"
+    if getattr(o, "calmd", False):
+        if o.write_kept is None:
+            parser.error("--calmd needs --write-kept: it recomputes NM and MD of the records that file receives")
+        for option, tag in (("--tag-group", o.tag_group), ("--tag-pmd-score", o.tag_pmd_score)):
+            if tag in ("NM", "MD"):
+                parser.error("%s %s with --calmd: NM and MD are the two tags that option replaces" % (option, tag))
     if o.write_groups is not None:
         if o.write_kept is None:
             parser.error("--write-groups needs --write-kept: it chooses the groups whose records that file receives")
@@ -836,6 +851,10 @@ class _KeptOutput:
         if self.mask is not None:
             self.mask_what, self.mask_single = options.mask_what, bool(options.single_stranded)
             stream.set_kept_mask(self.mask[0], self.mask[1], self.mask_what, self.mask_single)
+        # (--calmd: NM and MD of every slab it writes from here on recomputed, and counted)
+        self.calmd = bool(getattr(options, "calmd", False))
+        if self.calmd:
+            stream.set_kept_md(True)
         self.writer = BgzfWriter(self.tmp, engine=engine)
         try:
             self.writer.write(bam_header_bytes(stream.header))
@@ -860,6 +879,7 @@ class _KeptOutput:
     def commit(self, logger):
         index = None
         masked = self.stream.kept_mask_counts() if self.mask is not None else None
+        recomputed = self.stream.kept_md_counts() if self.calmd else None
         if self.index is not None:
             index = self.index.finish(self.stream.kept_index_linear())
             self.index_tmp.write_bytes(index)
@@ -880,6 +900,10 @@ class _KeptOutput:
             (self.folder / "mask_ends.tsv").write_text("path\tk5\tk3\twhat\tsingle_stranded\trecords\tbases\n%s\t%d\t%d\t%s\t%d\t%d\t%d\n"
                                                        % (self.path, self.mask[0], self.mask[1], self.mask_what, int(self.mask_single),
                                                           masked[0], masked[1]))
+        if recomputed is not None:
+            logger.info("Recomputed NM and MD of %d of %d written records (%d left as they are)", recomputed[0], self.records, recomputed[1])
+            (self.folder / "calmd.tsv").write_text("path\trecords\trecomputed\tskipped\thad_tags\n%s\t%d\t%d\t%d\t%d\n"
+                                                   % (self.path, self.records, recomputed[0], recomputed[1], recomputed[2]))
         if index is not None:
             logger.info("Wrote index %s (%d references with records, %d chunks)", self.index_path, self.index.n_references, self.index.n_chunks)
 

@@ -724,14 +724,19 @@ class GpuBamStream:
             raise ValueError("%r: %s" % (str(self.path), self._error()))
         return out[:out_len.value]
 
-    def kept_bound(self, group_tag=None, score_tag=None):
+    def kept_bound(self, group_tag=None, score_tag=None, calmd=None):
         """Bytes that always suffice for the members ``write_kept`` makes of the view handed out last (include/mdx.h
         ``mdx_gbam_kept_bound``: from the view's record offsets, never a guess) — with the tags' 5 and 7 bytes for every record
-        of the view where they are asked for (``mdx_gbam_kept_bound_tagged``)."""
+        of the view where they are asked for (``mdx_gbam_kept_bound_tagged``), and with what recomputing NM and MD can add
+        (``mdx_gbam_kept_bound_md``) where ``calmd`` is true; ``None``: as ``set_kept_md`` left the stream."""
         import ctypes
         tag_bytes = (5 if group_tag is not None else 0) + (7 if score_tag is not None else 0)
         bound = ctypes.c_int64(0)
-        if tag_bytes:
+        if getattr(self, "_kept_md", False) if calmd is None else calmd:
+            fn = self._lib.mdx_gbam_kept_bound_md
+            fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int
+            rc = fn(self._g, ctypes.c_int32(tag_bytes), ctypes.c_int32(1), ctypes.byref(bound))
+        elif tag_bytes:
             fn = self._lib.mdx_gbam_kept_bound_tagged
             fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int
             rc = fn(self._g, ctypes.c_int32(tag_bytes), ctypes.byref(bound))
@@ -828,6 +833,35 @@ class GpuBamStream:
             from .engine import MdxError
             raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
         return int(records.value), int(bases.value)
+
+    def set_kept_md(self, on=True):
+        """Every later ``write_kept`` of this stream hands its records on with ``NM`` and ``MD`` recomputed against the
+        engine's reference (include/mdx.h ``mdx_gbam_set_kept_md``; the rule: csrc/mdx_kept_md.h) — from the bytes the file will
+        hold, so behind ``set_kept_mask`` and with the tags of ``write_kept`` in place; ``raw_bytes`` and ``kept_index`` are
+        those of the new records.  ``on=False`` switches it off.  Either way the counts start again at 0.  A write on an
+        engine without a reference is ``MdxError`` -3."""
+        import ctypes
+        fn = self._lib.mdx_gbam_set_kept_md
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32], ctypes.c_int
+        rc = fn(self._g, ctypes.c_int32(1 if on else 0))
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        self._kept_md = bool(on)
+
+    def kept_md_counts(self):
+        """``(recomputed, skipped, had_tags)``: the written records whose ``NM`` and ``MD`` were recomputed, those left as they
+        are, and those that had either tag, summed over the ``write_kept`` calls since ``set_kept_md``
+        (``mdx_gbam_kept_md_counts``)."""
+        import ctypes
+        fn = self._lib.mdx_gbam_kept_md_counts
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_void_p], ctypes.c_int
+        out = (ctypes.c_uint64 * 3)()
+        rc = fn(self._g, out)
+        if rc != 0:
+            from .engine import MdxError
+            raise MdxError(rc, "%r: %s" % (str(self.path), self._error()))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def kept_index(self, stream_base, prev, n_written):
         """The index entries of the records the last ``write_kept`` of this view wrote (include/mdx.h ``mdx_gbam_kept_index``;

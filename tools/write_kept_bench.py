@@ -12,17 +12,22 @@ one BAM, then three commands timed as cold processes, each under a time limit of
   kept_index  `--write-kept kept_index.bam --write-index`                                                ... and its BAI index
   --mask-ends K5[,K3] instead: the legs plain, kept, and one per --mask-what,
   mask_all, mask_transitions, mask_mismatches  `--write-kept mask_X.bam --mask-ends K5,K3 --mask-what X`   ... handed on masked
+  --calmd instead: the legs plain, kept, and
+  calmd       `--write-kept calmd.bam --calmd`                                                           ... NM and MD recomputed
+  mask_calmd  `--write-kept mask_calmd.bam --mask-ends 2,2 --calmd`                                      ... behind the mask
 
 The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
 times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
 (write_kept.tsv) and the file's size.  kept - plain and pmd - plain (medians) are the feature's cost, pmd_tagged - pmd_all that
 of the tags (12 bytes a record, the score column, the walk over every written record's tags), kept_index - kept that of the
 index (four launches and two small copies per slab, the file's assembly on the host), mask_X - kept that of the mask (one
-launch per slab, in place in the stream; mask_ends.tsv gives the records and bases it masked).  --parent-root DIR: a
-built checkout of the parent commit; `plain` is then also timed there, in the same alternation — a difference between the two
-beyond the spread means the option-less path has changed.  One JSON line on stdout.
+launch per slab, in place in the stream; mask_ends.tsv gives the records and bases it masked), calmd - kept that of the
+recomputed tags (five launches and sixteen bytes back per slab, a second stream; calmd.tsv gives the records recomputed and
+skipped).  --parent-root DIR: a built checkout of the parent commit; `plain` is then also timed there — with --calmd `kept` as
+well —, in the same alternation: a difference between the two beyond the spread means the option-less path has changed.
+One JSON line on stdout.
 
-    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index | --mask-ends K]"""
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index | --mask-ends K | --calmd]"""
 import argparse
 import json
 import os
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--tags", action="store_true", help="also time --by-pmd-score --write-kept with and without --tag-group / --tag-pmd-score")
     ap.add_argument("--index", action="store_true", help="coordinate-sorted records; time --write-kept with and without --write-index")
     ap.add_argument("--mask-ends", metavar="K5[,K3]", help="time --write-kept with and without --mask-ends K5[,K3], for each --mask-what")
+    ap.add_argument("--calmd", action="store_true", help="time --write-kept with and without --calmd, and with --mask-ends 2,2 --calmd")
     args = ap.parse_args()
     import numpy as np
 
@@ -89,12 +95,17 @@ def main():
         if args.mask_ends:
             legs = legs[:2] + [("mask_" + what, ROOT, ["--write-kept", os.path.join(work, "mask_%s.bam" % what), "--mask-ends", args.mask_ends,
                                                        "--mask-what", what]) for what in ("all", "transitions", "mismatches")]
+        if args.calmd:
+            legs = legs[:2] + [("calmd", ROOT, ["--write-kept", os.path.join(work, "calmd.bam"), "--calmd"]),
+                               ("mask_calmd", ROOT, ["--write-kept", os.path.join(work, "mask_calmd.bam"), "--mask-ends", "2,2", "--calmd"])]
         if args.tags:
             pmd_all = ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept"]
             legs += [("pmd_all", ROOT, pmd_all + [os.path.join(work, "pmd_all.bam")]),
                      ("pmd_tagged", ROOT, pmd_all + [os.path.join(work, "pmd_tagged.bam"), "--tag-group", "XG", "--tag-pmd-score", "DS"])]
         if args.parent_root:
             legs.insert(1, ("parent_plain", os.path.abspath(args.parent_root), []))
+            if args.calmd:
+                legs.insert(3, ("parent_kept", os.path.abspath(args.parent_root), ["--write-kept", os.path.join(work, "parent_kept.bam")]))
         times = {name: [] for name, _, _ in legs}
         status = 0
         for _ in range(args.repeats):
@@ -120,7 +131,7 @@ def main():
                 path, groups, records, raw = open(tsv).read().splitlines()[1].split("\t")
                 result[name].update(groups=groups, records_written=int(records), uncompressed_bytes=int(raw), file_bytes=os.path.getsize(path))
         if status == 0:
-            for name in ("kept",) if args.index or args.mask_ends else ("kept", "pmd"):
+            for name in ("kept",) if args.index or args.mask_ends or args.calmd else ("kept", "pmd"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
             if args.index:
                 result["kept_index_minus_kept_s"] = round(result["kept_index"]["median_s"] - result["kept"]["median_s"], 3)
@@ -139,6 +150,18 @@ def main():
                     leg.update(masked_records=int(row[5]), masked_bases=int(row[6]))
                     if (leg["records_written"], leg["uncompressed_bytes"]) != (result["kept"]["records_written"], result["kept"]["uncompressed_bytes"]):
                         result["error"] = "mask_%s.bam does not hold kept.bam's records and bytes" % what
+            if args.calmd:
+                for name in ("calmd", "mask_calmd"):
+                    leg = result[name]
+                    result["%s_minus_kept_s" % name] = round(leg["median_s"] - result["kept"]["median_s"], 3)
+                    row = open(os.path.join(work, name, "calmd.tsv")).read().splitlines()[1].split("\t")
+                    leg.update(recomputed=int(row[2]), skipped=int(row[3]), had_tags=int(row[4]))
+                    if leg["records_written"] != result["kept"]["records_written"] or leg["recomputed"] + leg["skipped"] != leg["records_written"]:
+                        result["error"] = "%s.bam does not hold kept.bam's records, or calmd.tsv does not add up" % name
+                if args.parent_root:
+                    result["kept_minus_parent_kept_s"] = round(result["kept"]["median_s"] - result["parent_kept"]["median_s"], 3)
+                    if open(os.path.join(work, "kept.bam"), "rb").read() != open(os.path.join(work, "parent_kept.bam"), "rb").read():
+                        result["error"] = "kept.bam differs from the parent's"
             if args.tags:
                 result["pmd_tagged_minus_pmd_all_s"] = round(result["pmd_tagged"]["median_s"] - result["pmd_all"]["median_s"], 3)
                 extra = result["pmd_tagged"]["uncompressed_bytes"] - result["pmd_all"]["uncompressed_bytes"]
