@@ -377,6 +377,47 @@ int mdx_finish_merged(mdx_ctx *ctx, const uint64_t *d_tables, uint64_t *d_merged
 int mdx_finish_merged_host(mdx_ctx *ctx, uint64_t *merged);
 int mdx_lgd_copies(const mdx_ctx *ctx);
 
+/* ---- Duplicate removal: later copies of a molecule get 0x400 in the flag column before the batch is counted, and the flag
+ * filter (0xF04) of every launch, count and written file drops them.
+ *
+ * A record is EXAMINED if (FLAG & 0xF04) == 0 on the column as it stands, its library is below the context's libraries (on a
+ * stratified context: cfg.nlib / n_groups — the batch's lib column, not the key), FLAG & 0x1 is clear, tid >= 0, pos >= 0 and
+ * its CIGAR consumes a reference base.  Its ends are the unclipped ones: left = pos - the leading run of S and H, right = pos +
+ * the reference span - 1 + the trailing run of S and H; a left below -2^31 or a right above 2^32 - 1 leaves the record
+ * unexamined.  Two examined records are copies of one molecule if they agree in (library, tid, FLAG & 0x10, left, right)
+ * (ends = 0, both) or in (library, tid, FLAG & 0x10, the 5' coordinate: left forwards, right on the reverse strand) (ends = 1);
+ * nothing else is compared, and nothing is hashed in place of a field.  The first in the order of the marked batches' records
+ * represents the molecule, every later one is marked — whatever the batches' sizes, the lanes' schedule or the table's size.
+ *
+ *   mdx_dedup_begin    after mdx_create, before the first mdx_dedup_mark: the set of signatures in HBM — 16 bytes per examined
+ *                      record in a store that grows, and a table of 64-bit slots with a 32-bit count each, at most half full,
+ *                      doubled (a rehash launch on the stream, no readback) when the records marked so far and the coming
+ *                      batch's could pass that.  expected_records sizes the first table (0: a small one).  A second call
+ *                      empties the set and takes the new `ends`.
+ *   mdx_dedup_mark     enqueued on the context's stream: the batch's flag column — device memory the caller grants as
+ *                      writable — gets 0x400 where the record is a later copy.  The batches marked are consecutive stretches
+ *                      of one stream of records.  MDX_ERR_STATE without mdx_dedup_begin.
+ *   mdx_dedup_counts   synchronous: per library the records examined, marked, left unexamined because paired, and left
+ *                      unexamined for another reason (no position, no reference base, ends beyond their fields).  Records
+ *                      the flag filter drops or whose library the context does not know are in none of them.
+ *   mdx_dedup_histogram  synchronous: per library the molecules seen c times, bin c - 1 for c = 1..1023, bin 1023 for c >= 1024.
+ *   mdx_dedup_info     synchronous: info[0] slots of the table, [1] times it has grown, [2] the longest walk of an insert (slots
+ *                      looked at), [3] all walks summed, [4] the store's entries (the examined records), [5] bytes of HBM the
+ *                      store and the table hold, [6] the records (or slots) a block of the stage's kernels takes, [7] the
+ *                      records a round of its one-block prefix sum takes (tests: the sizes at which the kernels turn).
+ * mdx_reset empties the set and the counters (the setting stays), mdx_destroy frees them.  MDX_TEST_DUP_SLOTS=<n> in the
+ * environment: the first table's slots, for tests of growth and long walks.
+ *
+ * Limits: a batch of fewer than 2^30 records, as everywhere, and at most 2^30 records marked between mdx_dedup_begin (or
+ * mdx_reset) and the end of the stream, whether examined or not: the table is sized by the records marked, never more than
+ * half full, and has at most 2^31 slots (a record keeps its slot's index in 32 bits).  The mdx_dedup_mark that would pass
+ * either returns MDX_ERR_ARG and marks nothing; the batches before it stand. */
+int mdx_dedup_begin(mdx_ctx *ctx, int32_t ends, int64_t expected_records);
+int mdx_dedup_mark(mdx_ctx *ctx, mdx_batch *device_batch);
+int mdx_dedup_counts(mdx_ctx *ctx, uint64_t *out /* [n_libraries][4] */);
+int mdx_dedup_histogram(mdx_ctx *ctx, uint64_t *out /* [n_libraries][1024] */);
+int mdx_dedup_info(mdx_ctx *ctx, uint64_t *info /* [8] */);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

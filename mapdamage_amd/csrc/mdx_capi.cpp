@@ -184,6 +184,22 @@ struct mdx_ctx {
         DevBuf pmd_scores;
         uint64_t pmd_scores_serial = 0;
     } strata;
+    // duplicate removal (mdx_dedup_begin): the set of signatures the marked batches have brought — store and table —, the
+    // counters, and the scratch columns of one mdx_dedup_mark.  Nothing of it exists before mdx_dedup_begin.
+    struct Dedup {
+        bool on = false;
+        int ends = 0;
+        MdxDupSig *store = nullptr;
+        uint64_t store_cap = 0;                // entries
+        MdxDupTable table = {nullptr, nullptr, 0};
+        uint64_t n_slots = 0;                  // a power of two
+        unsigned long long *state = nullptr;   // [4] (MdxDedupArgs::state)
+        unsigned long long *counters = nullptr;    // [cfg.nlib][4]
+        uint64_t marked = 0;                   // records of the batches marked so far: no fewer than the store's entries, known without a readback
+        uint64_t growths = 0;
+        std::vector<void *> retired;           // the store and the tables that were outgrown: freed where the stream is idle anyway
+        DevBuf tmp, tile, rank, slot_of;
+    } dedup;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -260,6 +276,56 @@ Key key_args(const mdx_ctx *c, const mdx_batch *b) {
     return k;
 }
 
+
+// ---- duplicate removal: the context's side (the launches: mdx_dedup.hip)
+int dedup_libraries(const mdx_ctx *c) { return c->cfg.nlib / (c->strata.n_groups > 0 ? c->strata.n_groups : 1); }
+
+void dedup_free_retired(mdx_ctx *c) {
+    for (void *p : c->dedup.retired) (void)hipFree(p);
+    c->dedup.retired.clear();
+}
+
+void dedup_release(mdx_ctx *c) {
+    auto &d = c->dedup;
+    dedup_free_retired(c);
+    void *ptrs[] = {d.store, d.table.slots, d.table.counts, d.state, d.counters};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    d.tmp.release(); d.tile.release(); d.rank.release(); d.slot_of.release();
+    d = mdx_ctx::Dedup{};
+}
+
+// an empty table of n_slots slots (a power of two), emptied on the stream
+int dedup_new_table(mdx_ctx *c, uint64_t n_slots, MdxDupTable *t) {
+    t->slots = nullptr; t->counts = nullptr; t->mask = n_slots - 1;
+    HIP_TRY(c, hipMalloc((void **)&t->slots, (size_t)n_slots * 8));
+    if (hipMalloc((void **)&t->counts, (size_t)n_slots * 4) != hipSuccess) {
+        (void)hipFree(t->slots);
+        t->slots = nullptr;
+        return fail(c, MDX_ERR_HIP, "mdx_dedup: out of device memory for a table of " + std::to_string(n_slots) + " slots");
+    }
+    hipError_t e = hipMemsetAsync(t->slots, 0xFF, (size_t)n_slots * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(t->counts, 0, (size_t)n_slots * 4, c->stream);
+    if (e != hipSuccess) {
+        // (nothing knows the table yet: freed here; hipFree waits for a fill that was enqueued)
+        (void)hipFree(t->slots); (void)hipFree(t->counts);
+        t->slots = nullptr; t->counts = nullptr;
+        return fail(c, MDX_ERR_HIP, std::string("mdx_dedup: emptying a new table: ") + hipGetErrorString(e));
+    }
+    return MDX_OK;
+}
+
+// the set and the counters emptied (enqueued); table and store keep their sizes
+int dedup_clear(mdx_ctx *c) {
+    auto &d = c->dedup;
+    HIP_TRY(c, hipMemsetAsync(d.table.slots, 0xFF, (size_t)d.n_slots * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.table.counts, 0, (size_t)d.n_slots * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.state, 0, 4 * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.counters, 0, (size_t)c->cfg.nlib * 4 * 8, c->stream));
+    d.marked = 0; d.growths = 0;
+    return MDX_OK;
+}
+
+#define MDX_DEDUP_MAX_SLOTS ((uint64_t)1 << 31)    // a slot's index is kept in 32 bits per record of the batch
 }  // namespace
 
 extern "C" {
@@ -411,6 +477,7 @@ void mdx_destroy(mdx_ctx *c) {
     if (c->gbam_tables) (void)hipFree(c->gbam_tables);
     if (c->gbam_stream) (void)hipStreamDestroy((hipStream_t)c->gbam_stream);
     if (c->gbam_event) (void)hipEventDestroy((hipEvent_t)c->gbam_event);
+    dedup_release(c);
     c->lists.release();
     c->unpacked.release();
     c->lowq.release();
@@ -1350,9 +1417,145 @@ int mdx_reset(mdx_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     int rc = zero_accumulators(c);
     if (rc != MDX_OK) return rc;
+    if (c->dedup.on && (rc = dedup_clear(c)) != MDX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dedup_free_retired(c);
     c->err.clear();
     c->counted = false;
+    return MDX_OK;
+}
+
+int mdx_dedup_begin(mdx_ctx *c, int32_t ends, int64_t expected_records) {
+    if (!c) return MDX_ERR_ARG;
+    if ((ends != MDX_DUP_ENDS_BOTH && ends != MDX_DUP_ENDS_5P) || expected_records < 0)
+        return fail(c, MDX_ERR_ARG, "mdx_dedup_begin: ends is 0 (both) or 1 (5p), expected_records not negative");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dedup_release(c);
+    auto &d = c->dedup;
+    uint64_t want = 2 * (uint64_t)expected_records < ((uint64_t)1 << 16) ? (uint64_t)1 << 16 : 2 * (uint64_t)expected_records;
+    // (tests: growth and long walks out of a few thousand records)
+    if (const char *e = getenv("MDX_TEST_DUP_SLOTS"); e && *e) want = strtoull(e, nullptr, 10) < 2 ? 2 : strtoull(e, nullptr, 10);
+    if (want > MDX_DEDUP_MAX_SLOTS) want = MDX_DEDUP_MAX_SLOTS;
+    uint64_t n_slots = 2;
+    while (n_slots < want) n_slots <<= 1;
+    if (const int rc = dedup_new_table(c, n_slots, &d.table); rc != MDX_OK) return rc;
+    d.n_slots = n_slots;
+    d.store_cap = n_slots / 2;
+    HIP_TRY(c, hipMalloc((void **)&d.store, (size_t)d.store_cap * sizeof(MdxDupSig)));
+    HIP_TRY(c, hipMalloc((void **)&d.state, 4 * 8));
+    HIP_TRY(c, hipMalloc((void **)&d.counters, (size_t)c->cfg.nlib * 4 * 8));
+    HIP_TRY(c, hipMemsetAsync(d.state, 0, 4 * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.counters, 0, (size_t)c->cfg.nlib * 4 * 8, c->stream));
+    d.ends = ends;
+    d.on = true;
+    return MDX_OK;
+}
+
+int mdx_dedup_mark(mdx_ctx *c, mdx_batch *b) {
+    if (const int rc = check_batch(c, b); rc != MDX_OK) return rc;
+    auto &d = c->dedup;
+    if (!d.on) return fail(c, MDX_ERR_STATE, "mdx_dedup_mark: call mdx_dedup_begin first");
+    if (b->n_reads == 0) return MDX_OK;
+    if (b->n_reads >= ((int64_t)1 << 30)) return fail(c, MDX_ERR_ARG, "mdx_dedup_mark: a batch holds fewer than 2^30 records");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const uint64_t n = (uint64_t)b->n_reads, need = d.marked + n;
+    // the table never more than half full, whatever the batch turns out to hold: grown before the launch, on the stream
+    if (2 * need > d.n_slots) {
+        uint64_t n_slots = d.n_slots * 2;
+        while (n_slots < 2 * need) n_slots <<= 1;
+        if (n_slots > MDX_DEDUP_MAX_SLOTS)
+            return fail(c, MDX_ERR_ARG, "mdx_dedup_mark: more than 2^30 records; the table of signatures has at most 2^31 slots");
+        MdxDupTable grown;
+        if (const int rc = dedup_new_table(c, n_slots, &grown); rc != MDX_OK) return rc;
+        mdx_k_dedup_rehash(d.table, d.n_slots, grown, d.store, c->stream);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+            (void)hipFree(grown.slots); (void)hipFree(grown.counts);
+            return fail(c, MDX_ERR_HIP, std::string("mdx_dedup_mark: the rehash launch: ") + hipGetErrorString(e));
+        }
+        d.retired.push_back(d.table.slots);
+        d.retired.push_back(d.table.counts);
+        d.table = grown;
+        d.n_slots = n_slots;
+        d.growths++;
+    }
+    if (need > d.store_cap) {
+        const uint64_t cap = need > 2 * d.store_cap ? need : 2 * d.store_cap;
+        MdxDupSig *grown = nullptr;
+        HIP_TRY(c, hipMalloc((void **)&grown, (size_t)cap * sizeof(MdxDupSig)));
+        const uint64_t have = d.marked < d.store_cap ? d.marked : d.store_cap;
+        if (have && hipMemcpyAsync(grown, d.store, (size_t)have * sizeof(MdxDupSig), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) {
+            (void)hipFree(grown);
+            return fail(c, MDX_ERR_HIP, "mdx_dedup_mark: copy of the signature store failed");
+        }
+        d.retired.push_back(d.store);
+        d.store = grown;
+        d.store_cap = cap;
+    }
+    const uint64_t blocks = (n + (uint64_t)mdx_k_dedup_block() - 1) / (uint64_t)mdx_k_dedup_block();
+    HIP_TRY(c, d.tmp.reserve((size_t)n * sizeof(MdxDupSig)));
+    HIP_TRY(c, d.tile.reserve((size_t)blocks * 4));
+    HIP_TRY(c, d.rank.reserve((size_t)n * 4));
+    HIP_TRY(c, d.slot_of.reserve((size_t)n * 4));
+    MdxDupKey k{};
+    k.n = b->n_reads; k.n_cigar = b->n_cigar;
+    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos; k.cigar_off = b->cigar_off; k.cigar = b->cigar;
+    k.n_libraries = dedup_libraries(c); k.ends = d.ends;
+    MdxDedupArgs a{};
+    a.tmp = (MdxDupSig *)d.tmp.p; a.tile = (uint32_t *)d.tile.p; a.rank = (uint32_t *)d.rank.p; a.slot_of = (uint32_t *)d.slot_of.p;
+    a.store = d.store; a.store_cap = d.store_cap; a.table = d.table; a.state = d.state; a.counters = d.counters;
+    // (the flag column: the caller grants it as writable)
+    mdx_k_dedup_mark(k, const_cast<uint16_t *>(b->flag), a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    d.marked = need;
+    return MDX_OK;
+}
+
+static int dedup_idle(mdx_ctx *c, const char *who) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->dedup.on) return fail(c, MDX_ERR_STATE, std::string(who) + ": call mdx_dedup_begin first");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    dedup_free_retired(c);
+    return MDX_OK;
+}
+
+int mdx_dedup_counts(mdx_ctx *c, uint64_t *out) {
+    if (const int rc = dedup_idle(c, "mdx_dedup_counts"); rc != MDX_OK) return rc;
+    if (!out) return fail(c, MDX_ERR_ARG, "mdx_dedup_counts: null output");
+    HIP_TRY(c, hipMemcpy(out, c->dedup.counters, (size_t)dedup_libraries(c) * 4 * 8, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_dedup_histogram(mdx_ctx *c, uint64_t *out) {
+    if (const int rc = dedup_idle(c, "mdx_dedup_histogram"); rc != MDX_OK) return rc;
+    if (!out) return fail(c, MDX_ERR_ARG, "mdx_dedup_histogram: null output");
+    auto &d = c->dedup;
+    const int n_libraries = dedup_libraries(c);
+    const size_t bytes = (size_t)n_libraries * MDX_DUP_HIST_BINS * 8;
+    unsigned long long *hist = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&hist, bytes));
+    hipError_t e = hipMemsetAsync(hist, 0, bytes, c->stream);
+    if (e == hipSuccess) {
+        mdx_k_dedup_histogram(d.table, d.n_slots, d.store, n_libraries, hist, c->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, hist, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(hist);
+    if (e != hipSuccess) return fail(c, MDX_ERR_HIP, std::string("mdx_dedup_histogram: ") + hipGetErrorString(e));
+    return MDX_OK;
+}
+
+int mdx_dedup_info(mdx_ctx *c, uint64_t *info) {
+    if (const int rc = dedup_idle(c, "mdx_dedup_info"); rc != MDX_OK) return rc;
+    if (!info) return fail(c, MDX_ERR_ARG, "mdx_dedup_info: null output");
+    const auto &d = c->dedup;
+    unsigned long long state[4] = {0, 0, 0, 0};
+    HIP_TRY(c, hipMemcpy(state, d.state, sizeof state, hipMemcpyDeviceToHost));
+    info[0] = d.n_slots; info[1] = d.growths; info[2] = state[3]; info[3] = state[2]; info[4] = state[0] + state[1];
+    info[5] = d.store_cap * sizeof(MdxDupSig) + d.n_slots * 12;
+    info[6] = (uint64_t)mdx_k_dedup_block(); info[7] = (uint64_t)mdx_k_dedup_scan_records();
     return MDX_OK;
 }
 

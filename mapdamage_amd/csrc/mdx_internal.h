@@ -483,6 +483,25 @@ extern "C" int mdx_ctx_reference(const mdx_ctx *c, const uint8_t **ref, const in
 extern "C" void mdx_ctx_scratch_give(mdx_ctx *c, void *arena, size_t cap, void *tables, void *stream, void *event);
 extern "C" void mdx_ctx_scratch_take(mdx_ctx *c, void **arena, size_t *cap, void **tables, void **stream, void **event);
 
+// ---- duplicate removal (mdx_dedup.hip, where the launches are told; the rule: mdx_dup_key.h, the set: mdx_dup_table.h)
+#include "mdx_dup_table.h"
+struct MdxDedupArgs {
+    MdxDupSig *tmp;                 // [n] the batch's signatures (a = MDX_DT_EMPTY: not examined)
+    uint32_t *tile;                 // [blocks] the examined records of a block, then those in front of it
+    uint32_t *rank;                 // [n] a record's rank among the batch's examined ones (0xFFFFFFFF: not examined)
+    uint32_t *slot_of;              // [n] by rank: the slot the record went to
+    MdxDupSig *store;
+    uint64_t store_cap;             // entries: nothing is written or read beyond
+    MdxDupTable table;
+    unsigned long long *state;      // [4]: store entries in front of the batch, the batch's examined records, slots looked at, longest walk
+    unsigned long long *counters;   // [libraries][4]: examined, duplicates, paired, other
+};
+int mdx_k_dedup_block();            // records (or slots) a block of the stage's kernels takes: all but the scan
+int64_t mdx_k_dedup_scan_records(); // records a round of the scan's one block takes: the counts of 1024 such blocks, a lane each
+void mdx_k_dedup_mark(const MdxDupKey &k, uint16_t *flag, const MdxDedupArgs &a, hipStream_t s);
+void mdx_k_dedup_rehash(const MdxDupTable &from, uint64_t n_slots, const MdxDupTable &to, const MdxDupSig *store, hipStream_t s);
+void mdx_k_dedup_histogram(const MdxDupTable &t, uint64_t n_slots, const MdxDupSig *store, int n_libraries, unsigned long long *hist, hipStream_t s);
+
 // ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
 #include "mdx_filter.h"
 

@@ -53,6 +53,7 @@ EXPORTS = (
     "mdx_stats_loglik", "mdx_stats_run", "mdx_stats_pmat",
     "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
     "mdx_gsam_filter_counts",
+    "mdx_dedup_begin", "mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -207,6 +208,9 @@ def load_library(path=None):
     lib.mdx_finish_merged.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_finish_merged_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_lgd_copies.argtypes = [ctypes.c_void_p]
+    lib.mdx_dedup_begin.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]
+    for name in ("mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info"):
+        getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -453,6 +457,46 @@ class DamageEngine:
     def lgd_copies(self):
         """Copies of the dense fragment-length histogram this context keeps (``mdx_lgd_copies``; tests)."""
         return int(self._lib.mdx_lgd_copies(self._ctx))
+
+    # ------------------------------------------------------------------ duplicate removal
+    DUPLICATE_ENDS = ("both", "5p")
+    DUPLICATE_BINS = 1024
+
+    def _base_library_count(self):
+        return len(self.libraries) // max(1, int(self._lib.mdx_strata_groups(self._ctx)))
+
+    def dedup_begin(self, ends="both", expected_records=0):
+        """From here on ``dedup_mark`` knows the records it has seen (include/mdx.h ``mdx_dedup_begin``): ``ends`` "both" — a
+        molecule is (library, sequence, strand, both unclipped ends) — or "5p" — ... the 5' end alone."""
+        if ends not in self.DUPLICATE_ENDS:
+            raise ValueError("dedup_begin: ends is one of %s" % ", ".join(self.DUPLICATE_ENDS))
+        self._check(self._lib.mdx_dedup_begin(self._ctx, ctypes.c_int32(self.DUPLICATE_ENDS.index(ends)), ctypes.c_int64(int(expected_records))))
+
+    def dedup_mark(self, view):
+        """0x400 into the flag column of a device batch (an ``MdxBatch`` of device pointers, or a ``DeviceBatch``) where the
+        record is a later copy of a molecule seen before, in this batch or an earlier one (``mdx_dedup_mark``): enqueued."""
+        dev = view.dev if isinstance(view, DeviceBatch) else view
+        self._check(self._lib.mdx_dedup_mark(self._ctx, ctypes.byref(dev)))
+
+    def dedup_counts(self):
+        """uint64 [base libraries][4]: examined, duplicates, not examined because paired, not examined otherwise (``mdx_dedup_counts``)."""
+        out = np.zeros((self._base_library_count(), 4), np.uint64)
+        self._check(self._lib.mdx_dedup_counts(self._ctx, _ptr(out)))
+        return out
+
+    def dedup_histogram(self):
+        """uint64 [base libraries][1024]: molecules seen ``c`` times in column ``c - 1``, the last column ``c >= 1024`` (``mdx_dedup_histogram``)."""
+        out = np.zeros((self._base_library_count(), self.DUPLICATE_BINS), np.uint64)
+        self._check(self._lib.mdx_dedup_histogram(self._ctx, _ptr(out)))
+        return out
+
+    def dedup_info(self):
+        """The set's table (``mdx_dedup_info``): slots, growths, longest and summed walk of an insert, examined records, bytes of HBM,
+        the records a block of the stage's kernels takes and those a round of its one-block prefix sum takes."""
+        out = np.zeros(8, np.uint64)
+        self._check(self._lib.mdx_dedup_info(self._ctx, _ptr(out)))
+        return dict(zip(("slots", "growths", "longest_probe", "probes", "examined", "bytes", "block_records", "scan_records"),
+                        (int(x) for x in out)))
 
     def set_reference(self, ref):
         """``ref``: a ``Reference`` (contigs in host memory) or a ``fasta.FastaOnDisk`` — the FASTA file itself, which the

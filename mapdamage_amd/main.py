@@ -254,6 +254,21 @@ def build_parser():
                         "that does not fill SEQ, a place outside the reference, tags that cannot be walked, CG:B) is written as it "
                         "is.  An ambiguity code of the reference appears in MD as N.  calmd.tsv gives the records recomputed and "
                         "skipped.  Not a reference option")
+    g.add_argument("--remove-duplicates", action="store_true", default=False,
+                   help="drop the later copies of a molecule before anything is counted, in the same pass: among the unpaired "
+                        "records the flag filter, the record filters and --downsample to a fraction leave, those of one library "
+                        "that share sequence, strand and both unclipped ends (the leading and trailing S and H operations counted "
+                        "in, as DeDup, `rmdup_collapsed` and `samtools markdup` take the ends) are one molecule; the first in the "
+                        "input's order is counted, every later one gets flag 0x400 on the device, which the flag filter 0xF04 "
+                        "drops from the tables, every kind of groups and the file of --write-kept.  Exact — the fields are "
+                        "compared, not a hash of them — and the same whatever the slabs.  Paired records are not examined.  "
+                        "duplicates.tsv and duplicates_histogram.tsv give the counts per library.  BAM input on the device decode "
+                        "path only: not SAM text, --host-decode, --gpus above 1 or -n N; at most 2^30 records in the input.  Not "
+                        "a reference option")
+    g.add_argument("--duplicate-ends", choices=DUPLICATE_ENDS, default=None,
+                   help="with --remove-duplicates: `both` ends of the molecule (the default: merged reads, whose two ends are the "
+                        "molecule's), or the `5p` end alone — the unclipped start of a forward record, the unclipped end of a "
+                        "reverse one —, as `samtools rmdup -s` does for single-end reads whose 3' end is where sequencing stopped")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -384,6 +399,28 @@ def _check_write_kept(parser, o):
             parser.error("--write-kept %s is the input file: the run would overwrite what it reads" % o.write_kept)
 
 
+DUPLICATE_ENDS = ("both", "5p")
+
+
+def _check_remove_duplicates(parser, o):
+    """The argument errors of --remove-duplicates / --duplicate-ends."""
+    if o.duplicate_ends is not None and not o.remove_duplicates:
+        parser.error("--duplicate-ends needs --remove-duplicates: it says which ends of a molecule that option compares")
+    if not o.remove_duplicates:
+        return
+    o.duplicate_ends = o.duplicate_ends or "both"
+    if o.rescale_only or o.stats_only:
+        parser.error("--remove-duplicates belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
+    if not o.gpu_decode:
+        parser.error("--remove-duplicates marks the records on the device decode path: not with --host-decode")
+    if o.gpus > 1:
+        parser.error("--remove-duplicates cannot be combined with --gpus %d: the ranks take alternate slabs of the input, and a "
+                     "set of molecules per rank would miss the copies another rank has seen; use --gpus 1" % o.gpus)
+    if o.downsample is not None and o.downsample >= 1:
+        parser.error("--remove-duplicates cannot be combined with -n %d: the reservoir of a fixed number of reads is the host's; "
+                     "a fraction (-n below 1) is drawn on the way, in front of the duplicates" % int(o.downsample))
+
+
 def parse_args(argv):
     parser = build_parser()
     o = parser.parse_args(argv)
@@ -434,6 +471,7 @@ def parse_args(argv):
         except ValueError as error:
             parser.error(str(error))
     _check_write_kept(parser, o)
+    _check_remove_duplicates(parser, o)
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -810,6 +848,19 @@ def _device_path_applies(options, world=1, sam_text=True):
     return (bam or (sam_text and world == 1)) and (options.downsample is None or (options.downsample < 1 and world == 1))
 
 
+def _expected_records(options, reader):
+    """What sizes the first table of --remove-duplicates: a regular file's bytes over 48 (a short read with its qualities
+    compresses to 40 to 70 bytes in BAM), 0 — a small table that grows — for a stream.  Only the number of times the table
+    grows, and the slots it ends with, depend on it."""
+    source = getattr(reader, "source", None)
+    if source is not None and source.is_stream:
+        return 0
+    try:
+        return os.path.getsize(options.filename) // 48
+    except (OSError, TypeError):
+        return 0
+
+
 def _slab_bytes(options, world):
     """Compressed bytes per slab of the device decode path: a quarter of --chunk-mb (a slab of compressed bytes inflates to
     about four times its size) — 256 MiB at the default.  (Rounds 4-5 gave a single rank slabs of 1 GiB, for their fixed
@@ -958,9 +1009,13 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     by_pmd = bool(getattr(options, "by_pmd_score", False))
     # (--write-kept: BAM input, one rank — parse_args and main have seen to it)
     write_kept = getattr(options, "write_kept", None) is not None and not sam_text
+    # (--remove-duplicates: BAM input, one rank, as for --write-kept; the set of molecules lives on the device)
+    dedup = bool(getattr(options, "remove_duplicates", False)) and not sam_text
     carry = None
     try:
         engine.set_reference(ref)
+        if dedup:
+            engine.dedup_begin(options.duplicate_ends, _expected_records(options, reader))
         stages.mark("reference resident")
         warned_about_quals = False
         error = None
@@ -1029,6 +1084,10 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                     elif options.minqual and not warned_about_quals and stream.missing_qualities():
                         logger.warning("Reads without PHRED scores found; cannot filter by --min-basequal")
                         warned_about_quals = True
+                    if dedup:
+                        # (behind the draws, in front of the count: the later copies leave with 0x400, and everything from
+                        # here on — the kernels' flag filter, the groups' keys, --write-kept — sees the final flags)
+                        engine.dedup_mark(view)
                     engine.tabulate_view(view, record_base=n_reads)
                     if kept_out is not None:
                         kept_out.add(view)
@@ -1055,6 +1114,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             if error is None:
                 options.filter_counts = stream.filter_counts()
             tables = ranks.finish(engine, error)
+            if dedup:
+                options.duplicates = (engine.dedup_counts(), engine.dedup_histogram(), engine.dedup_info())
             if kept_out is not None:
                 kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
@@ -1085,7 +1146,7 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         reason = str(error)
     # never silent: a regression of the device path must not show up as nothing but a slow run
     options.gpu_decode_fallbacks = getattr(options, "gpu_decode_fallbacks", 0) + 1
-    if write_kept:
+    if write_kept or dedup:
         # (no route through the host decoder: the run ends, main says why)
         engine.close()
         logger.warning("GPU decode path gave up: %s", reason)
@@ -1098,6 +1159,28 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                        reason, "compressed" if isinstance(carry[1], tuple) else "byte",
                        carry[1][0] if isinstance(carry[1], tuple) else carry[1], carry[2])
     return None, carry
+
+
+def _report_duplicates(options, libraries, logger):
+    """--remove-duplicates: the log line, duplicates.tsv (per library: examined, duplicates, molecules, not examined because
+    paired / otherwise) and duplicates_histogram.tsv (per library: molecules seen ``Copies`` times, the non-empty bins; the last
+    bin is ``>=1024``) — the counts a library-complexity estimate starts from."""
+    counts, hist, info = options.duplicates
+    rows, bins = ["Sample\tLibrary\tExamined\tDuplicates\tMolecules\tPaired\tOther\n"], ["Sample\tLibrary\tCopies\tMolecules\n"]
+    for (sample, library), (examined, dups, paired, other), h in zip(libraries, counts.tolist(), hist.tolist()):
+        rows.append("%s\t%s\t%d\t%d\t%d\t%d\t%d\n" % (sample, library, examined, dups, examined - dups, paired, other))
+        bins += ["%s\t%s\t%s\t%d\n" % (sample, library, c + 1 if c + 1 < len(h) else ">=%d" % len(h), m) for c, m in enumerate(h) if m]
+    (options.folder / "duplicates.tsv").write_text("".join(rows))
+    (options.folder / "duplicates_histogram.tsv").write_text("".join(bins))
+    examined, dups, paired, other = (int(x) for x in counts.sum(axis=0))
+    logger.info("Duplicates: %d records examined, %d removed, %d molecules; not examined: %d paired, %d other",
+                examined, dups, examined - dups, paired, other)
+    if paired:
+        logger.warning("--remove-duplicates: %d paired records were not examined (a pair's molecule needs the mate's coordinates, "
+                       "which the option does not follow); they are counted as they are", paired)
+    logger.debug("Duplicates: ends %s; table of %d slots, grown %d times, longest walk %d slots, mean %.3f; %d bytes of HBM",
+                 options.duplicate_ends, info["slots"], info["growths"], info["longest_probe"],
+                 info["probes"] / max(1, info["examined"]), info["bytes"])
 
 
 def main(argv):
@@ -1223,6 +1306,10 @@ def main(argv):
             logger.error("--write-kept needs BAM input: '%s' is SAM text, and writing BAM from parsed text is not part of the "
                          "option (samtools view -b in front of the run)", options.filename)
             return 1
+        if options.remove_duplicates and not reader.is_bam:
+            logger.error("--remove-duplicates needs BAM input: '%s' is SAM text, which the option does not take (samtools view "
+                         "-b in front of the run)", options.filename)
+            return 1
         libraries = reader.get_libraries()
         try:
             options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
@@ -1266,6 +1353,10 @@ def main(argv):
             logger.error("--write-kept is written by the device decode path, which did not finish this run: nothing is "
                          "written, and the run does not go on without its output")
             return 1
+        if tables is None and options.remove_duplicates:
+            logger.error("--remove-duplicates marks the records on the device decode path, which did not finish this run: the "
+                         "host decoder cannot go on with a set of molecules that lives on the device, and nothing is written")
+            return 1
         if tables is None:
             tables = _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry)
         fallbacks = getattr(options, "gpu_decode_fallbacks", 0)
@@ -1285,6 +1376,8 @@ def main(argv):
             tables = groupings.kind_of(options).write(tables, options, options.strata, logger)
         else:
             tables.write(options.folder)
+        if options.remove_duplicates:
+            _report_duplicates(options, libraries, logger)
         if options.freq_files:
             (options.folder / "5pCtoT_freq.txt").write_text(tables.damage_frequency_text("5p", options.readplot))
             (options.folder / "3pGtoA_freq.txt").write_text(tables.damage_frequency_text("3p", options.readplot))

@@ -15,6 +15,10 @@ one BAM, then three commands timed as cold processes, each under a time limit of
   --calmd instead: the legs plain, kept, and
   calmd       `--write-kept calmd.bam --calmd`                                                           ... NM and MD recomputed
   mask_calmd  `--write-kept mask_calmd.bam --mask-ends 2,2 --calmd`                                      ... behind the mask
+  --remove-duplicates RATE instead: single-end records in coordinate order (its paired ones would all go unexamined), RATE of
+  them later copies of another record, and the legs plain, kept, and
+  dedup       `--remove-duplicates`                                                                      the later copies marked
+  dedup_kept  `--remove-duplicates --write-kept dedup_kept.bam`                                          ... and the rest written
 
 The repeats alternate the commands (plain, kept, pmd, plain, ...), three of each by default.  Reported per command: the wall
 times, their median and spread (max - min), reads/s from the median, and for the two writers the records and bytes written
@@ -23,11 +27,13 @@ of the tags (12 bytes a record, the score column, the walk over every written re
 index (four launches and two small copies per slab, the file's assembly on the host), mask_X - kept that of the mask (one
 launch per slab, in place in the stream; mask_ends.tsv gives the records and bases it masked), calmd - kept that of the
 recomputed tags (five launches and sixteen bytes back per slab, a second stream; calmd.tsv gives the records recomputed and
-skipped).  --parent-root DIR: a built checkout of the parent commit; `plain` is then also timed there — with --calmd `kept` as
+skipped), dedup - plain and dedup_kept - kept that of the duplicate stage (six small launches per slab; the table's slots, its
+growths, the longest and the mean walk of an insert and the HBM it holds are taken from the log, the counts from
+duplicates.tsv).  --parent-root DIR: a built checkout of the parent commit; `plain` is then also timed there — with --calmd `kept` as
 well —, in the same alternation: a difference between the two beyond the spread means the option-less path has changed.
 One JSON line on stdout.
 
-    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index | --mask-ends K | --calmd]"""
+    python tools/write_kept_bench.py [--reads N] [--repeats K] [--dir DIR] [--timeout S] [--parent-root DIR] [--tags | --index | --mask-ends K | --calmd | --remove-duplicates RATE]"""
 import argparse
 import json
 import os
@@ -63,6 +69,8 @@ def main():
     ap.add_argument("--index", action="store_true", help="coordinate-sorted records; time --write-kept with and without --write-index")
     ap.add_argument("--mask-ends", metavar="K5[,K3]", help="time --write-kept with and without --mask-ends K5[,K3], for each --mask-what")
     ap.add_argument("--calmd", action="store_true", help="time --write-kept with and without --calmd, and with --mask-ends 2,2 --calmd")
+    ap.add_argument("--remove-duplicates", type=float, metavar="RATE", help="single-end sorted records, RATE of them later copies; time "
+                    "--remove-duplicates with and without --write-kept")
     args = ap.parse_args()
     import numpy as np
 
@@ -73,7 +81,14 @@ def main():
         ref = synth.make_genome()
         bam, fa = os.path.join(work, "x.bam"), os.path.join(work, "x.fa")
         t0 = time.perf_counter()
-        if args.index:
+        if args.remove_duplicates is not None:
+            # (config-3's records, single-end, in coordinate order; the copies are whole records drawn again, each behind its first)
+            n_dup = int(round(args.reads * args.remove_duplicates))
+            batch = synth.make_reads(ref, args.reads - n_dup, args.seed, read_len=100, paired=False, frac_softclip=0.10, frac_ins=0.04, frac_del=0.04,
+                                     frac_skip=0.002, frac_hardclip=0.001, contigs=[0, 1], with_qual=True, sort=True)
+            pick = np.sort(np.concatenate([np.arange(batch.n), np.random.default_rng(args.seed).integers(0, batch.n, n_dup)]), kind="stable")
+            batch = batch.take(pick)
+        elif args.index:
             # (config-3's records — synth.config3_batch — in coordinate order)
             batch = synth.make_reads(ref, args.reads, args.seed, read_len=100, paired=True, frac_softclip=0.10, frac_ins=0.04, frac_del=0.04,
                                      frac_skip=0.002, frac_hardclip=0.001, contigs=[0, 1], with_qual=True, sort=True)
@@ -98,6 +113,10 @@ def main():
         if args.calmd:
             legs = legs[:2] + [("calmd", ROOT, ["--write-kept", os.path.join(work, "calmd.bam"), "--calmd"]),
                                ("mask_calmd", ROOT, ["--write-kept", os.path.join(work, "mask_calmd.bam"), "--mask-ends", "2,2", "--calmd"])]
+        if args.remove_duplicates is not None:
+            legs = legs[:2] + [("dedup", ROOT, ["--remove-duplicates"]),
+                               ("dedup_kept", ROOT, ["--remove-duplicates", "--write-kept", os.path.join(work, "dedup_kept.bam")])]
+            result["sorted"], result["duplicate_rate"] = True, args.remove_duplicates
         if args.tags:
             pmd_all = ["--by-pmd-score", "--pmd-thresholds", "3", "--write-kept"]
             legs += [("pmd_all", ROOT, pmd_all + [os.path.join(work, "pmd_all.bam")]),
@@ -131,7 +150,7 @@ def main():
                 path, groups, records, raw = open(tsv).read().splitlines()[1].split("\t")
                 result[name].update(groups=groups, records_written=int(records), uncompressed_bytes=int(raw), file_bytes=os.path.getsize(path))
         if status == 0:
-            for name in ("kept",) if args.index or args.mask_ends or args.calmd else ("kept", "pmd"):
+            for name in ("kept",) if args.index or args.mask_ends or args.calmd or args.remove_duplicates is not None else ("kept", "pmd"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
             if args.index:
                 result["kept_index_minus_kept_s"] = round(result["kept_index"]["median_s"] - result["kept"]["median_s"], 3)
@@ -162,6 +181,21 @@ def main():
                     result["kept_minus_parent_kept_s"] = round(result["kept"]["median_s"] - result["parent_kept"]["median_s"], 3)
                     if open(os.path.join(work, "kept.bam"), "rb").read() != open(os.path.join(work, "parent_kept.bam"), "rb").read():
                         result["error"] = "kept.bam differs from the parent's"
+            if args.remove_duplicates is not None:
+                import re
+                result["dedup_minus_plain_s"] = round(result["dedup"]["median_s"] - result["plain"]["median_s"], 3)
+                result["dedup_kept_minus_kept_s"] = round(result["dedup_kept"]["median_s"] - result["kept"]["median_s"], 3)
+                for name in ("dedup", "dedup_kept"):
+                    row = [int(x) for x in open(os.path.join(work, name, "duplicates.tsv")).read().splitlines()[1].split("\t")[2:]]
+                    result[name].update(zip(("examined", "duplicates", "molecules", "paired", "other"), row))
+                    log = open(os.path.join(work, name, "Runtime_log.txt")).read()
+                    m = re.search(r"table of (\d+) slots, grown (\d+) times, longest walk (\d+) slots, mean ([0-9.]+); (\d+) bytes of HBM", log)
+                    if m:
+                        result[name].update(slots=int(m.group(1)), growths=int(m.group(2)), longest_probe=int(m.group(3)), mean_probe=float(m.group(4)),
+                                            hbm_bytes=int(m.group(5)), hbm_bytes_per_examined=round(int(m.group(5)) / max(1, row[0]), 1))
+                if result["dedup_kept"]["records_written"] != n_counted - result["dedup_kept"]["duplicates"]:
+                    result["error"] = "dedup_kept.bam: %d records, %d counted without the option, %d duplicates" % (
+                        result["dedup_kept"]["records_written"], n_counted, result["dedup_kept"]["duplicates"])
             if args.tags:
                 result["pmd_tagged_minus_pmd_all_s"] = round(result["pmd_tagged"]["median_s"] - result["pmd_all"]["median_s"], 3)
                 extra = result["pmd_tagged"]["uncompressed_bytes"] - result["pmd_all"]["uncompressed_bytes"]
@@ -169,7 +203,8 @@ def main():
                     result["error"] = "pmd_tagged.bam: %d records, %d bytes more than pmd_all.bam; %d records counted" % (
                         result["pmd_tagged"]["records_written"], extra, n_counted)
             tables = {name: [open(os.path.join(work, name, f)).read() for f in FILES] for name, _, _ in legs}
-            same = all(t == tables["plain"] for t in tables.values())
+            # (the legs that drop the duplicates agree among themselves, the others with `plain`)
+            same = all(t == tables["dedup" if name.startswith("dedup") else "plain"] for name, t in tables.items())
             result["usual_tables"] = "byte-identical" if same else "MISMATCH"
             if result["kept"]["records_written"] != n_counted:
                 result["error"] = "kept.bam holds %d records, the run counted %d" % (result["kept"]["records_written"], n_counted)
