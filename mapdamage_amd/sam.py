@@ -701,12 +701,14 @@ class GpuBamStream:
         (rescale.py:277-278), BadReadError for a record the kernels cannot process."""
         import ctypes
         import numpy as np
-        n, nb, ncg = int(view.n_reads), int(view.n_bases), int(view.n_cigar)
-        # (the slab's inflated bytes are at most: per record 36 + a name of 255 + its CIGAR + 1.5 x its bases + tags — bounded
-        # by what the decoder itself allows: 4 x the compressed slab and more; taken from the view: bases x 1.5 + 4 per
-        # operation + 400 per record covers names and tags of any file this library has seen; a longer one is MDX_ERR_ARG)
-        cap = int(nb * 1.5) + 4 * ncg + 400 * n + (1 << 20)
-        cap += (cap // 0xFF00 + 1) * 64
+        # (the bound include/mdx.h states for ``out``: the inflated bytes of the view's records, from the chain of their offsets,
+        # seven more for every record of the view, 64 per member — ``mdx_gbam_kept_bound_tagged``, never a guess)
+        bound = ctypes.c_int64(0)
+        fn = self._lib.mdx_gbam_kept_bound_tagged
+        fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p], ctypes.c_int
+        if fn(self._g, ctypes.c_int32(7), ctypes.byref(bound)) != 0:
+            raise ValueError("%r: %s" % (str(self.path), self._error()))
+        cap = int(bound.value)
         out = np.empty(cap, np.uint8)
         out_len, clash = ctypes.c_int64(0), ctypes.c_int64(-1)
         fn = self._lib.mdx_gbam_rescale_slab
