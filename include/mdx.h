@@ -418,6 +418,54 @@ int mdx_dedup_counts(mdx_ctx *ctx, uint64_t *out /* [n_libraries][4] */);
 int mdx_dedup_histogram(mdx_ctx *ctx, uint64_t *out /* [n_libraries][1024] */);
 int mdx_dedup_info(mdx_ctx *ctx, uint64_t *info /* [8] */);
 
+/* ---- Depth of coverage of the counted records, gathered beside the tabulation: how much of the resident reference they
+ * cover, how deep, and where (the rule: csrc/mdx_depth_key.h).
+ *
+ * A record is COUNTED if (FLAG & 0xF04) == 0 on the flag column as it stands (behind the record filters,
+ * mdx_gbam_view_set_flags and mdx_dedup_mark), its library is below the context's libraries (on a stratified context:
+ * cfg.nlib / n_groups), 0 <= tid < n_contig, pos >= 0, its CIGAR consumes a reference base and pos + refspan does not pass
+ * the end of sequence tid.  A record that passes the first two checks and fails a later one is OUTSIDE: counted as such, it
+ * adds nothing.  M, = and X cover their bases; D and N advance without covering (samtools depth without -J); I, S, H and P
+ * neither advance nor break a covered stretch.
+ *
+ * The accumulator is a difference array in HBM: one int32 per base of the reference in its concatenated order and one more,
+ * allocated in whole tiles — 4 bytes per base, 12.4 GB for a genome of 3.1 Gb.  An interval [s, e) of sequence t adds +1 at
+ * off[t] + s and -1 at off[t] + e; the depth of a base is the prefix sum up to it.
+ *
+ *   mdx_depth_begin   after the reference is resident (else MDX_ERR_STATE): the zeroed accumulator; a second call zeroes it.
+ *                     An allocation that fails is MDX_ERR_HIP with the size in the message.  A new reference releases the
+ *                     accumulator: begin again.
+ *   mdx_depth_add     enqueued on the context's stream: the intervals of a device batch's counted records, two atomics each,
+ *                     and the counters.  Reads flag, lib, tid, pos and the CIGAR; writes nothing of the batch.  MDX_ERR_STATE
+ *                     without mdx_depth_begin.
+ *   mdx_depth_finish  synchronous; three launches (tile sums, a one-block scan of them, a pass that rebuilds the depths and
+ *                     consumes them) that leave the accumulator as it is: it may be called again, and more batches added
+ *                     behind it.  per_contig [n_contig][4]: counted records, covered bases (depth >= 1), aligned bases (the
+ *                     sum of depths), the largest depth.  hist [1024]: bases at depth d in bin d for d <= 1022, bin 1023 for
+ *                     d >= 1023; it sums to the reference's length.  counts [4]: counted records, outside records, intervals,
+ *                     maximal runs of depth > 0.  Any pointer may be NULL.
+ *   mdx_depth_runs    synchronous: the maximal runs of equal depth > 0 in reference order, end exclusive — the lines of
+ *                     `bedtools genomecov -bg`.  *n = their number; cap too small: MDX_ERR_ARG, *n still set, nothing written.
+ *   mdx_depth_fetch   introspection for tests, as mdx_reference_fetch: the depths of bases [start, end) of sequence tid.  The
+ *                     sums in front of the tile that holds the sequence's first element come from the finish's first two
+ *                     launches; the elements from there to `end` are copied and summed on the host.  (The sequence's own
+ *                     elements alone would not do: its first one also holds the -1s of the reads that end with the sequence
+ *                     in front.)
+ *   mdx_depth_info    info[0] records a block of the add kernel takes, [1] elements of a tile, [2] tiles a round of the
+ *                     one-block scan takes, [3] bytes of HBM held.
+ * mdx_reset zeroes the accumulator and the counters, mdx_destroy frees them.  MDX_TEST_DEPTH_ROUND=<tiles> in the
+ * environment, read at the mdx_depth_begin that allocates: a smaller info[2], for tests of the scan's round boundary.
+ *
+ * Limit: an element is an int32, so fewer than 2^31 records are added between mdx_depth_begin (or mdx_reset) and the end —
+ * added, whether counted or not, which the host knows without a readback.  The mdx_depth_add that would pass it returns
+ * MDX_ERR_ARG and adds nothing; the batches before it stand. */
+int mdx_depth_begin(mdx_ctx *ctx);
+int mdx_depth_add(mdx_ctx *ctx, const mdx_batch *device_batch);
+int mdx_depth_finish(mdx_ctx *ctx, uint64_t *per_contig /* [n_contig][4] */, uint64_t *hist /* [1024] */, uint64_t *counts /* [4] */);
+int mdx_depth_runs(mdx_ctx *ctx, int32_t *tid, int64_t *start, int64_t *end, uint32_t *depth, int64_t cap, int64_t *n);
+int mdx_depth_fetch(mdx_ctx *ctx, int32_t tid, int64_t start, int64_t end, uint32_t *out);
+int mdx_depth_info(mdx_ctx *ctx, uint64_t *info /* [4] */);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

@@ -200,6 +200,19 @@ struct mdx_ctx {
         std::vector<void *> retired;           // the store and the tables that were outgrown: freed where the stream is idle anyway
         DevBuf tmp, tile, rank, slot_of;
     } dedup;
+    // depth of coverage (mdx_depth_begin): the difference array over the resident reference, the counters of the adds and the
+    // scratch of a finish.  Nothing of it exists before mdx_depth_begin; a new reference releases it.
+    struct Depth {
+        bool on = false;
+        int32_t *diff = nullptr;               // [n_tiles * tile]: G + 1 elements and the padding, which stays zero
+        int64_t G = 0, n_tiles = 0;
+        int round = 0;                         // tiles a round of the one-block scan takes
+        int32_t *tile_sum = nullptr;           // [n_tiles]
+        unsigned long long *tile_runs = nullptr;   // [n_tiles]
+        unsigned long long *words = nullptr;   // counts [4] | records [n_contig] | res [n_contig][3] | hist [1024] | misc [2]
+        uint64_t added = 0;                    // records of the batches added: no fewer than the counted ones, known without a readback
+        std::vector<int64_t> off;              // the reference's offsets on the host [n_contig + 1]
+    } depth;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -326,6 +339,28 @@ int dedup_clear(mdx_ctx *c) {
 }
 
 #define MDX_DEDUP_MAX_SLOTS ((uint64_t)1 << 31)    // a slot's index is kept in 32 bits per record of the batch
+
+// ---- depth of coverage: the context's side (the launches: mdx_depth.hip)
+void depth_release(mdx_ctx *c) {
+    auto &d = c->depth;
+    void *ptrs[] = {d.diff, d.tile_sum, d.tile_runs, d.words};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    d = mdx_ctx::Depth{};
+}
+size_t depth_words(const mdx_ctx *c) { return 4 + (size_t)c->n_contig * 4 + MDX_DEPTH_HIST_BINS + 2; }
+unsigned long long *depth_records(mdx_ctx *c) { return c->depth.words + 4; }
+unsigned long long *depth_res(mdx_ctx *c) { return c->depth.words + 4 + (size_t)c->n_contig; }
+unsigned long long *depth_hist(mdx_ctx *c) { return c->depth.words + 4 + (size_t)c->n_contig * 4; }
+unsigned long long *depth_misc(mdx_ctx *c) { return depth_hist(c) + MDX_DEPTH_HIST_BINS; }
+
+// the accumulator and the counters zeroed (enqueued)
+int depth_clear(mdx_ctx *c) {
+    auto &d = c->depth;
+    HIP_TRY(c, hipMemsetAsync(d.diff, 0, (size_t)d.n_tiles * (size_t)mdx_k_depth_tile() * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d.words, 0, depth_words(c) * 8, c->stream));
+    d.added = 0;
+    return MDX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -478,6 +513,7 @@ void mdx_destroy(mdx_ctx *c) {
     if (c->gbam_stream) (void)hipStreamDestroy((hipStream_t)c->gbam_stream);
     if (c->gbam_event) (void)hipEventDestroy((hipEvent_t)c->gbam_event);
     dedup_release(c);
+    depth_release(c);
     c->lists.release();
     c->unpacked.release();
     c->lowq.release();
@@ -518,6 +554,7 @@ static int ref_begin(mdx_ctx *c, int64_t n, int32_t n_contig) {
     if (c->d_ref) { (void)hipFree(c->d_ref); c->d_ref = nullptr; }
     if (c->d_ref4) { (void)hipFree(c->d_ref4); c->d_ref4 = nullptr; }
     if (c->d_contig_off) { (void)hipFree(c->d_contig_off); c->d_contig_off = nullptr; }
+    depth_release(c);      // (an accumulator is laid out by the reference it was begun on)
     c->n_contig = 0; c->ref_len = 0;
     HIP_TRY(c, hipMalloc((void **)&c->d_ref, (size_t)n + 2 * kRefPad + 1));
     HIP_TRY(c, hipMalloc((void **)&c->d_contig_off, (size_t)(n_contig + 1) * 8));
@@ -1418,6 +1455,7 @@ int mdx_reset(mdx_ctx *c) {
     int rc = zero_accumulators(c);
     if (rc != MDX_OK) return rc;
     if (c->dedup.on && (rc = dedup_clear(c)) != MDX_OK) return rc;
+    if (c->depth.on && (rc = depth_clear(c)) != MDX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     dedup_free_retired(c);
     c->err.clear();
@@ -1556,6 +1594,197 @@ int mdx_dedup_info(mdx_ctx *c, uint64_t *info) {
     info[0] = d.n_slots; info[1] = d.growths; info[2] = state[3]; info[3] = state[2]; info[4] = state[0] + state[1];
     info[5] = d.store_cap * sizeof(MdxDupSig) + d.n_slots * 12;
     info[6] = (uint64_t)mdx_k_dedup_block(); info[7] = (uint64_t)mdx_k_dedup_scan_records();
+    return MDX_OK;
+}
+
+int mdx_depth_begin(mdx_ctx *c) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->d_ref || !c->d_contig_off) return fail(c, MDX_ERR_STATE, "mdx_depth_begin: mdx_set_reference has not been called");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto &d = c->depth;
+    if (d.on) return depth_clear(c);
+    const int64_t tile = mdx_k_depth_tile();
+    d.G = c->ref_len;
+    d.n_tiles = (d.G + 1 + tile - 1) / tile;
+    d.round = (int)mdx_k_depth_round();
+    // (tests: the scan's round boundary out of a reference of a few tiles)
+    if (const char *e = getenv("MDX_TEST_DEPTH_ROUND"); e && *e) {
+        const long long r = strtoll(e, nullptr, 10);
+        if (r >= 1 && r < d.round) d.round = (int)r;
+    }
+    const size_t bytes = (size_t)d.n_tiles * (size_t)tile * 4;
+    if (hipMalloc((void **)&d.diff, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        d.diff = nullptr;
+        depth_release(c);
+        return fail(c, MDX_ERR_HIP, "mdx_depth_begin: out of device memory for the accumulator of " + std::to_string(bytes) + " bytes (4 per base of a reference of " +
+                                    std::to_string(c->ref_len) + ")");
+    }
+    d.off.resize((size_t)c->n_contig + 1);
+    hipError_t e = hipMalloc((void **)&d.tile_sum, (size_t)d.n_tiles * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.tile_runs, (size_t)d.n_tiles * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&d.words, depth_words(c) * 8);
+    if (e == hipSuccess) e = hipMemcpy(d.off.data(), c->d_contig_off, d.off.size() * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        depth_release(c);
+        return fail(c, MDX_ERR_HIP, std::string("mdx_depth_begin: ") + hipGetErrorString(e));
+    }
+    if (const int rc = depth_clear(c); rc != MDX_OK) { depth_release(c); return rc; }
+    d.on = true;
+    return MDX_OK;
+}
+
+int mdx_depth_add(mdx_ctx *c, const mdx_batch *b) {
+    if (const int rc = check_batch(c, b); rc != MDX_OK) return rc;
+    auto &d = c->depth;
+    if (!d.on) return fail(c, MDX_ERR_STATE, "mdx_depth_add: call mdx_depth_begin first");
+    if (b->n_reads == 0) return MDX_OK;
+    // (an element is an int32: the counted records are not known without a readback, the records added bound them)
+    if (d.added + (uint64_t)b->n_reads >= ((uint64_t)1 << 31))
+        return fail(c, MDX_ERR_ARG, "mdx_depth_add: 2^31 records or more since mdx_depth_begin; an element of the accumulator is an int32");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    MdxDepthKey k{};
+    k.n = b->n_reads; k.n_cigar = b->n_cigar;
+    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos; k.cigar_off = b->cigar_off; k.cigar = b->cigar;
+    k.contig_off = c->d_contig_off; k.n_contig = c->n_contig; k.n_libraries = dedup_libraries(c);
+    mdx_k_depth_add(k, d.diff, d.words, depth_records(c), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    d.added += (uint64_t)b->n_reads;
+    return MDX_OK;
+}
+
+// the finish's launches on the stream; with `runs`, the run starts are counted, their buffers sized by a readback and filled
+static int depth_scan(mdx_ctx *c, bool runs, DevBuf *run_pos, DevBuf *run_depth, uint64_t *n_starts) {
+    auto &d = c->depth;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // (what a finish gathers starts from zero: res, hist, misc; the counters of the adds stand)
+    HIP_TRY(c, hipMemsetAsync(depth_res(c), 0, ((size_t)c->n_contig * 3 + MDX_DEPTH_HIST_BINS + 2) * 8, c->stream));
+    MdxDepthScan a{};
+    a.diff = d.diff; a.G = d.G; a.contig_off = c->d_contig_off; a.n_contig = c->n_contig; a.n_tiles = d.n_tiles; a.round = d.round;
+    a.want_runs = runs ? 1 : 0;
+    a.tile_sum = d.tile_sum; a.tile_runs = d.tile_runs; a.res = depth_res(c); a.hist = depth_hist(c); a.misc = depth_misc(c);
+    mdx_k_depth_finish(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if (runs) {
+        unsigned long long starts = 0;
+        HIP_TRY(c, hipMemcpyAsync(&starts, depth_misc(c), 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        *n_starts = starts;
+        if (starts) {
+            if (run_pos->reserve((size_t)starts * 8) != hipSuccess || run_depth->reserve((size_t)starts * 4) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, MDX_ERR_HIP, "mdx_depth_runs: out of device memory for " + std::to_string(starts) + " runs of 12 bytes");
+            }
+            a.run_pos = (int64_t *)run_pos->p; a.run_depth = (uint32_t *)run_depth->p; a.run_cap = starts;
+        }
+    }
+    mdx_k_depth_stats(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return MDX_OK;
+}
+
+int mdx_depth_finish(mdx_ctx *c, uint64_t *per_contig, uint64_t *hist, uint64_t *counts) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_finish: call mdx_depth_begin first");
+    if (const int rc = depth_scan(c, false, nullptr, nullptr, nullptr); rc != MDX_OK) return rc;
+    std::vector<unsigned long long> w(depth_words(c));
+    HIP_TRY(c, hipMemcpyAsync(w.data(), c->depth.words, w.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t nc = (size_t)c->n_contig;
+    if (per_contig)
+        for (size_t t = 0; t < nc; t++) {
+            per_contig[4 * t] = w[4 + t];
+            for (int q = 0; q < 3; q++) per_contig[4 * t + 1 + q] = w[4 + nc + 3 * t + q];
+        }
+    if (hist) for (size_t q = 0; q < MDX_DEPTH_HIST_BINS; q++) hist[q] = w[4 + 4 * nc + q];
+    if (counts) { counts[0] = w[0]; counts[1] = w[1]; counts[2] = w[2]; counts[3] = w[4 + 4 * nc + MDX_DEPTH_HIST_BINS + 1]; }
+    return MDX_OK;
+}
+
+int mdx_depth_runs(mdx_ctx *c, int32_t *tid, int64_t *start, int64_t *end, uint32_t *depth, int64_t cap, int64_t *n) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_runs: call mdx_depth_begin first");
+    if (!n || cap < 0 || (cap > 0 && (!tid || !start || !end || !depth))) return fail(c, MDX_ERR_ARG, "mdx_depth_runs: null output");
+    DevBuf d_pos, d_depth;
+    uint64_t starts = 0;
+    int rc = depth_scan(c, true, &d_pos, &d_depth, &starts);
+    unsigned long long positive = 0;
+    hipError_t e = hipSuccess;
+    if (rc == MDX_OK) {
+        e = hipMemcpyAsync(&positive, depth_misc(c) + 1, 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    } else {
+        (void)hipStreamSynchronize(c->stream);
+    }
+    std::vector<int64_t> pos;
+    std::vector<uint32_t> dep;
+    if (rc == MDX_OK && e == hipSuccess && (int64_t)positive <= cap && starts) {
+        try { pos.resize((size_t)starts); dep.resize((size_t)starts); } catch (const std::bad_alloc &) { rc = fail(c, MDX_ERR_ARG, "mdx_depth_runs: out of host memory"); }
+        if (rc == MDX_OK) e = hipMemcpy(pos.data(), d_pos.p, (size_t)starts * 8, hipMemcpyDeviceToHost);
+        if (rc == MDX_OK && e == hipSuccess) e = hipMemcpy(dep.data(), d_depth.p, (size_t)starts * 4, hipMemcpyDeviceToHost);
+    }
+    d_pos.release(); d_depth.release();
+    if (rc != MDX_OK) return rc;
+    if (e != hipSuccess) return fail(c, MDX_ERR_HIP, std::string("mdx_depth_runs: ") + hipGetErrorString(e));
+    *n = (int64_t)positive;
+    if ((int64_t)positive > cap) return fail(c, MDX_ERR_ARG, "mdx_depth_runs: " + std::to_string(positive) + " runs, room for " + std::to_string(cap));
+    // a run ends where the next begins, or with its sequence; the runs of depth 0 leave here
+    const std::vector<int64_t> &off = c->depth.off;
+    const int nc = c->n_contig;
+    int t = 0;
+    int64_t out = 0;
+    for (size_t r = 0; r < pos.size(); r++) {
+        while (t + 1 < nc && pos[r] >= off[(size_t)t + 1]) t++;
+        if (dep[r] == 0 || out >= cap) continue;
+        const int64_t stop = r + 1 < pos.size() && pos[r + 1] < off[(size_t)t + 1] ? pos[r + 1] : off[(size_t)t + 1];
+        tid[out] = t; start[out] = pos[r] - off[(size_t)t]; end[out] = stop - off[(size_t)t]; depth[out] = dep[r];
+        out++;
+    }
+    return MDX_OK;
+}
+
+int mdx_depth_fetch(mdx_ctx *c, int32_t tid, int64_t start, int64_t end, uint32_t *out) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_fetch: call mdx_depth_begin first");
+    if (!out || tid < 0 || tid >= c->n_contig || start < 0 || end < start) return fail(c, MDX_ERR_ARG, "mdx_depth_fetch: bad range");
+    const std::vector<int64_t> &off = c->depth.off;
+    if (end > off[(size_t)tid + 1] - off[(size_t)tid]) return fail(c, MDX_ERR_ARG, "mdx_depth_fetch: beyond the sequence's end");
+    if (end == 0) return MDX_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    // The element of a sequence's first base also holds the -1s of the reads that end with the sequence in front of it, so the
+    // sequence's own elements do not sum to its depths: the sums in front of the tile that holds its first element come from
+    // the finish's first two launches, the rest is summed here.
+    const int64_t tile = mdx_k_depth_tile(), at = off[(size_t)tid], first = at / tile * tile;
+    MdxDepthScan a{};
+    a.diff = c->depth.diff; a.G = c->depth.G; a.contig_off = c->d_contig_off; a.n_contig = c->n_contig; a.n_tiles = c->depth.n_tiles;
+    a.round = c->depth.round; a.tile_sum = c->depth.tile_sum; a.tile_runs = c->depth.tile_runs; a.misc = depth_misc(c);
+    mdx_k_depth_finish(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    try {
+        int32_t before = 0;
+        std::vector<int32_t> w((size_t)(at + end - first));
+        HIP_TRY(c, hipMemcpy(&before, c->depth.tile_sum + first / tile, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(w.data(), c->depth.diff + first, w.size() * 4, hipMemcpyDeviceToHost));
+        int64_t d = before;
+        for (int64_t i = first; i < at + end; i++) {
+            d += w[(size_t)(i - first)];
+            if (i >= at + start) out[i - at - start] = (uint32_t)d;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(c, MDX_ERR_ARG, "mdx_depth_fetch: out of host memory");
+    }
+    return MDX_OK;
+}
+
+int mdx_depth_info(mdx_ctx *c, uint64_t *info) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_info: call mdx_depth_begin first");
+    if (!info) return fail(c, MDX_ERR_ARG, "mdx_depth_info: null output");
+    const auto &d = c->depth;
+    info[0] = (uint64_t)mdx_k_depth_block(); info[1] = (uint64_t)mdx_k_depth_tile(); info[2] = (uint64_t)d.round;
+    info[3] = (uint64_t)d.n_tiles * ((uint64_t)mdx_k_depth_tile() * 4 + 12) + depth_words(c) * 8;
     return MDX_OK;
 }
 

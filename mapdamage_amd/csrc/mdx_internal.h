@@ -502,6 +502,32 @@ void mdx_k_dedup_mark(const MdxDupKey &k, uint16_t *flag, const MdxDedupArgs &a,
 void mdx_k_dedup_rehash(const MdxDupTable &from, uint64_t n_slots, const MdxDupTable &to, const MdxDupSig *store, hipStream_t s);
 void mdx_k_dedup_histogram(const MdxDupTable &t, uint64_t n_slots, const MdxDupSig *store, int n_libraries, unsigned long long *hist, hipStream_t s);
 
+// ---- depth of coverage (mdx_depth.hip, where the launches are told; the rule: mdx_depth_key.h)
+#include "mdx_depth_key.h"
+struct MdxDepthScan {
+    const int32_t *diff;            // [n_tiles * tile], zero from element G + 1 on
+    int64_t G;                      // bases of the reference
+    const int64_t *contig_off;      // [n_contig + 1]
+    int n_contig;
+    int64_t n_tiles;
+    int round;                      // tiles a round of the one-block scan takes (1 .. mdx_k_depth_round())
+    int want_runs;                  // count the run starts beside the sums
+    int32_t *tile_sum;              // [n_tiles] a tile's sum, then the sum in front of it
+    unsigned long long *tile_runs;  // [n_tiles] the same for its run starts
+    unsigned long long *res;        // [n_contig][3]: covered, aligned, max
+    unsigned long long *hist;       // [MDX_DEPTH_HIST_BINS]
+    unsigned long long *misc;       // [2]: all run starts (the scan), those of depth > 0 (the third pass)
+    int64_t *run_pos;               // [run_cap] or null: every run start's element ...
+    uint32_t *run_depth;            // ... and depth, in reference order
+    unsigned long long run_cap;
+};
+int mdx_k_depth_block();            // records a block of depth_add_kernel takes
+int64_t mdx_k_depth_tile();         // elements of a tile of the finish
+int64_t mdx_k_depth_round();        // tiles a round of the one-block scan takes at most
+void mdx_k_depth_add(const MdxDepthKey &k, int32_t *diff, unsigned long long *counts, unsigned long long *seq_records, hipStream_t s);
+void mdx_k_depth_finish(const MdxDepthScan &a, hipStream_t s);      // sums and scan
+void mdx_k_depth_stats(const MdxDepthScan &a, hipStream_t s);       // the third pass
+
 // ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
 #include "mdx_filter.h"
 

@@ -54,6 +54,7 @@ EXPORTS = (
     "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
     "mdx_gsam_filter_counts",
     "mdx_dedup_begin", "mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info",
+    "mdx_depth_begin", "mdx_depth_add", "mdx_depth_finish", "mdx_depth_runs", "mdx_depth_fetch", "mdx_depth_info",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -211,6 +212,13 @@ def load_library(path=None):
     lib.mdx_dedup_begin.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]
     for name in ("mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info"):
         getattr(lib, name).argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_depth_begin.argtypes = [ctypes.c_void_p]
+    lib.mdx_depth_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_depth_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_depth_runs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                   ctypes.c_void_p]
+    lib.mdx_depth_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
+    lib.mdx_depth_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -498,10 +506,59 @@ class DamageEngine:
         return dict(zip(("slots", "growths", "longest_probe", "probes", "examined", "bytes", "block_records", "scan_records"),
                         (int(x) for x in out)))
 
+    # ------------------------------------------------------------------ depth of coverage
+    DEPTH_BINS = 1024
+
+    def depth_begin(self):
+        """The zeroed accumulator over the resident reference, 4 bytes per base (include/mdx.h ``mdx_depth_begin``); a second
+        call zeroes it."""
+        self._check(self._lib.mdx_depth_begin(self._ctx))
+
+    def depth_add(self, view):
+        """The covered intervals of a device batch's counted records into the accumulator (``mdx_depth_add``): enqueued.  The
+        flag column is read as it stands, so behind ``dedup_mark`` the later copies add nothing."""
+        dev = view.dev if isinstance(view, DeviceBatch) else view
+        self._check(self._lib.mdx_depth_add(self._ctx, ctypes.byref(dev)))
+
+    def depth_finish(self):
+        """``(per_contig, hist, counts)`` (``mdx_depth_finish``): uint64 [sequences][4] — counted records, covered bases,
+        aligned bases, largest depth —, uint64 [1024] — bases at depth ``d``, the last bin ``>= 1023`` — and a dict of the
+        records counted, those outside their sequence, the intervals and the runs of depth > 0."""
+        per_contig = np.zeros((getattr(self, "_n_contig", 0), 4), np.uint64)
+        hist = np.zeros(self.DEPTH_BINS, np.uint64)
+        counts = np.zeros(4, np.uint64)
+        self._check(self._lib.mdx_depth_finish(self._ctx, _ptr(per_contig), _ptr(hist), _ptr(counts)))
+        return per_contig, hist, dict(zip(("counted", "outside", "intervals", "runs"), (int(x) for x in counts)))
+
+    def depth_runs(self):
+        """``(tid, start, end, depth)``: the maximal runs of equal depth > 0 in reference order (``mdx_depth_runs``)."""
+        n = ctypes.c_int64(0)
+        rc = self._lib.mdx_depth_runs(self._ctx, None, None, None, None, ctypes.c_int64(0), ctypes.byref(n))
+        if rc != 0 and n.value == 0:
+            self._check(rc)
+        cap = max(1, n.value)
+        tid, start, end, depth = np.zeros(cap, np.int32), np.zeros(cap, np.int64), np.zeros(cap, np.int64), np.zeros(cap, np.uint32)
+        self._check(self._lib.mdx_depth_runs(self._ctx, _ptr(tid), _ptr(start), _ptr(end), _ptr(depth), ctypes.c_int64(cap), ctypes.byref(n)))
+        return tid[:n.value], start[:n.value], end[:n.value], depth[:n.value]
+
+    def depth_fetch(self, tid, start, end):
+        """uint32 depths of bases ``[start, end)`` of sequence ``tid`` as the accumulator holds them (``mdx_depth_fetch``; tests)."""
+        out = np.zeros(max(0, end - start), np.uint32)
+        self._check(self._lib.mdx_depth_fetch(self._ctx, ctypes.c_int32(tid), ctypes.c_int64(start), ctypes.c_int64(end), _ptr(out) if len(out) else _ptr(np.zeros(1, np.uint32))))
+        return out
+
+    def depth_info(self):
+        """The stage's sizes (``mdx_depth_info``): the records a block of the add kernel takes, the elements of a tile, the
+        tiles a round of the one-block scan takes, the bytes of HBM held."""
+        out = np.zeros(4, np.uint64)
+        self._check(self._lib.mdx_depth_info(self._ctx, _ptr(out)))
+        return dict(zip(("block_records", "tile", "round_tiles", "bytes"), (int(x) for x in out)))
+
     def set_reference(self, ref):
         """``ref``: a ``Reference`` (contigs in host memory) or a ``fasta.FastaOnDisk`` — the FASTA file itself, which the
         library sends to HBM as it lies on disk and strips of its line ends there (``mdx_set_reference_fasta``)."""
         path = getattr(ref, "path", None)
+        self._n_contig = len(ref.names)
         if path is not None:
             names = [n.encode() for n in ref.names]
             arr = (ctypes.c_char_p * max(1, len(names)))(*names)

@@ -16,6 +16,7 @@ from pathlib import Path
 import numpy as np
 
 from . import __version__, groupings
+from . import depth as depth_files
 from .batch import mark_unmaskable
 from .engine import BadReadError, DamageEngine, MdxError
 from .groupings import PmdScore, TerminalDamage        # noqa: F401  (where callers import them from)
@@ -269,6 +270,18 @@ def build_parser():
                    help="with --remove-duplicates: `both` ends of the molecule (the default: merged reads, whose two ends are the "
                         "molecule's), or the `5p` end alone — the unclipped start of a forward record, the unclipped end of a "
                         "reverse one —, as `samtools rmdup -s` does for single-end reads whose 3' end is where sequencing stopped")
+    g.add_argument("--depth", action="store_true", default=False,
+                   help="depth of coverage of the counted records, in the same pass: every record the flag filter, the record "
+                        "filters, --downsample to a fraction and --remove-duplicates leave, whose library is known and whose "
+                        "alignment lies inside its sequence, covers the reference bases of its M, = and X operations (D and N "
+                        "advance without covering, as `samtools depth` without -J).  coverage.tsv gives per sequence and for "
+                        "the whole reference the reads, covered bases, breadth, aligned bases, mean and largest depth; "
+                        "depth_histogram.tsv the reference bases at every depth.  Takes 4 bytes of device memory per reference "
+                        "base.  The groups of a run do not part it.  BAM input on the device decode path only: not SAM text, "
+                        "--host-decode, --gpus above 1 or -n N.  Not a reference option")
+    g.add_argument("--depth-bedgraph", metavar="PATH", default=None,
+                   help="with --depth: the stretches of equal depth above 0 as `name start end depth` lines, what `bedtools "
+                        "genomecov -bg` writes; written under a temporary name and moved into place at the end")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -421,6 +434,34 @@ def _check_remove_duplicates(parser, o):
                      "a fraction (-n below 1) is drawn on the way, in front of the duplicates" % int(o.downsample))
 
 
+def _check_depth(parser, o):
+    """The argument errors of --depth / --depth-bedgraph."""
+    if o.depth_bedgraph is not None and not o.depth:
+        parser.error("--depth-bedgraph needs --depth: it writes the runs of the depth that option gathers")
+    if not o.depth:
+        return
+    if o.rescale_only or o.stats_only:
+        parser.error("--depth belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
+    if not o.gpu_decode:
+        parser.error("--depth is gathered on the device decode path: not with --host-decode")
+    if o.gpus > 1:
+        parser.error("--depth cannot be combined with --gpus %d: the ranks take alternate slabs of the input, and the "
+                     "accumulators of the ranks would have to be summed across the cards; use --gpus 1" % o.gpus)
+    if o.downsample is not None and o.downsample >= 1:
+        parser.error("--depth cannot be combined with -n %d: the reservoir of a fixed number of reads is the host's and knows "
+                     "its sample at the end of the input only; a fraction (-n below 1) is drawn on the way" % int(o.downsample))
+    if o.depth_bedgraph is not None:
+        if not Path(o.depth_bedgraph).absolute().parent.is_dir():
+            parser.error("--depth-bedgraph %s: its directory does not exist" % o.depth_bedgraph)
+        if o.filename is not None and not is_stream(o.filename):
+            try:
+                same = os.path.samefile(o.filename, o.depth_bedgraph)
+            except OSError:
+                same = False
+            if same:
+                parser.error("--depth-bedgraph %s is the input file: the run would overwrite what it reads" % o.depth_bedgraph)
+
+
 def parse_args(argv):
     parser = build_parser()
     o = parser.parse_args(argv)
@@ -472,6 +513,7 @@ def parse_args(argv):
             parser.error(str(error))
     _check_write_kept(parser, o)
     _check_remove_duplicates(parser, o)
+    _check_depth(parser, o)
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -1011,11 +1053,15 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     write_kept = getattr(options, "write_kept", None) is not None and not sam_text
     # (--remove-duplicates: BAM input, one rank, as for --write-kept; the set of molecules lives on the device)
     dedup = bool(getattr(options, "remove_duplicates", False)) and not sam_text
+    # (--depth: BAM input, one rank, likewise; the accumulator lies over the resident reference)
+    depth = bool(getattr(options, "depth", False)) and not sam_text
     carry = None
     try:
         engine.set_reference(ref)
         if dedup:
             engine.dedup_begin(options.duplicate_ends, _expected_records(options, reader))
+        if depth:
+            engine.depth_begin()
         stages.mark("reference resident")
         warned_about_quals = False
         error = None
@@ -1088,6 +1134,9 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                         # (behind the draws, in front of the count: the later copies leave with 0x400, and everything from
                         # here on — the kernels' flag filter, the groups' keys, --write-kept — sees the final flags)
                         engine.dedup_mark(view)
+                    if depth:
+                        # (the final flags: behind the filters, the draws and the duplicates' marks)
+                        engine.depth_add(view)
                     engine.tabulate_view(view, record_base=n_reads)
                     if kept_out is not None:
                         kept_out.add(view)
@@ -1116,6 +1165,9 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             tables = ranks.finish(engine, error)
             if dedup:
                 options.duplicates = (engine.dedup_counts(), engine.dedup_histogram(), engine.dedup_info())
+            if depth:
+                options.depth_result = (list(ref.names), [int(x) for x in ref.lengths]) + engine.depth_finish() + (
+                    engine.depth_runs() if options.depth_bedgraph is not None else None, engine.depth_info())
             if kept_out is not None:
                 kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
@@ -1146,7 +1198,7 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         reason = str(error)
     # never silent: a regression of the device path must not show up as nothing but a slow run
     options.gpu_decode_fallbacks = getattr(options, "gpu_decode_fallbacks", 0) + 1
-    if write_kept or dedup:
+    if write_kept or dedup or depth:
         # (no route through the host decoder: the run ends, main says why)
         engine.close()
         logger.warning("GPU decode path gave up: %s", reason)
@@ -1181,6 +1233,17 @@ def _report_duplicates(options, libraries, logger):
     logger.debug("Duplicates: ends %s; table of %d slots, grown %d times, longest walk %d slots, mean %.3f; %d bytes of HBM",
                  options.duplicate_ends, info["slots"], info["growths"], info["longest_probe"],
                  info["probes"] / max(1, info["examined"]), info["bytes"])
+
+
+def _report_depth(options, logger):
+    """--depth: coverage.tsv, depth_histogram.tsv, the log line and the bedGraph of --depth-bedgraph (mapdamage_amd/depth.py)."""
+    names, lengths, per_contig, hist, counts, runs, info = options.depth_result
+    (options.folder / "coverage.tsv").write_text(depth_files.coverage_text(names, lengths, per_contig))
+    (options.folder / "depth_histogram.tsv").write_text(depth_files.histogram_text(hist))
+    if runs is not None:
+        depth_files.write_bedgraph(options.depth_bedgraph, names, *runs)
+    logger.info(depth_files.log_line(lengths, per_contig, counts))
+    logger.debug("Depth: %d intervals, %d runs of depth > 0; %d bytes of HBM", counts["intervals"], counts["runs"], info["bytes"])
 
 
 def main(argv):
@@ -1310,6 +1373,10 @@ def main(argv):
             logger.error("--remove-duplicates needs BAM input: '%s' is SAM text, which the option does not take (samtools view "
                          "-b in front of the run)", options.filename)
             return 1
+        if options.depth and not reader.is_bam:
+            logger.error("--depth needs BAM input: '%s' is SAM text, which the option does not take (samtools view -b in front "
+                         "of the run)", options.filename)
+            return 1
         libraries = reader.get_libraries()
         try:
             options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
@@ -1357,6 +1424,10 @@ def main(argv):
             logger.error("--remove-duplicates marks the records on the device decode path, which did not finish this run: the "
                          "host decoder cannot go on with a set of molecules that lives on the device, and nothing is written")
             return 1
+        if tables is None and options.depth:
+            logger.error("--depth is gathered on the device decode path, which did not finish this run: the host decoder cannot "
+                         "go on with an accumulator that lives on the device, and nothing is written")
+            return 1
         if tables is None:
             tables = _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry)
         fallbacks = getattr(options, "gpu_decode_fallbacks", 0)
@@ -1378,6 +1449,8 @@ def main(argv):
             tables.write(options.folder)
         if options.remove_duplicates:
             _report_duplicates(options, libraries, logger)
+        if options.depth:
+            _report_depth(options, logger)
         if options.freq_files:
             (options.folder / "5pCtoT_freq.txt").write_text(tables.damage_frequency_text("5p", options.readplot))
             (options.folder / "3pGtoA_freq.txt").write_text(tables.damage_frequency_text("3p", options.readplot))
