@@ -466,6 +466,32 @@ int mdx_depth_runs(mdx_ctx *ctx, int32_t *tid, int64_t *start, int64_t *end, uin
 int mdx_depth_fetch(mdx_ctx *ctx, int32_t tid, int64_t start, int64_t end, uint32_t *out);
 int mdx_depth_info(mdx_ctx *ctx, uint64_t *info /* [4] */);
 
+/* Depth on target: the depths of mdx_depth_* parted by the region strata of the context (mdx_set_strata_regions), without a
+ * second pass over the records.  The rule of what counts and covers is unchanged; only the attribution of BASES is new: base
+ * p of sequence t belongs to interval k of t iff iv_start[k] <= p < iv_end[k], and to the rest otherwise — every base of a
+ * sequence without intervals too.  (The tables part RECORDS, by the first interval a record overlaps: a read that hangs over
+ * an interval's edge adds its outside bases to the rest here.)  The intervals are the strata's as they stand, abutting
+ * intervals of different groups apart.
+ *
+ * Synchronous: the tile sums and their scan as for mdx_depth_finish, then one pass (depth_regions_kernel) that rebuilds the
+ * depths as the third launch of the finish does and consumes them as runs that also end where the interval changes.  The
+ * accumulator stays as it is: the call may be repeated, and made between adds.
+ *   per_interval [n_iv][4]       covered bases, aligned bases, smallest depth, largest depth of each interval, in the order of
+ *                                the strata's columns
+ *   per_group [n_groups][4]      bases, covered, aligned, largest depth: a group's row is the sum (the max) over its
+ *                                intervals; the row of rest_group also holds the bases no interval covers and their numbers
+ *   group_hist [n_groups][1024]  bases of the group at depth d, binned as mdx_depth_finish bins; the rest's bases in the row
+ *                                of rest_group.  The rows sum to the histogram of mdx_depth_finish.
+ * Any pointer may be NULL.  n_iv == 0 is valid: everything is the rest.
+ * MDX_ERR_STATE without mdx_depth_begin or without region strata.  MDX_ERR_ARG, naming the interval, if one ends beyond its
+ * sequence's length (mdx_set_strata_regions does not know the lengths), or if the strata name another number of sequences
+ * than the reference has: nothing is launched.
+ * The first call reads the intervals back, builds their columns in the accumulator's element coordinates (16 bytes per
+ * interval) and allocates the words the pass writes (32 bytes per interval, 8 KiB per group); mdx_depth_info's bytes include
+ * them from then on.  mdx_reset, mdx_destroy, a new reference and a new mdx_set_strata_regions release them. */
+int mdx_depth_regions(mdx_ctx *ctx, uint64_t *per_interval /* [n_iv][4] */, uint64_t *per_group /* [n_groups][4] */,
+                      uint64_t *group_hist /* [n_groups][1024] */);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

@@ -212,6 +212,17 @@ struct mdx_ctx {
         unsigned long long *words = nullptr;   // counts [4] | records [n_contig] | res [n_contig][3] | hist [1024] | misc [2]
         uint64_t added = 0;                    // records of the batches added: no fewer than the counted ones, known without a readback
         std::vector<int64_t> off;              // the reference's offsets on the host [n_contig + 1]
+        // depth on target (mdx_depth_regions), laid out by the region strata as they stood at the first call; a new
+        // mdx_set_strata_regions, mdx_reset and whatever releases the accumulator release it
+        struct OnTarget {
+            bool on = false;
+            int64_t n_iv = 0;
+            int n_groups = 0, rest_group = 0;
+            int64_t *cols = nullptr;               // gs [n_iv] | ge [n_iv]: the intervals in element coordinates
+            unsigned long long *words = nullptr;   // per_iv [n_iv][4] | ghist [n_groups][1024] | rest [4]
+            std::vector<int64_t> span;             // [n_iv] the bases of each, on the host ...
+            std::vector<int32_t> group;            // ... and its group
+        } regions;
     } depth;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -341,8 +352,16 @@ int dedup_clear(mdx_ctx *c) {
 #define MDX_DEDUP_MAX_SLOTS ((uint64_t)1 << 31)    // a slot's index is kept in 32 bits per record of the batch
 
 // ---- depth of coverage: the context's side (the launches: mdx_depth.hip)
+void depth_regions_release(mdx_ctx *c) {
+    auto &r = c->depth.regions;
+    if (r.cols) (void)hipFree(r.cols);
+    if (r.words) (void)hipFree(r.words);
+    r = mdx_ctx::Depth::OnTarget{};
+}
+size_t depth_regions_words(const mdx_ctx::Depth::OnTarget &r) { return (size_t)r.n_iv * 4 + (size_t)r.n_groups * MDX_DEPTH_HIST_BINS + 4; }
 void depth_release(mdx_ctx *c) {
     auto &d = c->depth;
+    depth_regions_release(c);
     void *ptrs[] = {d.diff, d.tile_sum, d.tile_runs, d.words};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     d = mdx_ctx::Depth{};
@@ -1457,6 +1476,7 @@ int mdx_reset(mdx_ctx *c) {
     if (c->dedup.on && (rc = dedup_clear(c)) != MDX_OK) return rc;
     if (c->depth.on && (rc = depth_clear(c)) != MDX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    depth_regions_release(c);
     dedup_free_retired(c);
     c->err.clear();
     c->counted = false;
@@ -1778,6 +1798,105 @@ int mdx_depth_fetch(mdx_ctx *c, int32_t tid, int64_t start, int64_t end, uint32_
     return MDX_OK;
 }
 
+// What mdx_depth_regions keeps from call to call: the strata's intervals read back, held to the sequences' lengths, and
+// their columns in the accumulator's element coordinates; the words the pass writes.
+static int depth_regions_prepare(mdx_ctx *c) {
+    auto &r = c->depth.regions;
+    if (r.on) return MDX_OK;
+    const auto &st = c->strata;
+    if (st.strata_n_contig != c->n_contig)
+        return fail(c, MDX_ERR_ARG, "mdx_depth_regions: mdx_set_strata_regions named " + std::to_string(st.strata_n_contig) +
+                                    " sequences, the reference has " + std::to_string(c->n_contig));
+    const size_t nc = (size_t)c->n_contig;
+    const std::vector<int64_t> &off = c->depth.off;
+    std::vector<int64_t> iv_off(nc + 1), cols;
+    std::vector<int32_t> start, end;
+    HIP_TRY(c, hipMemcpy(iv_off.data(), st.regions.iv_off, (nc + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t n_iv = iv_off[nc];
+    try {
+        start.resize((size_t)n_iv); end.resize((size_t)n_iv); cols.resize(2 * (size_t)n_iv);
+        r.span.resize((size_t)n_iv); r.group.resize((size_t)n_iv);
+    } catch (const std::bad_alloc &) {
+        depth_regions_release(c);
+        return fail(c, MDX_ERR_ARG, "mdx_depth_regions: out of host memory");
+    }
+    if (n_iv > 0) {
+        HIP_TRY(c, hipMemcpy(start.data(), st.regions.iv_start, (size_t)n_iv * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(end.data(), st.regions.iv_end, (size_t)n_iv * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(r.group.data(), st.regions.iv_group, (size_t)n_iv * 4, hipMemcpyDeviceToHost));
+    }
+    for (size_t t = 0; t < nc; t++)
+        for (int64_t k = iv_off[t]; k < iv_off[t + 1]; k++) {
+            const int64_t length = off[t + 1] - off[t];
+            if (end[(size_t)k] > length) {
+                depth_regions_release(c);
+                return fail(c, MDX_ERR_ARG, "mdx_depth_regions: interval " + std::to_string(k) + " (sequence " + std::to_string(t) + ", [" +
+                                            std::to_string(start[(size_t)k]) + ", " + std::to_string(end[(size_t)k]) + ")) ends beyond the " +
+                                            std::to_string(length) + " bases of its sequence");
+            }
+            cols[(size_t)k] = off[t] + start[(size_t)k];
+            cols[(size_t)n_iv + (size_t)k] = off[t] + end[(size_t)k];
+            r.span[(size_t)k] = (int64_t)end[(size_t)k] - start[(size_t)k];
+        }
+    r.n_iv = n_iv; r.n_groups = st.n_groups; r.rest_group = st.regions.rest_group;
+    hipError_t e = hipMalloc((void **)&r.words, depth_regions_words(r) * 8);
+    if (e == hipSuccess && n_iv > 0) e = hipMalloc((void **)&r.cols, (size_t)n_iv * 16);
+    if (e == hipSuccess && n_iv > 0) e = hipMemcpy(r.cols, cols.data(), (size_t)n_iv * 16, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        const size_t bytes = depth_regions_words(r) * 8 + (size_t)n_iv * 16;
+        depth_regions_release(c);
+        return fail(c, MDX_ERR_HIP, "mdx_depth_regions: " + std::string(hipGetErrorString(e)) + " (" + std::to_string(bytes) + " bytes for " +
+                                    std::to_string(n_iv) + " intervals and " + std::to_string(st.n_groups) + " groups)");
+    }
+    r.on = true;
+    return MDX_OK;
+}
+
+int mdx_depth_regions(mdx_ctx *c, uint64_t *per_interval, uint64_t *per_group, uint64_t *group_hist) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_regions: call mdx_depth_begin first");
+    if (c->strata.kind != STRATA_REGIONS) return fail(c, MDX_ERR_STATE, "mdx_depth_regions: the context has no region strata (mdx_set_strata_regions)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    if (const int rc = depth_regions_prepare(c); rc != MDX_OK) return rc;
+    auto &d = c->depth;
+    auto &r = d.regions;
+    const size_t n_iv = (size_t)r.n_iv, ng = (size_t)r.n_groups, n_words = depth_regions_words(r);
+    HIP_TRY(c, hipMemsetAsync(r.words, 0, n_words * 8, c->stream));
+    MdxDepthScan a{};
+    a.diff = d.diff; a.G = d.G; a.contig_off = c->d_contig_off; a.n_contig = c->n_contig; a.n_tiles = d.n_tiles; a.round = d.round;
+    a.tile_sum = d.tile_sum; a.tile_runs = d.tile_runs; a.misc = depth_misc(c);
+    mdx_k_depth_finish(a, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    MdxDepthRegions k{};
+    k.gs = r.cols; k.ge = r.cols ? r.cols + n_iv : nullptr; k.grp = c->strata.regions.iv_group; k.n_iv = r.n_iv; k.rest_group = r.rest_group;
+    k.per_iv = r.words; k.ghist = r.words + 4 * n_iv; k.rest = k.ghist + ng * MDX_DEPTH_HIST_BINS;
+    mdx_k_depth_regions(a, k, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<unsigned long long> w;
+    try { w.resize(n_words); } catch (const std::bad_alloc &) { return fail(c, MDX_ERR_ARG, "mdx_depth_regions: out of host memory"); }
+    HIP_TRY(c, hipMemcpyAsync(w.data(), r.words, n_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (per_interval) for (size_t q = 0; q < 4 * n_iv; q++) per_interval[q] = w[q];
+    if (group_hist) for (size_t q = 0; q < ng * MDX_DEPTH_HIST_BINS; q++) group_hist[q] = w[4 * n_iv + q];
+    if (per_group) {
+        // bases, covered, aligned, max: a named group from its intervals, the rest's row also what no interval holds
+        for (size_t q = 0; q < 4 * ng; q++) per_group[q] = 0;
+        uint64_t on_target = 0;
+        for (size_t iv = 0; iv < n_iv; iv++) {
+            uint64_t *row = per_group + 4 * (size_t)r.group[iv];
+            row[0] += (uint64_t)r.span[iv]; row[1] += w[4 * iv]; row[2] += w[4 * iv + 1];
+            row[3] = w[4 * iv + 3] > row[3] ? w[4 * iv + 3] : row[3];
+            on_target += (uint64_t)r.span[iv];
+        }
+        const unsigned long long *rest = w.data() + 4 * n_iv + ng * MDX_DEPTH_HIST_BINS;
+        uint64_t *row = per_group + 4 * (size_t)r.rest_group;
+        row[0] += (uint64_t)d.G - on_target; row[1] += rest[0]; row[2] += rest[1];
+        row[3] = rest[2] > row[3] ? rest[2] : row[3];
+    }
+    return MDX_OK;
+}
+
 int mdx_depth_info(mdx_ctx *c, uint64_t *info) {
     if (!c) return MDX_ERR_ARG;
     if (!c->depth.on) return fail(c, MDX_ERR_STATE, "mdx_depth_info: call mdx_depth_begin first");
@@ -1785,6 +1904,7 @@ int mdx_depth_info(mdx_ctx *c, uint64_t *info) {
     const auto &d = c->depth;
     info[0] = (uint64_t)mdx_k_depth_block(); info[1] = (uint64_t)mdx_k_depth_tile(); info[2] = (uint64_t)d.round;
     info[3] = (uint64_t)d.n_tiles * ((uint64_t)mdx_k_depth_tile() * 4 + 12) + depth_words(c) * 8;
+    if (d.regions.on) info[3] += (uint64_t)d.regions.n_iv * 16 + depth_regions_words(d.regions) * 8;
     return MDX_OK;
 }
 
@@ -1848,6 +1968,7 @@ int mdx_set_strata_regions(mdx_ctx *c, int32_t n_groups, int32_t n_contig, const
                 return fail(c, MDX_ERR_ARG, which + "has group " + std::to_string(iv_group[k]) + ", outside [0, n_groups)");
         }
     if (const int rc = begin_strata(c, STRATA_REGIONS, n_groups); rc != MDX_OK) return rc;
+    depth_regions_release(c);      // (what mdx_depth_regions laid out by the earlier intervals)
     if (c->strata.d_regions) { (void)hipFree(c->strata.d_regions); c->strata.d_regions = nullptr; }
     const size_t off_bytes = ((size_t)(n_contig + 1) * 8 + 15) & ~(size_t)15, col_bytes = ((size_t)n_iv * 4 + 15) & ~(size_t)15;
     HIP_TRY(c, hipMalloc(&c->strata.d_regions, off_bytes + 3 * col_bytes + 64));

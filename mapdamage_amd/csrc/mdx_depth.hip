@@ -1,4 +1,4 @@
-// Depth of coverage on the device (mdx_depth_begin / _add / _finish / _runs; the rule: mdx_depth_key.h).
+// Depth of coverage on the device (mdx_depth_begin / _add / _finish / _runs / _regions; the rule: mdx_depth_key.h).
 //
 // The accumulator is a difference array over the resident reference in its concatenated contig order, one int32 per base and
 // one more: an interval [s, e) of sequence t adds +1 at off[t] + s and -1 at off[t] + e — two atomics per interval, not one
@@ -13,6 +13,9 @@
 //     stats  a fixed grid strides over the tiles; a lane owns MDX_DP_LANE consecutive elements, loaded sixteen bytes at a
 //            time, rebuilds their depths from the tile's prefix and the lanes in front of it and consumes them as runs of
 //            equal depth: per sequence covered / aligned / max, the histogram (in the LDS, depth 0 in registers), the runs
+//   regions  (mdx_depth_regions, behind sums and scan) the stats pass's walk once more, a run also ending where the interval of the
+//            region strata changes: per interval covered / aligned / min / max, per group a histogram in global memory (one
+//            64-bit atomic per run; the bases in no interval: LDS bins and registers, as in stats)
 // The array is allocated in whole tiles and zeroed, so every load is in bounds and aligned; elements from G on (the last -1s
 // and the padding) are read for the sums and never counted as bases.  finish does not modify diff.
 #include "mdx_internal.h"
@@ -297,6 +300,148 @@ __global__ __launch_bounds__(MDX_DP_BLOCK) void depth_stats_kernel(const int32_t
     }
 }
 
+// ---- depth on target (mdx_depth_regions): every base to its interval and group, or to the rest
+// What a lane has gathered for the interval it is in (or, owner < 0, nothing: the rest has its own registers)
+struct IvAcc { uint32_t covered, mn, mx; u64 aligned; };
+
+__device__ __forceinline__ void iv_clear(IvAcc *a) { a->covered = 0; a->mn = 0xFFFFFFFFu; a->mx = 0; a->aligned = 0; }
+
+// per_iv [n_iv][4]: covered, aligned, min, max
+__device__ __forceinline__ void flush_iv(IvAcc *a, u64 *per_iv, int64_t k) {
+    u64 *const row = per_iv + 4 * (size_t)k;
+    if (a->covered) {
+        atomicAdd(&row[0], (u64)a->covered);
+        atomicAdd(&row[1], a->aligned);
+        atomicMax(&row[3], (u64)a->mx);
+    }
+    if (a->mn != 0xFFFFFFFFu) atomicMin(&row[2], (u64)a->mn);
+    iv_clear(a);
+}
+
+// a run of n elements at depth d inside an interval of group row `gh`: the interval's numbers into the lane's registers, the
+// group's bin by one global atomic per run (depth 0: the lane's register, flushed where the interval changes)
+__device__ __forceinline__ void take_run_iv(int32_t d, uint32_t n, u64 *gh, u64 *gzeros, IvAcc *a) {
+    if (n == 0) return;
+    if (d <= 0) { *gzeros += n; a->mn = 0; return; }
+    atomicAdd(&gh[d < MDX_DEPTH_HIST_BINS - 1 ? d : MDX_DEPTH_HIST_BINS - 1], (u64)n);
+    a->covered += n;
+    a->aligned += (u64)(uint32_t)d * n;
+    a->mx = (uint32_t)d > a->mx ? (uint32_t)d : a->mx;
+    a->mn = (uint32_t)d < a->mn ? (uint32_t)d : a->mn;
+}
+
+// the first interval in [lo, hi) whose end lies behind element g (hi where none does)
+__device__ __forceinline__ int64_t iv_behind(const int64_t *ge, int64_t lo, int64_t hi, int64_t g) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (ge[mid] > g) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(MDX_DP_BLOCK) void depth_regions_init_kernel(u64 *per_iv, int64_t n_iv) {
+    const int64_t k = (int64_t)blockIdx.x * MDX_DP_BLOCK + threadIdx.x;
+    if (k < n_iv) per_iv[4 * (size_t)k + 2] = ~0ull;      // (the min: no depth reaches it)
+}
+
+// gs / ge [n_iv]: the intervals in element coordinates, sorted and disjoint over the whole array, every end <= G; grp [n_iv]: a
+// row of ghist each.  per_iv [n_iv][4] (min preset to ~0); ghist [n_groups][1024], the rest's row `rest_group` among them (its
+// bins in the LDS, like depth_stats_kernel's); rest [3]: covered, aligned, max of the bases in no interval.
+__global__ __launch_bounds__(MDX_DP_BLOCK) void depth_regions_kernel(const int32_t *diff, int64_t G, int64_t n_tiles, const int32_t *tile_sum,
+                                                                       const int64_t *gs, const int64_t *ge, const int32_t *grp, int64_t n_iv,
+                                                                       int rest_group, u64 *per_iv, u64 *ghist, u64 *rest) {
+    __shared__ uint32_t bins[MDX_DEPTH_HIST_BINS];
+    __shared__ u64 wave_tot[MDX_DP_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int w = threadIdx.x; w < MDX_DEPTH_HIST_BINS; w += MDX_DP_BLOCK) bins[w] = 0u;
+    __syncthreads();
+    const int64_t NONE = 0x7FFFFFFFFFFFFFFFll;
+    u64 zeros = 0;                      // the rest's bases at depth 0
+    SeqAcc racc{0u, 0u, 0ull};          // the rest's covered / aligned / max: kept over the tiles, flushed once
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t tile0 = tile * MDX_DP_TILE, g0 = tile0 + (int64_t)threadIdx.x * MDX_DP_LANE;
+        Lane16 x;
+        load_lane(diff, g0, &x);
+        int32_t s = 0;
+#pragma unroll
+        for (int j = 0; j < MDX_DP_LANE; j++) s += x.v[j];
+        const u64 is = wave_incl_scan((u64)(int64_t)s, lane);
+        if (lane == 63) wave_tot[wave] = is;
+        __syncthreads();
+        u64 bs = 0;
+        for (int w = 0; w < wave; w++) bs += wave_tot[w];
+        int32_t d = tile_sum[tile] + (int32_t)(int64_t)(bs + is) - s;
+        // the tile's first interval (the same search in every lane); this lane's from there, searched only where the tile holds
+        // the end of one (at most a tile's elements of them lie in front of the lane)
+        const int64_t k_tile = iv_behind(ge, 0, n_iv, tile0);
+        int64_t k = k_tile;
+        if (k_tile < n_iv && ge[k_tile] < tile0 + MDX_DP_TILE && g0 > tile0)
+            k = iv_behind(ge, k_tile, k_tile + MDX_DP_TILE < n_iv ? k_tile + MDX_DP_TILE : n_iv, g0);
+        int64_t cur_s = k < n_iv ? gs[k] : NONE, cur_e = k < n_iv ? ge[k] : NONE;
+        int64_t owner = -1;             // the interval the lane is in, -1: none
+        u64 *gh = ghist;                // ... and its group's row
+        u64 gzeros = 0;
+        IvAcc acc;
+        iv_clear(&acc);
+        int32_t run_d = 0;
+        uint32_t run_n = 0;
+#pragma unroll
+        for (int j = 0; j < MDX_DP_LANE; j++) {
+            const int64_t i = g0 + j;
+            if (i >= G) continue;
+            while (i >= cur_e) {        // (one step: the intervals are not empty)
+                k++;
+                cur_s = k < n_iv ? gs[k] : NONE; cur_e = k < n_iv ? ge[k] : NONE;
+            }
+            const int64_t now = i >= cur_s ? k : -1;
+            d += x.v[j];
+            if (now != owner || d != run_d) {
+                if (owner < 0) take_run(run_d, run_n, bins, &zeros, &racc); else take_run_iv(run_d, run_n, gh, &gzeros, &acc);
+                run_d = d; run_n = 0;
+            }
+            if (now != owner) {
+                if (owner >= 0) {
+                    flush_iv(&acc, per_iv, owner);
+                    if (gzeros) { atomicAdd(&gh[0], gzeros); gzeros = 0; }
+                }
+                owner = now;
+                if (now >= 0) gh = ghist + (size_t)grp[now] * MDX_DEPTH_HIST_BINS;
+            }
+            run_n++;
+        }
+        if (owner < 0) take_run(run_d, run_n, bins, &zeros, &racc); else take_run_iv(run_d, run_n, gh, &gzeros, &acc);
+        // what the lane still holds for its last interval: one set of atomics for the wavefront where its lanes end in the same one
+        // (a target wider than a wavefront's 1024 elements), a lane each otherwise
+        const int64_t o0 = __shfl(owner, 0, 64);
+        if (__ballot(owner != o0) == 0) {
+            if (o0 >= 0) {
+                const u64 c = wave_sum_u64((u64)acc.covered), a = wave_sum_u64(acc.aligned), z = wave_sum_u64(gzeros);
+                const uint32_t m = wave_max_u32(acc.mx), n = ~wave_max_u32(~acc.mn);
+                if (lane == 0) {
+                    IvAcc all{(uint32_t)c, n, m, a};
+                    flush_iv(&all, per_iv, o0);
+                    if (z) atomicAdd(&gh[0], z);
+                }
+            }
+        } else if (owner >= 0) {
+            flush_iv(&acc, per_iv, owner);
+            if (gzeros) atomicAdd(&gh[0], gzeros);
+        }
+        __syncthreads();
+    }
+    // (the LDS bins: the atomics of every lane's runs are behind the loop's last barrier)
+    u64 *const rh = ghist + (size_t)rest_group * MDX_DEPTH_HIST_BINS;
+    for (int w = threadIdx.x; w < MDX_DEPTH_HIST_BINS; w += MDX_DP_BLOCK)
+        if (bins[w]) atomicAdd(&rh[w], (u64)bins[w]);
+    zeros = wave_sum_u64(zeros);
+    const u64 rc = wave_sum_u64((u64)racc.covered), ra = wave_sum_u64(racc.aligned);
+    const uint32_t rm = wave_max_u32(racc.mx);
+    if (lane == 0) {
+        if (zeros) atomicAdd(&rh[0], zeros);
+        if (rc) { atomicAdd(&rest[0], rc); atomicAdd(&rest[1], ra); atomicMax(&rest[2], (u64)rm); }
+    }
+}
+
 }  // namespace
 
 void mdx_k_depth_add(const MdxDepthKey &k, int32_t *diff, unsigned long long *counts, unsigned long long *seq_records, hipStream_t s) {
@@ -315,4 +460,12 @@ void mdx_k_depth_stats(const MdxDepthScan &a, hipStream_t s) {
     const unsigned grid = a.n_tiles < MDX_DP_STATS_GRID ? (unsigned)a.n_tiles : MDX_DP_STATS_GRID;
     depth_stats_kernel<<<grid, MDX_DP_BLOCK, 0, s>>>(a.diff, a.G, a.contig_off, a.n_contig, a.n_tiles, a.tile_sum, a.tile_runs, a.res, a.hist, a.misc,
                                                      a.run_pos, a.run_depth, a.run_cap);
+}
+
+void mdx_k_depth_regions(const MdxDepthScan &a, const MdxDepthRegions &r, hipStream_t s) {
+    if (a.n_tiles <= 0) return;
+    if (r.n_iv > 0)
+        depth_regions_init_kernel<<<(unsigned)((r.n_iv + MDX_DP_BLOCK - 1) / MDX_DP_BLOCK), MDX_DP_BLOCK, 0, s>>>(r.per_iv, r.n_iv);
+    const unsigned grid = a.n_tiles < MDX_DP_STATS_GRID ? (unsigned)a.n_tiles : MDX_DP_STATS_GRID;
+    depth_regions_kernel<<<grid, MDX_DP_BLOCK, 0, s>>>(a.diff, a.G, a.n_tiles, a.tile_sum, r.gs, r.ge, r.grp, r.n_iv, r.rest_group, r.per_iv, r.ghist, r.rest);
 }

@@ -527,6 +527,18 @@ int64_t mdx_k_depth_round();        // tiles a round of the one-block scan takes
 void mdx_k_depth_add(const MdxDepthKey &k, int32_t *diff, unsigned long long *counts, unsigned long long *seq_records, hipStream_t s);
 void mdx_k_depth_finish(const MdxDepthScan &a, hipStream_t s);      // sums and scan
 void mdx_k_depth_stats(const MdxDepthScan &a, hipStream_t s);       // the third pass
+// depth on target (mdx_depth_regions): the region strata's intervals in the accumulator's element coordinates, off[t] + start and
+// off[t] + end — sorted and disjoint over the whole array, every end <= G (the caller has checked) —, and what the pass gathers
+struct MdxDepthRegions {
+    const int64_t *gs, *ge;         // [n_iv]
+    const int32_t *grp;             // [n_iv] the group of each: a row of ghist
+    int64_t n_iv;
+    int rest_group;                 // the row of ghist the bases in no interval go to
+    unsigned long long *per_iv;     // [n_iv][4]: covered, aligned, min, max
+    unsigned long long *ghist;      // [n_groups][MDX_DEPTH_HIST_BINS]
+    unsigned long long *rest;       // [3]: covered, aligned, max of the bases in no interval
+};
+void mdx_k_depth_regions(const MdxDepthScan &a, const MdxDepthRegions &r, hipStream_t s);   // behind mdx_k_depth_finish: presets and the pass
 
 // ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
 #include "mdx_filter.h"

@@ -54,7 +54,7 @@ EXPORTS = (
     "mdx_bam_apply_record_filter", "mdx_gbam_set_record_filter", "mdx_gbam_filter_counts", "mdx_gsam_set_record_filter",
     "mdx_gsam_filter_counts",
     "mdx_dedup_begin", "mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info",
-    "mdx_depth_begin", "mdx_depth_add", "mdx_depth_finish", "mdx_depth_runs", "mdx_depth_fetch", "mdx_depth_info",
+    "mdx_depth_begin", "mdx_depth_add", "mdx_depth_finish", "mdx_depth_runs", "mdx_depth_fetch", "mdx_depth_info", "mdx_depth_regions",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -219,6 +219,7 @@ def load_library(path=None):
                                    ctypes.c_void_p]
     lib.mdx_depth_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     lib.mdx_depth_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_depth_regions.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -389,6 +390,7 @@ class DamageEngine:
         self._check(self._lib.mdx_set_strata_regions(self._ctx, ctypes.c_int32(len(self.groups)), ctypes.c_int32(off.shape[0] - 1),
                                                      _ptr(off), _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), ctypes.c_int32(rest)))
         self.strata_kind = "regions"
+        self._n_intervals = int(cols[0].shape[0])
 
     DAMAGE_GROUPS = ["none", "5p", "3p", "both"]
 
@@ -553,6 +555,19 @@ class DamageEngine:
         out = np.zeros(4, np.uint64)
         self._check(self._lib.mdx_depth_info(self._ctx, _ptr(out)))
         return dict(zip(("block_records", "tile", "round_tiles", "bytes"), (int(x) for x in out)))
+
+    def depth_regions(self):
+        """``(per_interval, per_group, group_hist)`` (``mdx_depth_regions``): the depth parted by the intervals of
+        ``set_strata_regions``, base by base.  uint64 [intervals][4] — covered bases, aligned bases, smallest and largest
+        depth —, uint64 [groups][4] — bases, covered, aligned, largest depth, the rest group's row also what no interval
+        holds — and uint64 [groups][1024], a group's bases at depth ``d`` binned as ``depth_finish`` bins."""
+        n_iv, n_groups = getattr(self, "_n_intervals", 0), len(self.groups or ())
+        per_interval = np.zeros((n_iv, 4), np.uint64)
+        per_group = np.zeros((n_groups, 4), np.uint64)
+        group_hist = np.zeros((n_groups, self.DEPTH_BINS), np.uint64)
+        self._check(self._lib.mdx_depth_regions(self._ctx, _ptr(per_interval) if n_iv else None, _ptr(per_group) if n_groups else None,
+                                                _ptr(group_hist) if n_groups else None))
+        return per_interval, per_group, group_hist
 
     def set_reference(self, ref):
         """``ref``: a ``Reference`` (contigs in host memory) or a ``fasta.FastaOnDisk`` — the FASTA file itself, which the

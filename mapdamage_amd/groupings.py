@@ -75,6 +75,11 @@ class RegionGroups(Kind):
         # (--only-regions: the usual files from the named groups alone, summed on the host; by_region/ keeps '*')
         usual = tables.sum_of_groups(range(len(names) - 1)) if options.only_regions else None
         tables.write(options.folder, subdir=self.directory, groups_text=text, usual=usual)
+        if getattr(options, "depth_regions_result", None) is not None:
+            # (--depth-regions: the depth parted by the same intervals, beside groups.tsv)
+            from . import depth
+            depth.write_region_files(options.folder / self.directory, options.depth_result[0], names, r, options.depth_regions_result,
+                                     options.depth_thresholds)
         return tables.merged if usual is None else usual
 
 

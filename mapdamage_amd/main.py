@@ -282,6 +282,17 @@ def build_parser():
     g.add_argument("--depth-bedgraph", metavar="PATH", default=None,
                    help="with --depth: the stretches of equal depth above 0 as `name start end depth` lines, what `bedtools "
                         "genomecov -bg` writes; written under a temporary name and moved into place at the end")
+    g.add_argument("--depth-regions", action="store_true", default=False,
+                   help="with --depth and --regions / --region-groups: the depth on target, from the same pass.  Every reference "
+                        "base belongs to the region that holds it (after the merging of a group's overlapping and abutting "
+                        "regions) and to that region's group, or to '*' — base by base, so a read that hangs over a region's edge "
+                        "adds its outside bases to '*', whichever group its record is counted in.  by_region/ gets coverage.tsv "
+                        "(per group: bases, covered, breadth, aligned bases, mean and largest depth), depth_histogram.tsv and "
+                        "depth_thresholds.tsv (per group) and regions_depth.tsv (a line per region: what `samtools bedcov` or "
+                        "`mosdepth --by` give)")
+    g.add_argument("--depth-thresholds", metavar="T[,T...]", default=None,
+                   help="with --depth-regions: the depths T for which depth_thresholds.tsv gives the bases at depth >= T; strictly "
+                        "increasing integers in 1..1022, at most 32 (default: 1,5,10,20)")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -435,9 +446,20 @@ def _check_remove_duplicates(parser, o):
 
 
 def _check_depth(parser, o):
-    """The argument errors of --depth / --depth-bedgraph."""
+    """The argument errors of --depth / --depth-bedgraph / --depth-regions / --depth-thresholds."""
     if o.depth_bedgraph is not None and not o.depth:
         parser.error("--depth-bedgraph needs --depth: it writes the runs of the depth that option gathers")
+    if o.depth_thresholds is not None and not o.depth_regions:
+        parser.error("--depth-thresholds needs --depth-regions: it chooses the lines of that option's depth_thresholds.tsv")
+    if o.depth_regions:
+        if not o.depth:
+            parser.error("--depth-regions needs --depth: it parts the depth that option gathers")
+        if not (o.regions or o.region_groups):
+            parser.error("--depth-regions needs --regions or --region-groups: the regions it parts the depth by")
+        try:
+            o.depth_thresholds = depth_files.parse_thresholds(o.depth_thresholds)
+        except ValueError as error:
+            parser.error(str(error))
     if not o.depth:
         return
     if o.rescale_only or o.stats_only:
@@ -1168,6 +1190,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             if depth:
                 options.depth_result = (list(ref.names), [int(x) for x in ref.lengths]) + engine.depth_finish() + (
                     engine.depth_runs() if options.depth_bedgraph is not None else None, engine.depth_info())
+                if getattr(options, "depth_regions", False):
+                    options.depth_regions_result = engine.depth_regions()
             if kept_out is not None:
                 kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
@@ -1243,6 +1267,9 @@ def _report_depth(options, logger):
     if runs is not None:
         depth_files.write_bedgraph(options.depth_bedgraph, names, *runs)
     logger.info(depth_files.log_line(lengths, per_contig, counts))
+    if getattr(options, "depth_regions_result", None) is not None:
+        # (its four files are by_region/'s: groupings.RegionGroups.write)
+        logger.info(depth_files.region_log_line(options.depth_regions_result[1]))
     logger.debug("Depth: %d intervals, %d runs of depth > 0; %d bytes of HBM", counts["intervals"], counts["runs"], info["bytes"])
 
 

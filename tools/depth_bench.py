@@ -9,12 +9,17 @@ as cold processes, each under a time limit of its own, alternating:
   depth_bedgraph  `--depth --depth-bedgraph x.bg`                    (behind the alternation: the finish's launches a second
                                                                      time, the runs to the host, the file's text)
 
+With --targets N:WIDTH[,N:WIDTH...] a synthetic BED per entry — N targets of WIDTH bases spread evenly over the genome, one
+group — and, in the same alternation, `regions_plain` (`--depth --regions`, on the parent's build too: `parent_regions_plain`)
+and per BED `on_target_NxWIDTH` (`--depth --regions BED --depth-regions`); `regions_plain` uses the first BED.
+
 Reported per command: the wall times, their median and spread (max - min); depth - plain, dedup_depth - plain and
 plain - parent_plain (medians); from the log and coverage.tsv the records, the aligned and covered bases, the intervals, the
 runs and the HBM the accumulator holds.  The claim to check: depth - plain is within the repeats' spread, and so is
 plain - parent_plain.  One JSON line on stdout.
 
-    python tools/depth_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR]"""
+    python tools/depth_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR]
+                                [--targets N:WIDTH[,N:WIDTH...]]"""
 import argparse
 import json
 import os
@@ -31,6 +36,22 @@ sys.path.insert(0, ROOT)
 from tools.write_kept_bench import FILES, timed     # noqa: E402
 
 
+def write_targets(path, ref, n, width):
+    """``n`` targets of ``width`` bases, spread evenly over the sequences in proportion to their lengths (rounded down), apart from each other."""
+    total = sum(int(x) for x in ref.lengths)
+    with open(path, "w") as out:
+        for name, length in zip(ref.names, ref.lengths):
+            share = n * int(length) // total
+            if share == 0:          # (a sequence too short for a target of its own gets none)
+                continue
+            step = int(length) // share
+            if step <= width:
+                raise SystemExit("--targets %d:%d: the targets of %s would touch" % (n, width, name))
+            for k in range(share):
+                out.write("%s\t%d\t%d\n" % (name, k * step, k * step + width))
+    return path
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=8_000_000)
@@ -40,6 +61,7 @@ def main():
     ap.add_argument("--dir", help="where the BAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
+    ap.add_argument("--targets", help="N:WIDTH[,N:WIDTH...]: a synthetic BED of N targets of WIDTH bases each; times --depth-regions with every one")
     args = ap.parse_args()
     import numpy as np
 
@@ -67,6 +89,15 @@ def main():
         if args.parent_root:
             legs.append(("parent_plain", os.path.abspath(args.parent_root), []))
         legs += [("depth", ROOT, ["--depth"]), ("dedup_depth", ROOT, ["--remove-duplicates", "--depth"])]
+        beds = []
+        for entry in (args.targets.split(",") if args.targets else []):
+            n, width = (int(x) for x in entry.split(":"))
+            beds.append(("%dx%d" % (n, width), write_targets(os.path.join(work, "targets_%dx%d.bed" % (n, width)), ref, n, width)))
+        if beds:
+            legs.append(("regions_plain", ROOT, ["--depth", "--regions", beds[0][1]]))
+            if args.parent_root:
+                legs.append(("parent_regions_plain", os.path.abspath(args.parent_root), ["--depth", "--regions", beds[0][1]]))
+            legs += [("on_target_" + name, ROOT, ["--depth", "--regions", bed, "--depth-regions"]) for name, bed in beds]
         # (behind the alternation, on its own: a leg that writes a file of its size would sit in front of `plain` in every round)
         bedgraph = ("depth_bedgraph", ROOT, ["--depth", "--depth-bedgraph", os.path.join(work, "x.bg")])
         times = {name: [] for name, _, _ in legs + [bedgraph]}
@@ -101,6 +132,14 @@ def main():
         if status == 0:
             for name in ("depth", "dedup_depth", "depth_bedgraph"):
                 result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            for name, bed in beds:
+                leg = result["on_target_" + name]
+                leg["minus_regions_plain_s"] = round(leg["median_s"] - result["regions_plain"]["median_s"], 3)
+                leg["targets"] = sum(1 for _ in open(bed))
+                leg["regions_depth_bytes"] = os.path.getsize(os.path.join(work, "on_target_" + name, "by_region", "regions_depth.tsv"))
+                leg["log_line"] = re.search(r"Depth on target: .*", open(os.path.join(work, "on_target_" + name, "Runtime_log.txt")).read()).group(0)
+            if beds and args.parent_root:
+                result["regions_plain_minus_parent_regions_plain_s"] = round(result["regions_plain"]["median_s"] - result["parent_regions_plain"]["median_s"], 3)
             if args.parent_root:
                 result["plain_minus_parent_plain_s"] = round(result["plain"]["median_s"] - result["parent_plain"]["median_s"], 3)
                 result["depth_minus_parent_plain_s"] = round(result["depth"]["median_s"] - result["parent_plain"]["median_s"], 3)
