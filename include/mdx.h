@@ -492,6 +492,68 @@ int mdx_depth_info(mdx_ctx *ctx, uint64_t *info /* [4] */);
 int mdx_depth_regions(mdx_ctx *ctx, uint64_t *per_interval /* [n_iv][4] */, uint64_t *per_group /* [n_groups][4] */,
                       uint64_t *group_hist /* [n_groups][1024] */);
 
+/* ---- Allele counts and pseudo-haploid calls at listed sites, gathered beside the tabulation: what `samtools mpileup -l panel |
+ * pileupCaller` makes of the file the run would otherwise have to write first (the rule: csrc/mdx_pileup_key.h).
+ *
+ * A record is COUNTED, OUTSIDE or ignored exactly as for mdx_depth_add.  The sites of a counted record are those of its tid with
+ * 0-based position in [pos, pos + refspan); one walk of the CIGAR finds the operation that holds the site.  Under M, = or X the
+ * site has a query base, which goes to the first of: Masked (inside the first mask5 query bases of the molecule's 5' end or the
+ * last mask3 of its 3' end — the windows of mdx_gbam_set_kept_mask in mode MDX_MASK_ALL), Other (not exactly A, C, G or T; the
+ * complemented nibbles of MDX_SEQ_4BITQ too), LowQual (the record has qualities and the base's is below min_basequal), or one
+ * of eight base x strand counters, the base as stored and the strand by FLAG & 0x10.  Under D the site adds to Deletions, under
+ * N nothing.  Twelve uint32 counters per site: A+ C+ G+ T+ A- C- G- T- Deletions LowQual Other Masked.  Libraries and groups
+ * are summed.
+ *
+ * The call is a function of a site's counters, seed, tid and position alone — the same in one batch and in many, under any
+ * schedule: the eligible counts are the two strands summed, with alleles only those of ref and alt, with single_strand only the
+ * - strand's at a {C, T} site and only the + strand's at a {G, A} site (pileupCaller --singleStrandMode); fewer than min_depth
+ * eligible bases: N.  z = the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * ((tid << 32 | position) + 1).  RANDOM: the
+ * first base in A C G T order whose cumulative eligible count exceeds z % total.  MAJORITY: the base with the most eligible
+ * bases, among k tied ones number z % k of them in A C G T order.
+ *
+ *   mdx_pileup_begin   after the reference is resident (else MDX_ERR_STATE): site_pos [site_off[n_contig]] 0-based, strictly
+ *                      increasing inside a sequence's slice [site_off[t], site_off[t + 1]) and below that sequence's length;
+ *                      alleles [n_sites][2] (ref, alt as 0 .. 3 for A C G T, different) or NULL.  MDX_ERR_ARG, naming the
+ *                      site, for an unsorted, repeated or out-of-range one; for n_contig other than the reference's, no site,
+ *                      2^31 sites or more, or a config outside its ranges (single_strand needs alleles).  Uploads the sites
+ *                      and allocates the zeroed counters, 48 bytes per site (58 MB for a panel of 1.2 M sites); an allocation
+ *                      that fails is MDX_ERR_HIP with the size.  A second call releases the first one's sites and counters: it
+ *                      starts from zero.  A new reference releases them too: begin again.
+ *   mdx_pileup_add     enqueued on the context's stream: the (record, site) pairs of a device batch's counted records, one
+ *                      atomic each.  Reads flag, lib, tid, pos, the CIGAR and SEQ (all three forms) and, with min_basequal
+ *                      above 0, the quality column if the batch brings one; writes nothing of the batch.  MDX_ERR_STATE
+ *                      without mdx_pileup_begin.
+ *   mdx_pileup_finish  synchronous; one launch (a lane per site) that leaves the counters as they are: it may be called again,
+ *                      and more batches added behind it.  counters [n_sites][12]; refbase [n_sites]: the resident reference's
+ *                      letter at the site, N for one that is not A, C, G or T; call [n_sites]: A C G T N ('.' under
+ *                      MDX_PILEUP_CALL_NONE); depth [n_sites]: the sum of the eight base counters; counts [4]: counted records,
+ *                      outside records, records over at least one site, pairs.  Any pointer may be NULL.
+ *   mdx_pileup_info    info[0] pairs the add kernel's LDS list holds in a round, [1] records a block of it takes, [2] bytes
+ *                      of HBM held, [3] sites.
+ * mdx_reset zeroes the counters, mdx_destroy frees them.  MDX_TEST_PILEUP_LIST=<pairs> in the environment, read at
+ * mdx_pileup_begin: a smaller info[0], for tests of the list's round boundary.
+ *
+ * Limit: a counter is a uint32 and a record adds at most one to it, so fewer than 2^31 records are added between
+ * mdx_pileup_begin (or mdx_reset) and the end — added, whether counted or not, which the host knows without a readback.  The
+ * mdx_pileup_add that would pass it returns MDX_ERR_ARG and adds nothing; the batches before it stand. */
+#define MDX_PILEUP_CALL_NONE 0
+#define MDX_PILEUP_CALL_RANDOM 1
+#define MDX_PILEUP_CALL_MAJORITY 2
+typedef struct {
+    int32_t min_basequal;  /* 0..93 */
+    int32_t mask5, mask3;  /* 0..255 query bases at the molecule's 5' and 3' end */
+    int32_t call;          /* MDX_PILEUP_CALL_* */
+    int32_t min_depth;     /* >= 1 */
+    int32_t single_strand; /* 0 or 1; 1 needs alleles */
+    uint64_t seed;
+} mdx_pileup_config;
+int mdx_pileup_begin(mdx_ctx *ctx, const mdx_pileup_config *config, const int32_t *site_pos, const int64_t *site_off /* [n_contig + 1] */,
+                     int32_t n_contig, const uint8_t *alleles /* [n_sites][2] or NULL */);
+int mdx_pileup_add(mdx_ctx *ctx, const mdx_batch *device_batch);
+int mdx_pileup_finish(mdx_ctx *ctx, uint32_t *counters /* [n_sites][12] */, uint8_t *refbase, uint8_t *call, uint32_t *depth /* [n_sites] each */,
+                      uint64_t *counts /* [4] */);
+int mdx_pileup_info(mdx_ctx *ctx, uint64_t *info /* [4] */);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

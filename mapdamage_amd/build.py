@@ -8,8 +8,8 @@ import subprocess
 HERE = pathlib.Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libmdx.so"
-SOURCES = ["mdx_kernels.hip", "mdx_rescale.hip", "mdx_capi.cpp", "mdx_bamio.cpp", "mdx_gbam.hip", "mdx_samio.cpp", "mdx_gsam.hip", "mdx_libsort.hip", "mdx_strata.hip", "mdx_fasta.hip", "mdx_stats.hip", "mdx_dedup.hip", "mdx_depth.hip"]
-HEADERS = [CSRC / "mdx_internal.h", CSRC / "mdx_filter.h", CSRC / "mdx_damage_key.h", CSRC / "mdx_pmd_key.h", CSRC / "mdx_dup_key.h", CSRC / "mdx_dup_table.h", CSRC / "mdx_depth_key.h", CSRC / "mdx_kept.h", CSRC / "mdx_kept_tags.h", CSRC / "mdx_kept_index.h", CSRC / "mdx_kept_mask.h", CSRC / "mdx_kept_md.h", CSRC / "mdx_device.h", CSRC / "mdx_inflate.h", CSRC / "mdx_deflate.h", CSRC / "mdx_crc32.h", HERE.parent / "include" / "mdx.h"]
+SOURCES = ["mdx_kernels.hip", "mdx_rescale.hip", "mdx_capi.cpp", "mdx_bamio.cpp", "mdx_gbam.hip", "mdx_samio.cpp", "mdx_gsam.hip", "mdx_libsort.hip", "mdx_strata.hip", "mdx_fasta.hip", "mdx_stats.hip", "mdx_dedup.hip", "mdx_depth.hip", "mdx_pileup.hip"]
+HEADERS = [CSRC / "mdx_internal.h", CSRC / "mdx_filter.h", CSRC / "mdx_damage_key.h", CSRC / "mdx_pmd_key.h", CSRC / "mdx_dup_key.h", CSRC / "mdx_dup_table.h", CSRC / "mdx_depth_key.h", CSRC / "mdx_pileup_key.h", CSRC / "mdx_kept.h", CSRC / "mdx_kept_tags.h", CSRC / "mdx_kept_index.h", CSRC / "mdx_kept_mask.h", CSRC / "mdx_kept_md.h", CSRC / "mdx_device.h", CSRC / "mdx_inflate.h", CSRC / "mdx_deflate.h", CSRC / "mdx_crc32.h", HERE.parent / "include" / "mdx.h"]
 
 
 def hipcc():

@@ -224,6 +224,21 @@ struct mdx_ctx {
             std::vector<int32_t> group;            // ... and its group
         } regions;
     } depth;
+    // allele counts at listed sites (mdx_pileup_begin): the sites, their counters and the counters of the adds.  Nothing of it
+    // exists before mdx_pileup_begin; a new reference releases it (the sites were held to that reference's lengths).
+    struct Pileup {
+        bool on = false;
+        int64_t n_sites = 0;
+        bool has_alleles = false;
+        int32_t *site_pos = nullptr;           // [n_sites]
+        int64_t *site_off = nullptr;           // [n_contig + 1]
+        uint8_t *alleles = nullptr;            // [n_sites][2] or null
+        uint32_t *counters = nullptr;          // [n_sites][12]
+        unsigned long long *counts = nullptr;  // [4]: counted, outside, records over a site, pairs
+        int list = 0;                          // pairs a round of the add kernel's LDS list takes
+        uint64_t added = 0;                    // records of the batches added, known without a readback
+        mdx_pileup_config cfg{};
+    } pileup;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
     int64_t n_libsorts = 0;        // sorts done inside a launch so far (a resident batch brings its own: mdx_batch::libsort)
@@ -380,6 +395,22 @@ int depth_clear(mdx_ctx *c) {
     d.added = 0;
     return MDX_OK;
 }
+
+// ---- allele counts at listed sites: the context's side (the launches: mdx_pileup.hip)
+void pileup_release(mdx_ctx *c) {
+    auto &p = c->pileup;
+    void *ptrs[] = {p.site_pos, p.site_off, p.alleles, p.counters, p.counts};
+    for (void *q : ptrs) if (q) (void)hipFree(q);
+    p = mdx_ctx::Pileup{};
+}
+// the counters zeroed (enqueued)
+int pileup_clear(mdx_ctx *c) {
+    auto &p = c->pileup;
+    HIP_TRY(c, hipMemsetAsync(p.counters, 0, (size_t)p.n_sites * MDX_PILEUP_COUNTERS * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(p.counts, 0, 4 * 8, c->stream));
+    p.added = 0;
+    return MDX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -533,6 +564,7 @@ void mdx_destroy(mdx_ctx *c) {
     if (c->gbam_event) (void)hipEventDestroy((hipEvent_t)c->gbam_event);
     dedup_release(c);
     depth_release(c);
+    pileup_release(c);
     c->lists.release();
     c->unpacked.release();
     c->lowq.release();
@@ -574,6 +606,7 @@ static int ref_begin(mdx_ctx *c, int64_t n, int32_t n_contig) {
     if (c->d_ref4) { (void)hipFree(c->d_ref4); c->d_ref4 = nullptr; }
     if (c->d_contig_off) { (void)hipFree(c->d_contig_off); c->d_contig_off = nullptr; }
     depth_release(c);      // (an accumulator is laid out by the reference it was begun on)
+    pileup_release(c);     // (... and the sites were held to its sequences' lengths)
     c->n_contig = 0; c->ref_len = 0;
     HIP_TRY(c, hipMalloc((void **)&c->d_ref, (size_t)n + 2 * kRefPad + 1));
     HIP_TRY(c, hipMalloc((void **)&c->d_contig_off, (size_t)(n_contig + 1) * 8));
@@ -1475,6 +1508,7 @@ int mdx_reset(mdx_ctx *c) {
     if (rc != MDX_OK) return rc;
     if (c->dedup.on && (rc = dedup_clear(c)) != MDX_OK) return rc;
     if (c->depth.on && (rc = depth_clear(c)) != MDX_OK) return rc;
+    if (c->pileup.on && (rc = pileup_clear(c)) != MDX_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     depth_regions_release(c);
     dedup_free_retired(c);
@@ -1905,6 +1939,148 @@ int mdx_depth_info(mdx_ctx *c, uint64_t *info) {
     info[0] = (uint64_t)mdx_k_depth_block(); info[1] = (uint64_t)mdx_k_depth_tile(); info[2] = (uint64_t)d.round;
     info[3] = (uint64_t)d.n_tiles * ((uint64_t)mdx_k_depth_tile() * 4 + 12) + depth_words(c) * 8;
     if (d.regions.on) info[3] += (uint64_t)d.regions.n_iv * 16 + depth_regions_words(d.regions) * 8;
+    return MDX_OK;
+}
+
+int mdx_pileup_begin(mdx_ctx *c, const mdx_pileup_config *cfg, const int32_t *site_pos, const int64_t *site_off, int32_t n_contig,
+                     const uint8_t *alleles) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->d_ref || !c->d_contig_off) return fail(c, MDX_ERR_STATE, "mdx_pileup_begin: mdx_set_reference has not been called");
+    if (!cfg || !site_pos || !site_off) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: null argument");
+    if (n_contig != c->n_contig)
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: site_off is laid out for " + std::to_string(n_contig) + " sequences, the reference has " +
+                                    std::to_string(c->n_contig));
+    if (cfg->min_basequal < 0 || cfg->min_basequal > 93 || cfg->mask5 < 0 || cfg->mask5 > MDX_PILEUP_MAX_K || cfg->mask3 < 0 ||
+        cfg->mask3 > MDX_PILEUP_MAX_K || cfg->call < MDX_PILEUP_CALL_NONE || cfg->call > MDX_PILEUP_CALL_MAJORITY || cfg->min_depth < 1 ||
+        (cfg->single_strand != 0 && cfg->single_strand != 1))
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: config out of range (min_basequal 0..93, mask5 / mask3 0..255, call 0..2, min_depth >= 1, single_strand 0 or 1)");
+    if (cfg->single_strand && !alleles) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: single_strand needs the sites' alleles");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    pileup_release(c);
+    // the sites against the reference's sequences: every slice in order, inside its sequence
+    std::vector<int64_t> off((size_t)n_contig + 1);
+    HIP_TRY(c, hipMemcpy(off.data(), c->d_contig_off, off.size() * 8, hipMemcpyDeviceToHost));
+    if (site_off[0] != 0) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: site_off[0] is not 0");
+    for (int32_t t = 0; t < n_contig; t++)
+        if (site_off[t + 1] < site_off[t]) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: site_off is not monotone at sequence " + std::to_string(t));
+    const int64_t n_sites = site_off[n_contig];
+    if (n_sites < 1) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: no site");
+    if (n_sites >= ((int64_t)1 << 31)) return fail(c, MDX_ERR_ARG, "mdx_pileup_begin: 2^31 sites or more");
+    for (int32_t t = 0; t < n_contig; t++) {
+        const int64_t length = off[(size_t)t + 1] - off[(size_t)t];
+        for (int64_t g = site_off[t]; g < site_off[t + 1]; g++) {
+            auto where = [&] { return "mdx_pileup_begin: site " + std::to_string(g) + " (sequence " + std::to_string(t) + ", position " + std::to_string(site_pos[g]) + ")"; };
+            if (site_pos[g] < 0 || (int64_t)site_pos[g] >= length)
+                return fail(c, MDX_ERR_ARG, where() + " lies outside its sequence of " + std::to_string(length) + " bases");
+            if (g > site_off[t] && site_pos[g] <= site_pos[g - 1])
+                return fail(c, MDX_ERR_ARG, where() + (site_pos[g] == site_pos[g - 1] ? " repeats the site in front of it" : " is not sorted: the site in front of it lies behind it"));
+            if (alleles && (alleles[2 * g] > 3 || alleles[2 * g + 1] > 3 || alleles[2 * g] == alleles[2 * g + 1]))
+                return fail(c, MDX_ERR_ARG, where() + " has alleles that are not two different ones of A C G T (0 .. 3)");
+        }
+    }
+    auto &p = c->pileup;
+    p.n_sites = n_sites;
+    p.has_alleles = alleles != nullptr;
+    p.cfg = *cfg;
+    p.list = mdx_k_pileup_list();
+    // (tests: the list's round boundary out of a few hundred pairs)
+    if (const char *e = getenv("MDX_TEST_PILEUP_LIST"); e && *e) {
+        const long long r = strtoll(e, nullptr, 10);
+        if (r >= 1 && r < p.list) p.list = (int)r;
+    }
+    const size_t bytes = (size_t)n_sites * MDX_PILEUP_COUNTERS * 4;
+    if (hipMalloc((void **)&p.counters, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p.counters = nullptr;
+        pileup_release(c);
+        return fail(c, MDX_ERR_HIP, "mdx_pileup_begin: out of device memory for the counters of " + std::to_string(bytes) + " bytes (48 per site of " +
+                                    std::to_string(n_sites) + ")");
+    }
+    hipError_t e = hipMalloc((void **)&p.site_pos, (size_t)n_sites * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&p.site_off, off.size() * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&p.counts, 4 * 8);
+    if (e == hipSuccess && alleles) e = hipMalloc((void **)&p.alleles, (size_t)n_sites * 2);
+    if (e == hipSuccess) e = hipMemcpy(p.site_pos, site_pos, (size_t)n_sites * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p.site_off, site_off, off.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && alleles) e = hipMemcpy(p.alleles, alleles, (size_t)n_sites * 2, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        pileup_release(c);
+        return fail(c, MDX_ERR_HIP, std::string("mdx_pileup_begin: ") + hipGetErrorString(e));
+    }
+    if (const int rc = pileup_clear(c); rc != MDX_OK) { pileup_release(c); return rc; }
+    p.on = true;
+    return MDX_OK;
+}
+
+static MdxPileupSites pileup_sites(const mdx_ctx *c) {
+    const auto &p = c->pileup;
+    MdxPileupSites st{};
+    st.site_pos = p.site_pos; st.site_off = p.site_off; st.alleles = p.alleles; st.n_sites = p.n_sites; st.counters = p.counters;
+    return st;
+}
+
+int mdx_pileup_add(mdx_ctx *c, const mdx_batch *b) {
+    if (const int rc = check_batch(c, b); rc != MDX_OK) return rc;
+    auto &p = c->pileup;
+    if (!p.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_add: call mdx_pileup_begin first");
+    if (b->n_reads == 0) return MDX_OK;
+    // (a counter is a uint32: the counted records are not known without a readback, the records added bound them)
+    if (p.added + (uint64_t)b->n_reads >= ((uint64_t)1 << 31))
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_add: 2^31 records or more since mdx_pileup_begin; a counter is a uint32");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    MdxPileupKey k{};
+    k.n = b->n_reads; k.n_cigar = b->n_cigar; k.n_bases = b->n_bases;
+    k.flag = b->flag; k.lib = b->lib; k.tid = b->tid; k.pos = b->pos; k.cigar_off = b->cigar_off; k.cigar = b->cigar; k.seq_off = b->seq_off;
+    k.seq = b->seq; k.qual = b->qual; k.seq_packed = b->seq_format != MDX_SEQ_ASCII ? 1 : 0;
+    k.contig_off = c->d_contig_off; k.n_contig = c->n_contig; k.n_libraries = dedup_libraries(c);
+    k.k5 = (uint32_t)p.cfg.mask5; k.k3 = (uint32_t)p.cfg.mask3; k.min_qual = (uint32_t)p.cfg.min_basequal;
+    mdx_k_pileup_add(k, pileup_sites(c), p.list, p.counts, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    p.added += (uint64_t)b->n_reads;
+    return MDX_OK;
+}
+
+int mdx_pileup_finish(mdx_ctx *c, uint32_t *counters, uint8_t *refbase, uint8_t *call, uint32_t *depth, uint64_t *counts) {
+    if (!c) return MDX_ERR_ARG;
+    auto &p = c->pileup;
+    if (!p.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_finish: call mdx_pileup_begin first");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)p.n_sites;
+    DevBuf out;     // refbase [n] | call [n] | padding to 4 | depth [n]
+    const size_t depth_at = (2 * n + 3) / 4 * 4;
+    if (out.reserve(depth_at + 4 * n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MDX_ERR_HIP, "mdx_pileup_finish: out of device memory for " + std::to_string(n) + " sites of 6 bytes");
+    }
+    MdxPileupCall a{};
+    a.mode = p.cfg.call; a.single_strand = p.cfg.single_strand; a.min_depth = (uint32_t)p.cfg.min_depth; a.seed = p.cfg.seed;
+    a.ref = c->d_ref + kRefPad; a.contig_off = c->d_contig_off; a.n_contig = c->n_contig;
+    a.refbase = (uint8_t *)out.p; a.call = (uint8_t *)out.p + n; a.depth = (uint32_t *)((uint8_t *)out.p + depth_at);
+    mdx_k_pileup_call(pileup_sites(c), a, c->stream);
+    hipError_t e = hipGetLastError();
+    unsigned long long w[4] = {0, 0, 0, 0};
+    if (e == hipSuccess && counters) e = hipMemcpyAsync(counters, p.counters, n * MDX_PILEUP_COUNTERS * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && refbase) e = hipMemcpyAsync(refbase, a.refbase, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && call) e = hipMemcpyAsync(call, a.call, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && depth) e = hipMemcpyAsync(depth, a.depth, 4 * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(w, p.counts, sizeof w, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    out.release();
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, MDX_ERR_HIP, std::string("mdx_pileup_finish: ") + hipGetErrorString(e));
+    if (counts) for (int q = 0; q < 4; q++) counts[q] = w[q];
+    return MDX_OK;
+}
+
+int mdx_pileup_info(mdx_ctx *c, uint64_t *info) {
+    if (!c) return MDX_ERR_ARG;
+    if (!c->pileup.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_info: call mdx_pileup_begin first");
+    if (!info) return fail(c, MDX_ERR_ARG, "mdx_pileup_info: null output");
+    const auto &p = c->pileup;
+    info[0] = (uint64_t)p.list; info[1] = (uint64_t)mdx_k_pileup_block();
+    info[2] = (uint64_t)p.n_sites * (MDX_PILEUP_COUNTERS * 4 + 4 + (p.has_alleles ? 2 : 0)) + ((uint64_t)c->n_contig + 1) * 8 + 4 * 8;
+    info[3] = (uint64_t)p.n_sites;
     return MDX_OK;
 }
 

@@ -540,6 +540,31 @@ struct MdxDepthRegions {
 };
 void mdx_k_depth_regions(const MdxDepthScan &a, const MdxDepthRegions &r, hipStream_t s);   // behind mdx_k_depth_finish: presets and the pass
 
+// ---- allele counts at listed sites (mdx_pileup.hip, where the launches are told; the rule: mdx_pileup_key.h)
+#include "mdx_pileup_key.h"
+struct MdxPileupSites {
+    const int32_t *site_pos;        // [n_sites] 0-based, strictly increasing within a sequence, inside it
+    const int64_t *site_off;        // [n_contig + 1] a sequence's slice of site_pos
+    const uint8_t *alleles;         // [n_sites][2] ref, alt as 0 .. 3 for A C G T, or null
+    int64_t n_sites;
+    uint32_t *counters;             // [n_sites][MDX_PILEUP_COUNTERS]
+};
+struct MdxPileupCall {
+    int mode, single_strand;        // MDX_PILEUP_CALL_*
+    uint32_t min_depth;
+    uint64_t seed;
+    const uint8_t *ref;             // the resident reference's first base
+    const int64_t *contig_off;
+    int n_contig;
+    uint8_t *refbase, *call;        // [n_sites] letters: A C G T N (call: '.' under MDX_PILEUP_CALL_NONE)
+    uint32_t *depth;                // [n_sites] the sum of the eight base counters
+};
+int mdx_k_pileup_block();           // records a block of pileup_add_kernel takes
+int mdx_k_pileup_list();            // pairs its LDS list holds at most
+// counts [4]: counted, outside, records with at least one site, pairs; list: the list's capacity in force (1 .. mdx_k_pileup_list())
+void mdx_k_pileup_add(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, hipStream_t s);
+void mdx_k_pileup_call(const MdxPileupSites &st, const MdxPileupCall &a, hipStream_t s);
+
 // ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
 #include "mdx_filter.h"
 

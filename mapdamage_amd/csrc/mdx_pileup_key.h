@@ -1,0 +1,221 @@
+// Allele counts at listed sites (mdx_pileup_begin / mdx_pileup_add / mdx_pileup_finish, --pileup-sites): which records are
+// counted, what a counted record shows at a site it lies over, and the pseudo-haploid call made from a site's counters.  Plain
+// C++, one record or one (record, site) pair per call — pileup_add_kernel (mdx_pileup.hip) gives a lane one of either, and
+// pileup_call_kernel a site; the host compiles the same lines for the rule's CPU test (tests/test_pileup.py).
+//
+// A record is COUNTED, OUTSIDE or IGNORED exactly as mdx_depth_first (mdx_depth_key.h) decides: (FLAG & 0xF04) == 0 on the flag
+// column as it stands, a library the context knows, 0 <= tid < n_contig, pos >= 0, a CIGAR that consumes a reference base and
+// pos + refspan <= the length of sequence tid.  Groups do not part the pileup; libraries are summed.
+//
+// The sites of a counted record are those of its tid with 0-based position p in [pos, pos + refspan).  One walk of the CIGAR
+// finds the operation that holds p: under M, = or X the site has a query base, index q of SEQ; under D it adds to Deletions;
+// under N it adds nothing; I, S, H and P hold no reference base (I and S move q).  The query base is, the first that applies:
+//   Masked    q lies inside the first k5 query bases of the molecule's 5' end or the last k3 of its 3' end.  The query is SEQ
+//             without its terminal soft clips, [qs, qe) as mdx_damage_group and mdx_pmd_open find them; a reverse record
+//             (FLAG & 0x10) is stored reverse-complemented, so its 5' window is the stored query's right end.  These are the
+//             windows [qs, l1) and [r0, qe) of mdx_kept_mask_record (mdx_kept_mask.h) in mode MDX_MASK_ALL with k5, k3: for a
+//             record whose CIGAR's M I S = X lengths sum to its SEQ, the bases masked here are the bases that rule sets to N.
+//   Other     the symbol is not exactly A, C, G or T: in the packed column a nibble other than 1, 2, 4, 8 — the complemented
+//             nibbles of MDX_SEQ_4BITQ among them —; so is a q beyond the record's SEQ (a CIGAR longer than its SEQ).
+//   LowQual   the record has qualities (a quality column exists and the record's first quality byte is not 0xFF) and
+//             qual[q] < min_qual.
+//   base x strand   A+ C+ G+ T+ A- C- G- T-: the base as stored (the reference's orientation), the strand by FLAG & 0x10.
+// Twelve uint32 counters per site, in the order of MDX_PILEUP_*.
+//
+// The call is a function of a site's counters, the seed, tid and p alone (mdx_pileup_call): eligible counts e[A C G T] are the
+// two strands summed; with alleles only ref and alt are eligible; with single_strand a site whose alleles are {C, T} takes only
+// the - strand's counts and one whose alleles are {G, A} only the + strand's.  total = sum e; total < min_depth (or 0): N.
+// z = splitmix64's finaliser over seed + 0x9E3779B97F4A7C15 * (((u64)tid << 32 | (u32)p) + 1).  RANDOM: the first base in A C G T
+// order whose cumulative eligible count exceeds z % total.  MAJORITY: the base of the largest e; among k tied ones number
+// z % k of them in A C G T order.
+//
+// Offsets are clamped to their columns, as the other rules clamp them: no byte outside a column is read.
+#pragma once
+#include <stdint.h>
+#include "mdx_depth_key.h"
+
+#if defined(__HIPCC__)
+#define MDX_PU_FN __host__ __device__ __forceinline__
+#else
+#define MDX_PU_FN static inline
+#endif
+
+#define MDX_PILEUP_COUNTERS 12
+enum { MDX_PILEUP_DELETIONS = 8, MDX_PILEUP_LOWQUAL = 9, MDX_PILEUP_OTHER = 10, MDX_PILEUP_MASKED = 11 };   // 0 .. 7: A+ C+ G+ T+ A- C- G- T-
+#ifndef MDX_PILEUP_CALL_NONE                                   // (include/mdx.h has the three for the callers)
+#define MDX_PILEUP_CALL_NONE 0
+#define MDX_PILEUP_CALL_RANDOM 1
+#define MDX_PILEUP_CALL_MAJORITY 2
+#endif
+#define MDX_PILEUP_NO_CALL 4        // what mdx_pileup_call gives for N; 0 .. 3: A C G T
+#define MDX_PILEUP_MAX_K 255
+#define MDX_PILEUP_NOTHING (-1)     // mdx_pileup_site: the site lies under N (or, by a clamped column, under nothing)
+
+struct MdxPileupKey {
+    int64_t n, n_cigar, n_bases;
+    const uint16_t *flag, *lib;
+    const int32_t *tid, *pos;
+    const uint32_t *cigar_off, *cigar, *seq_off;
+    const uint8_t *seq, *qual;              // qual: may be null
+    int seq_packed;                         // MDX_SEQ_4BIT codes (1 A, 2 C, 4 T, 8 G; MDX_SEQ_4BITQ too) instead of ASCII
+    const int64_t *contig_off;              // [n_contig + 1]
+    int n_contig, n_libraries;
+    uint32_t k5, k3, min_qual;
+};
+
+// what the sites of one record share
+struct MdxPileupRecord {
+    uint32_t c0, c1;            // its operations
+    uint32_t s0, n_seq;         // its first base in the SEQ column, its bases
+    uint32_t qs, l1, r0, qe;    // the stored query's left and right windows, [qs, l1) and [r0, qe) of SEQ (all 0: none)
+    int32_t pos;
+    uint32_t rev, has_qual;
+};
+
+#define MDX_PU_IS_REF(op) ((0x18Du >> (op)) & 1u)     // M D N = X
+#define MDX_PU_IS_ALN(op) ((0x181u >> (op)) & 1u)     // M = X
+#define MDX_PU_IS_QRY(op) ((0x193u >> (op)) & 1u)     // M I S = X
+
+// record i: one of MDX_DEPTH_*; for MDX_DEPTH_COUNTED *r is ready for mdx_pileup_site and *span = its reference bases
+MDX_PU_FN int mdx_pileup_open(const MdxPileupKey &k, int64_t i, MdxPileupRecord *r, int64_t *span_out) {
+    const uint32_t fl = k.flag[i], lib = k.lib[i];
+    if ((fl & 0xF04u) != 0u) return MDX_DEPTH_IGNORED;
+    if (lib >= (uint32_t)k.n_libraries) return MDX_DEPTH_IGNORED;
+    const int32_t t = k.tid[i];
+    const int64_t p = k.pos[i];
+    if (t < 0 || t >= k.n_contig || p < 0) return MDX_DEPTH_OUTSIDE;
+    const uint32_t n_cigar = (uint32_t)k.n_cigar, n_bases = (uint32_t)k.n_bases;
+    uint32_t c0 = k.cigar_off[i], c1 = k.cigar_off[i + 1], s0 = k.seq_off[i], s1 = k.seq_off[i + 1];
+    if (c1 > n_cigar) c1 = n_cigar;
+    if (c0 > c1) c0 = c1;
+    if (s1 > n_bases) s1 = n_bases;
+    if (s0 > s1) s0 = s1;
+    int64_t span = 0;
+    for (uint32_t c = c0; c < c1; c++) {
+        const uint32_t w = k.cigar[c], op = w & 15u;
+        if (MDX_PU_IS_REF(op)) span += (int64_t)(w >> 4);
+    }
+    if (span <= 0) return MDX_DEPTH_OUTSIDE;
+    if (p + span > k.contig_off[t + 1] - k.contig_off[t]) return MDX_DEPTH_OUTSIDE;
+    // the terminal soft clips as mdx_damage_group takes them: a trailing clip is not looked for in the first operation
+    int64_t qs = 0, qe = (int64_t)(s1 - s0);
+    for (uint32_t c = c0; c < c1; c++) {
+        const uint32_t w = k.cigar[c], op = w & 15u;
+        if (op == 5u) continue;
+        if (op != 4u) break;
+        qs += (int64_t)(w >> 4);
+    }
+    for (uint32_t c = c1; c > c0 + 1u; c--) {
+        const uint32_t w = k.cigar[c - 1u], op = w & 15u;
+        if (op == 5u) continue;
+        if (op != 4u) break;
+        qe -= (int64_t)(w >> 4);
+    }
+    r->c0 = c0; r->c1 = c1; r->s0 = s0; r->n_seq = s1 - s0; r->pos = (int32_t)p;
+    r->rev = (fl & 0x10u) ? 1u : 0u;
+    r->has_qual = (k.qual != nullptr && s1 > s0 && k.qual[s0] != 0xFFu) ? 1u : 0u;
+    const int64_t nq = qe - qs;
+    if (nq <= 0) {
+        r->qs = r->l1 = r->r0 = r->qe = 0u;
+    } else {
+        // (0 <= qs < qe <= n_seq: the four fit their 32 bits)
+        const int64_t k_left = r->rev ? (int64_t)k.k3 : (int64_t)k.k5, k_right = r->rev ? (int64_t)k.k5 : (int64_t)k.k3;
+        r->qs = (uint32_t)qs; r->qe = (uint32_t)qe;
+        r->l1 = (uint32_t)(qs + (k_left < nq ? k_left : nq));
+        r->r0 = (uint32_t)(qe - (k_right < nq ? k_right : nq));
+    }
+    *span_out = span;
+    return MDX_DEPTH_COUNTED;
+}
+
+// is base q of the record's SEQ inside one of its windows?
+MDX_PU_FN bool mdx_pileup_masked(const MdxPileupRecord &r, int64_t q) {
+    return (q >= (int64_t)r.qs && q < (int64_t)r.l1) || (q >= (int64_t)r.r0 && q < (int64_t)r.qe);
+}
+
+// base q of the record's SEQ (q < n_seq) as 0 .. 3 for A C G T, 4 for anything else
+MDX_PU_FN uint32_t mdx_pileup_base(const MdxPileupKey &k, const MdxPileupRecord &r, uint32_t q) {
+    const uint32_t b = r.s0 + q;
+    if (k.seq_packed) {
+        const uint32_t nb = ((uint32_t)k.seq[b >> 1] >> (4u * (b & 1u))) & 15u;
+        return nb == 1u ? 0u : nb == 2u ? 1u : nb == 8u ? 2u : nb == 4u ? 3u : 4u;
+    }
+    const uint32_t ch = k.seq[b];
+    return ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
+}
+
+// the counter (0 .. 11) that the site at 0-based position p of the record's sequence takes from the opened record, or
+// MDX_PILEUP_NOTHING; p in [pos, pos + span)
+MDX_PU_FN int mdx_pileup_site(const MdxPileupKey &k, const MdxPileupRecord &r, int64_t p) {
+    int64_t at = r.pos, x = 0;
+    for (uint32_t c = r.c0; c < r.c1; c++) {
+        const uint32_t w = k.cigar[c], op = w & 15u;
+        const int64_t ln = (int64_t)(w >> 4);
+        if (MDX_PU_IS_REF(op)) {
+            if (p < at + ln) {
+                if (p < at) return MDX_PILEUP_NOTHING;
+                if (op == 2u) return MDX_PILEUP_DELETIONS;
+                if (op == 3u) return MDX_PILEUP_NOTHING;
+                const int64_t q = x + (p - at);
+                if (mdx_pileup_masked(r, q)) return MDX_PILEUP_MASKED;
+                if (q >= (int64_t)r.n_seq) return MDX_PILEUP_OTHER;
+                const uint32_t base = mdx_pileup_base(k, r, (uint32_t)q);
+                if (base > 3u) return MDX_PILEUP_OTHER;
+                if (r.has_qual && (uint32_t)k.qual[r.s0 + (uint32_t)q] < k.min_qual) return MDX_PILEUP_LOWQUAL;
+                return (int)(base + 4u * r.rev);
+            }
+            at += ln;
+        }
+        if (MDX_PU_IS_QRY(op)) x += ln;
+    }
+    return MDX_PILEUP_NOTHING;
+}
+
+MDX_PU_FN uint64_t mdx_pileup_z(uint64_t seed, int32_t tid, int64_t p) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * ((((uint64_t)(uint32_t)tid << 32) | (uint64_t)(uint32_t)p) + 1ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the call of a site from its counters: 0 .. 3 for A C G T, MDX_PILEUP_NO_CALL for N.  mode: MDX_PILEUP_CALL_RANDOM or _MAJORITY;
+// ref / alt: 0 .. 3, or both negative for a site without alleles
+MDX_PU_FN uint32_t mdx_pileup_call(const uint32_t *c, int mode, uint64_t seed, uint32_t min_depth, int single_strand, int ref, int alt,
+                                   int32_t tid, int64_t p) {
+    uint64_t e[4];
+    const bool alleles = ref >= 0 && alt >= 0;
+    bool plus = true, minus = true;
+    if (alleles && single_strand) {
+        const int lo = ref < alt ? ref : alt, hi = ref < alt ? alt : ref;
+        if (lo == 1 && hi == 3) plus = false;           // {C, T}: the - strand alone
+        if (lo == 0 && hi == 2) minus = false;          // {G, A}: the + strand alone
+    }
+    uint64_t total = 0;
+    for (int b = 0; b < 4; b++) {
+        e[b] = (plus ? (uint64_t)c[b] : 0ull) + (minus ? (uint64_t)c[4 + b] : 0ull);
+        if (alleles && b != ref && b != alt) e[b] = 0;
+        total += e[b];
+    }
+    if (total == 0 || total < (uint64_t)min_depth) return MDX_PILEUP_NO_CALL;
+    const uint64_t z = mdx_pileup_z(seed, tid, p);
+    if (mode == MDX_PILEUP_CALL_MAJORITY) {
+        uint64_t best = 0;
+        for (int b = 0; b < 4; b++) best = e[b] > best ? e[b] : best;
+        uint32_t ties = 0;
+        for (int b = 0; b < 4; b++) ties += e[b] == best ? 1u : 0u;
+        uint64_t pick = z % ties;
+        for (int b = 0; b < 4; b++)
+            if (e[b] == best) {
+                if (pick == 0) return (uint32_t)b;
+                pick--;
+            }
+        return MDX_PILEUP_NO_CALL;
+    }
+    const uint64_t draw = z % total;
+    uint64_t cum = 0;
+    for (int b = 0; b < 4; b++) {
+        cum += e[b];
+        if (cum > draw) return (uint32_t)b;
+    }
+    return MDX_PILEUP_NO_CALL;
+}

@@ -55,9 +55,16 @@ EXPORTS = (
     "mdx_gsam_filter_counts",
     "mdx_dedup_begin", "mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info",
     "mdx_depth_begin", "mdx_depth_add", "mdx_depth_finish", "mdx_depth_runs", "mdx_depth_fetch", "mdx_depth_info", "mdx_depth_regions",
+    "mdx_pileup_begin", "mdx_pileup_add", "mdx_pileup_finish", "mdx_pileup_info",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
+
+
+class MdxPileupConfig(ctypes.Structure):
+    """include/mdx.h ``mdx_pileup_config``."""
+    _fields_ = [("min_basequal", ctypes.c_int32), ("mask5", ctypes.c_int32), ("mask3", ctypes.c_int32), ("call", ctypes.c_int32),
+                ("min_depth", ctypes.c_int32), ("single_strand", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
 class MdxConfig(ctypes.Structure):
@@ -220,6 +227,10 @@ def load_library(path=None):
     lib.mdx_depth_fetch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
     lib.mdx_depth_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_depth_regions.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_pileup_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+    lib.mdx_pileup_add.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_pileup_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.mdx_pileup_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -568,6 +579,54 @@ class DamageEngine:
         self._check(self._lib.mdx_depth_regions(self._ctx, _ptr(per_interval) if n_iv else None, _ptr(per_group) if n_groups else None,
                                                 _ptr(group_hist) if n_groups else None))
         return per_interval, per_group, group_hist
+
+    # ------------------------------------------------------------------ allele counts at listed sites
+    PILEUP_COUNTERS = 12
+    PILEUP_CALLS = {"none": 0, "random": 1, "majority": 2}      # include/mdx.h MDX_PILEUP_CALL_*
+
+    def pileup_begin(self, site_pos, site_off, alleles=None, min_basequal=0, mask_ends=(0, 0), call="random", seed=0, min_depth=1,
+                     single_strand=False):
+        """The sites resident and their zeroed counters, 48 bytes per site (include/mdx.h ``mdx_pileup_begin``).  ``site_pos``:
+        0-based positions, strictly increasing inside each sequence's slice ``site_off[t]:site_off[t + 1]``; ``alleles``: uint8
+        [sites][2], ref and alt as 0 .. 3 for A C G T, or None.  A second call starts from zero with the new sites."""
+        site_pos = np.ascontiguousarray(site_pos, np.int32)
+        site_off = np.ascontiguousarray(site_off, np.int64)
+        if alleles is not None:
+            alleles = np.ascontiguousarray(alleles, np.uint8).reshape(-1, 2)
+            if len(alleles) != len(site_pos):
+                raise ValueError("pileup_begin: %d rows of alleles for %d sites" % (len(alleles), len(site_pos)))
+        if len(site_off) < 2 or int(site_off[-1]) != len(site_pos):
+            raise ValueError("pileup_begin: site_off does not end at the number of sites")
+        cfg = MdxPileupConfig(int(min_basequal), int(mask_ends[0]), int(mask_ends[1]), self.PILEUP_CALLS[call], int(min_depth),
+                              int(bool(single_strand)), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        self._check(self._lib.mdx_pileup_begin(self._ctx, ctypes.byref(cfg), _ptr(site_pos) if len(site_pos) else _ptr(np.zeros(1, np.int32)), _ptr(site_off),
+                                               ctypes.c_int32(len(site_off) - 1), _ptr(alleles) if alleles is not None and len(alleles) else None))
+        self._n_pileup_sites = len(site_pos)
+
+    def pileup_add(self, view):
+        """The (record, site) pairs of a device batch's counted records into the sites' counters (``mdx_pileup_add``): enqueued.
+        The flag column is read as it stands, so behind ``dedup_mark`` the later copies add nothing."""
+        dev = view.dev if isinstance(view, DeviceBatch) else view
+        self._check(self._lib.mdx_pileup_add(self._ctx, ctypes.byref(dev)))
+
+    def pileup_finish(self):
+        """``(counters, refbase, call, depth, counts)`` (``mdx_pileup_finish``): uint32 [sites][12] — A+ C+ G+ T+ A- C- G- T-
+        Deletions LowQual Other Masked —, the reference's letter and the call per site as bytes (``S1``; the call ``.`` under
+        ``call="none"``), uint32 depths — the sum of the eight base counters — and a dict of the records counted, those outside
+        their sequence, those over at least one site and the (record, site) pairs."""
+        n = getattr(self, "_n_pileup_sites", 0)
+        counters = np.zeros((max(1, n), self.PILEUP_COUNTERS), np.uint32)
+        refbase, call, depth = np.zeros(max(1, n), "S1"), np.zeros(max(1, n), "S1"), np.zeros(max(1, n), np.uint32)
+        counts = np.zeros(4, np.uint64)
+        self._check(self._lib.mdx_pileup_finish(self._ctx, _ptr(counters), _ptr(refbase), _ptr(call), _ptr(depth), _ptr(counts)))
+        return counters[:n], refbase[:n], call[:n], depth[:n], dict(zip(("counted", "outside", "over_a_site", "pairs"), (int(x) for x in counts)))
+
+    def pileup_info(self):
+        """The stage's sizes (``mdx_pileup_info``): the pairs the add kernel's list holds in a round, the records a block of it
+        takes, the bytes of HBM held, the sites."""
+        out = np.zeros(4, np.uint64)
+        self._check(self._lib.mdx_pileup_info(self._ctx, _ptr(out)))
+        return dict(zip(("list_pairs", "block_records", "bytes", "sites"), (int(x) for x in out)))
 
     def set_reference(self, ref):
         """``ref``: a ``Reference`` (contigs in host memory) or a ``fasta.FastaOnDisk`` — the FASTA file itself, which the

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import __version__, groupings
 from . import depth as depth_files
+from . import pileup as pileup_files
 from .batch import mark_unmaskable
 from .engine import BadReadError, DamageEngine, MdxError
 from .groupings import PmdScore, TerminalDamage        # noqa: F401  (where callers import them from)
@@ -293,6 +294,32 @@ def build_parser():
     g.add_argument("--depth-thresholds", metavar="T[,T...]", default=None,
                    help="with --depth-regions: the depths T for which depth_thresholds.tsv gives the bases at depth >= T; strictly "
                         "increasing integers in 1..1022, at most 32 (default: 1,5,10,20)")
+    g.add_argument("--pileup-sites", metavar="FILE", default=None,
+                   help="allele counts and a pseudo-haploid call at the sites of FILE, in the same pass: what `samtools mpileup -l "
+                        "FILE | pileupCaller` makes of the counted records, without writing them first.  Lines of "
+                        "sequence<TAB>position[<TAB>ref<TAB>alt[<TAB>id]], the position 1-based, in any order; `#` lines and empty "
+                        "lines are skipped.  A record is counted as for --depth; at every site it lies over, its base goes to one "
+                        "of A+ C+ G+ T+ A- C- G- T- (as stored; the strand by FLAG 0x10), Deletions, LowQual, Other or Masked.  "
+                        "pileup.tsv gives a line per site in (sequence, position) order, pileup_summary.tsv the totals.  Takes 48 "
+                        "bytes of device memory per site.  Libraries and groups are summed.  BAM input on the device decode path "
+                        "only: not SAM text, --host-decode, --gpus above 1 or -n N.  Not a reference option")
+    g.add_argument("--pileup-min-basequal", metavar="Q", type=int, default=None,
+                   help="with --pileup-sites: a base whose quality is below Q counts as LowQual (0..93, default 0); a record "
+                        "without qualities is never LowQual.  With --min-basequal as well, Q must not be above it")
+    g.add_argument("--pileup-mask-ends", metavar="K5[,K3]", default=None,
+                   help="with --pileup-sites: a base inside the first K5 query bases of the molecule's 5' end or the last K3 of its "
+                        "3' end counts as Masked (0..255 each, one number means both, default 0,0): the windows of --mask-ends "
+                        "with --mask-what all")
+    g.add_argument("--pileup-call", choices=pileup_files.CALLS, default=None,
+                   help="with --pileup-sites: `random` (the default) draws one of the site's eligible bases, `majority` takes the "
+                        "most frequent one and draws among ties, `none` leaves the Call column out.  The draw is a function of "
+                        "the site's counters, --pileup-seed, the sequence and the position alone")
+    g.add_argument("--pileup-seed", metavar="N", type=int, default=None, help="with --pileup-sites: the seed of the draws (default 0)")
+    g.add_argument("--pileup-min-depth", metavar="D", type=int, default=None,
+                   help="with --pileup-sites: a site with fewer than D eligible bases is called N (default 1)")
+    g.add_argument("--pileup-single-strand-mode", action="store_true", default=False,
+                   help="with --pileup-sites whose lines bring ref and alt: at a C/T site only the bases of reverse-strand records "
+                        "are eligible, at a G/A site only those of forward-strand records (pileupCaller --singleStrandMode)")
     g.add_argument("--batch-reads", type=int, default=4_000_000, help="records per device batch")
     g.add_argument("--gpu-decode", dest="gpu_decode", action="store_true", default=True,
                    help="inflate and unpack a BAM file on the GPU (include/mdx.h mdx_gbam_*): the compressed file goes "
@@ -484,6 +511,54 @@ def _check_depth(parser, o):
                 parser.error("--depth-bedgraph %s is the input file: the run would overwrite what it reads" % o.depth_bedgraph)
 
 
+def _check_pileup(parser, o):
+    """The argument errors of --pileup-sites and the --pileup-* options; the defaults filled in."""
+    given = [name for name, value in (("--pileup-min-basequal", o.pileup_min_basequal), ("--pileup-mask-ends", o.pileup_mask_ends),
+                                      ("--pileup-call", o.pileup_call), ("--pileup-seed", o.pileup_seed),
+                                      ("--pileup-min-depth", o.pileup_min_depth),
+                                      ("--pileup-single-strand-mode", o.pileup_single_strand_mode or None)) if value is not None]
+    if o.pileup_sites is None:
+        if given:
+            parser.error("%s need%s --pileup-sites: the list of sites the pileup is made at" % (" / ".join(given), "s" if len(given) == 1 else ""))
+        return
+    if o.rescale_only or o.stats_only:
+        parser.error("--pileup-sites belongs to the tabulation pass; neither --rescale-only nor --stats-only counts records")
+    if not o.gpu_decode:
+        parser.error("--pileup-sites is gathered on the device decode path: not with --host-decode")
+    if o.gpus > 1:
+        parser.error("--pileup-sites cannot be combined with --gpus %d: the ranks take alternate slabs of the input, and the "
+                     "counters of the ranks would have to be summed across the cards; use --gpus 1" % o.gpus)
+    if o.downsample is not None and o.downsample >= 1:
+        parser.error("--pileup-sites cannot be combined with -n %d: the reservoir of a fixed number of reads is the host's and knows "
+                     "its sample at the end of the input only; a fraction (-n below 1) is drawn on the way" % int(o.downsample))
+    o.pileup_min_basequal = 0 if o.pileup_min_basequal is None else o.pileup_min_basequal
+    if not 0 <= o.pileup_min_basequal <= 93:
+        parser.error("--pileup-min-basequal %d: a quality is 0..93" % o.pileup_min_basequal)
+    if o.pileup_min_basequal and o.minqual and o.pileup_min_basequal > o.minqual:
+        parser.error("--pileup-min-basequal %d is above --min-basequal %d: the decoder drops the qualities of a slab none of whose "
+                     "bases is below --min-basequal, so a higher threshold cannot be applied beside it" % (o.pileup_min_basequal, o.minqual))
+    try:
+        o.pileup_mask_ends = pileup_files.parse_mask_ends(o.pileup_mask_ends)
+    except ValueError as error:
+        parser.error("--pileup-mask-ends: %s" % error)
+    o.pileup_call = o.pileup_call or "random"
+    o.pileup_seed = 0 if o.pileup_seed is None else o.pileup_seed
+    if not 0 <= o.pileup_seed < 1 << 64:
+        parser.error("--pileup-seed %d: an unsigned number of 64 bits" % o.pileup_seed)
+    o.pileup_min_depth = 1 if o.pileup_min_depth is None else o.pileup_min_depth
+    if not 1 <= o.pileup_min_depth < 1 << 31:
+        parser.error("--pileup-min-depth %d: at least 1" % o.pileup_min_depth)
+    try:
+        with open(o.pileup_sites, "r") as handle:
+            alleles = pileup_files.first_line_has_alleles(handle)
+    except (OSError, UnicodeDecodeError) as error:
+        parser.error("--pileup-sites %s: %s" % (o.pileup_sites, error))
+    if alleles is None:
+        parser.error("--pileup-sites %s holds no site" % o.pileup_sites)
+    if o.pileup_single_strand_mode and not alleles:
+        parser.error("--pileup-single-strand-mode needs Ref and Alt on every site: the lines of %s bring no alleles" % o.pileup_sites)
+
+
 def parse_args(argv):
     parser = build_parser()
     o = parser.parse_args(argv)
@@ -536,6 +611,7 @@ def parse_args(argv):
     _check_write_kept(parser, o)
     _check_remove_duplicates(parser, o)
     _check_depth(parser, o)
+    _check_pileup(parser, o)
     if o.stats_only:
         if not o.folder:
             parser.error("--folder required when using --stats-only")
@@ -1077,6 +1153,9 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     dedup = bool(getattr(options, "remove_duplicates", False)) and not sam_text
     # (--depth: BAM input, one rank, likewise; the accumulator lies over the resident reference)
     depth = bool(getattr(options, "depth", False)) and not sam_text
+    # (--pileup-sites: likewise; the sites and their counters are resident beside the reference)
+    pileup = getattr(options, "pileup_sites_list", None) if not sam_text else None
+    pileup_qual = pileup is not None and options.pileup_min_basequal > 0
     carry = None
     try:
         engine.set_reference(ref)
@@ -1084,6 +1163,10 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             engine.dedup_begin(options.duplicate_ends, _expected_records(options, reader))
         if depth:
             engine.depth_begin()
+        if pileup is not None:
+            engine.pileup_begin(pileup.pos, pileup.off, pileup.alleles, min_basequal=options.pileup_min_basequal,
+                                mask_ends=options.pileup_mask_ends, call=options.pileup_call, seed=options.pileup_seed,
+                                min_depth=options.pileup_min_depth, single_strand=options.pileup_single_strand_mode)
         stages.mark("reference resident")
         warned_about_quals = False
         error = None
@@ -1094,8 +1177,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         stages.mark("warm-up joined")
         with (GpuSamStream if sam_text else GpuBamStream)(
                 engine, reader.source if reader.source is not None else options.filename, readgroups=readgroups,
-                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0 or by_pmd, min_basequal=options.minqual,
-                packed=True if by_pmd else None, record_filter=options.record_filter) as stream, \
+                lib_default=lib_default, chunk_bytes=slab, want_qual=options.minqual != 0 or by_pmd or pileup_qual, min_basequal=options.minqual,
+                packed=True if by_pmd or pileup_qual else None, record_filter=options.record_filter) as stream, \
                 (_KeptOutput(options, engine, stream) if write_kept else contextlib.nullcontext()) as kept_out:
             # (several ranks: rank r decodes the slabs r, r + W, ... and steps over the others)
             slab, n_reads, n_kept = 0, 0, 0
@@ -1159,6 +1242,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                     if depth:
                         # (the final flags: behind the filters, the draws and the duplicates' marks)
                         engine.depth_add(view)
+                    if pileup is not None:
+                        engine.pileup_add(view)
                     engine.tabulate_view(view, record_base=n_reads)
                     if kept_out is not None:
                         kept_out.add(view)
@@ -1192,6 +1277,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                     engine.depth_runs() if options.depth_bedgraph is not None else None, engine.depth_info())
                 if getattr(options, "depth_regions", False):
                     options.depth_regions_result = engine.depth_regions()
+            if pileup is not None:
+                options.pileup_result = (list(ref.names),) + engine.pileup_finish() + (engine.pileup_info(),)
             if kept_out is not None:
                 kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
@@ -1222,7 +1309,7 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
         reason = str(error)
     # never silent: a regression of the device path must not show up as nothing but a slow run
     options.gpu_decode_fallbacks = getattr(options, "gpu_decode_fallbacks", 0) + 1
-    if write_kept or dedup or depth:
+    if write_kept or dedup or depth or pileup is not None:
         # (no route through the host decoder: the run ends, main says why)
         engine.close()
         logger.warning("GPU decode path gave up: %s", reason)
@@ -1271,6 +1358,24 @@ def _report_depth(options, logger):
         # (its four files are by_region/'s: groupings.RegionGroups.write)
         logger.info(depth_files.region_log_line(options.depth_regions_result[1]))
     logger.debug("Depth: %d intervals, %d runs of depth > 0; %d bytes of HBM", counts["intervals"], counts["runs"], info["bytes"])
+
+
+def _report_pileup(options, logger):
+    """--pileup-sites: pileup.tsv, pileup_summary.tsv and the log lines (mapdamage_amd/pileup.py)."""
+    names, counters, refbase, call, depth, counts, info = options.pileup_result
+    sites = options.pileup_sites_list
+    with_call = options.pileup_call != "none"
+    pileup_files.write_pileup(options.folder / "pileup.tsv", names, sites, counters, refbase, call, depth, with_call)
+    values = dict(path=options.pileup_sites, min_basequal=options.pileup_min_basequal, mask_ends=options.pileup_mask_ends,
+                  call=options.pileup_call, seed=options.pileup_seed, min_depth=options.pileup_min_depth,
+                  single_strand=options.pileup_single_strand_mode)
+    (options.folder / "pileup_summary.tsv").write_text(pileup_files.summary_text(values, counters, call, depth, counts))
+    logger.info(pileup_files.log_line(values, counters, call, depth, counts))
+    strangers = pileup_files.off_build(sites, refbase)
+    if strangers:
+        logger.warning("--pileup-sites: at %d of %d sites the reference's base is neither Ref nor Alt; the usual sign of a list "
+                       "of sites made for another build of the genome", strangers, len(sites))
+    logger.debug("Pileup: %d pairs of a record and a site; a list of %d pairs a round; %d bytes of HBM", counts["pairs"], info["list_pairs"], info["bytes"])
 
 
 def main(argv):
@@ -1404,6 +1509,20 @@ def main(argv):
             logger.error("--depth needs BAM input: '%s' is SAM text, which the option does not take (samtools view -b in front "
                          "of the run)", options.filename)
             return 1
+        if options.pileup_sites is not None:
+            if not reader.is_bam:
+                logger.error("--pileup-sites needs BAM input: '%s' is SAM text, which the option does not take (samtools view -b "
+                             "in front of the run)", options.filename)
+                return 1
+            try:
+                options.pileup_sites_list = pileup_files.read_sites(options.pileup_sites, list(reader.handle.header.references),
+                                                                    list(reader.handle.header.lengths))
+            except (ValueError, OSError, UnicodeDecodeError) as error:
+                logger.error("%s", error)
+                return 1
+            if options.pileup_single_strand_mode and options.pileup_sites_list.alleles is None:
+                logger.error("--pileup-single-strand-mode needs Ref and Alt on every site: the lines of %s bring no alleles", options.pileup_sites)
+                return 1
         libraries = reader.get_libraries()
         try:
             options.strata = reference_strata(options, list(reader.handle.header.references), list(reader.handle.header.lengths))
@@ -1455,6 +1574,10 @@ def main(argv):
             logger.error("--depth is gathered on the device decode path, which did not finish this run: the host decoder cannot "
                          "go on with an accumulator that lives on the device, and nothing is written")
             return 1
+        if tables is None and options.pileup_sites is not None:
+            logger.error("--pileup-sites is gathered on the device decode path, which did not finish this run: the host decoder "
+                         "cannot go on with counters that live on the device, and nothing is written")
+            return 1
         if tables is None:
             tables = _tabulate_on_host(options, reader, ref, libraries, logger, ranks, carry)
         fallbacks = getattr(options, "gpu_decode_fallbacks", 0)
@@ -1478,6 +1601,8 @@ def main(argv):
             _report_duplicates(options, libraries, logger)
         if options.depth:
             _report_depth(options, logger)
+        if options.pileup_sites is not None:
+            _report_pileup(options, logger)
         if options.freq_files:
             (options.folder / "5pCtoT_freq.txt").write_text(tables.damage_frequency_text("5p", options.readplot))
             (options.folder / "3pGtoA_freq.txt").write_text(tables.damage_frequency_text("3p", options.readplot))
