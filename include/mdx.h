@@ -164,7 +164,9 @@ int mdx_set_reference(mdx_ctx *ctx, const uint8_t *bases, const int64_t *contig_
  * kernel takes the line ends out by the index's arithmetic — no pass over the bases on the host; pieces of the file that
  * hold none of the wanted sequences are not read.  lengths (may be NULL) receives the length of each; a name the index
  * lacks is MDX_ERR_ARG, or with missing_ok an empty contig (a record mapped to it is MDX_ERR_BAD_READ when it is met: the
- * reference fails in fetch at that read, not before).  Synchronous.
+ * reference fails in fetch at that read, not before).  A byte of the file belongs to one sequence: an index whose rows for two
+ * wanted sequences share bytes (a hand-edited or foreign .fai) is MDX_ERR_ARG, the message naming both; rows that merely
+ * touch are served.  Synchronous.
  * The file may be uncompressed or bgzip-compressed (BGZF; told by its first bytes, not by its name).  A BGZF file's index
  * holds offsets into the inflated text, as htslib writes them, and it has a second one, `<fasta_path>.gzi` (bgzip's block
  * index).  mdx_fasta_index makes sure both exist: a missing .fai is built from the text inflated on the host's threads — once —

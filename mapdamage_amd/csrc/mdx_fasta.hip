@@ -600,6 +600,22 @@ int mdx_fasta_to_device(const char *fasta_path, int32_t n_contig, const char *co
     // (the SAM specification wants the names of a header unique: a sequence wanted twice has one place too few)
     for (size_t j = 1; j < seqs.size(); j++)
         if (seqs[j].raw_off == seqs[j - 1].raw_off) { err = "a sequence of the FASTA file is named twice"; return MDX_ERR_ARG; }
+    // (a byte of the file goes to one sequence — the last that begins at or in front of it: rows of a hand-edited or foreign
+    // index that share bytes would leave the first of them its fill.  Each row against the one in front suffices: where none
+    // begins in front of its neighbour's end the ends ascend too.  Rows that touch — raw_end == raw_off — share nothing.)
+    for (size_t j = 1; j < seqs.size(); j++)
+        if (seqs[j].raw_off < seqs[j - 1].raw_end) {
+            // (the wanted rows' first bytes differ, as checked above: the offset tells the name)
+            std::string a, b;
+            for (int i = 0; i < n_contig; i++) {
+                const auto it = by_name.find(names[i] ? names[i] : "");
+                if (it == by_name.end() || idx[it->second].len == 0) continue;
+                if (idx[it->second].off == seqs[j - 1].raw_off) a = names[i];
+                if (idx[it->second].off == seqs[j].raw_off) b = names[i];
+            }
+            err = "the index gives sequence '" + b + "' bytes of the file that it also gives to sequence '" + a + "': re-index it with 'samtools faidx'";
+            return MDX_ERR_ARG;
+        }
     if (bgzf) return bgzf_to_device(f, fasta_path, table, from_gzi, seqs, d_out, err, stream);
     MdxFastaSeq *d_seqs = nullptr;
     uint8_t *stage[2] = {nullptr, nullptr};
