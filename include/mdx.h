@@ -556,6 +556,37 @@ int mdx_pileup_finish(mdx_ctx *ctx, uint32_t *counters /* [n_sites][12] */, uint
                       uint64_t *counts /* [4] */);
 int mdx_pileup_info(mdx_ctx *ctx, uint64_t *info /* [4] */);
 
+/* ---- Genotype likelihoods at the same sites, gathered by the same adds: what `angsd -GL 2 -doGlf 2 -sites panel` makes of the
+ * file (GATK's model; the rule: csrc/mdx_pileup_key.h).
+ *
+ * A (record, site) pair adds exactly when it adds to one of the eight base x strand counters — Masked, Other, LowQual, Deletions
+ * and N add nothing, so mask5 / mask3 and min_basequal shape the likelihoods as they shape the counts.  Its quality is
+ * min(qual[q], 93), for a record without qualities noqual_quality.  table [94][3] holds, per quality, round(2^24 * x) for x =
+ * log(1 - e), log((1 - e) / 2 + e / 6), log(e / 3) with e = min(0.75, 10^(-q / 10)): the term of an observed base b under a
+ * genotype bb, under a heterozygous one that holds b, under any other.  A site's sums are int64 [2 strands][4 bases][3], row c
+ * of them beside counter c, 192 bytes a site; the device only adds integers, so they are the same in one batch and in many,
+ * under any schedule.  At the finish the eligible strands are those of the call (single_strand of mdx_pileup_config); for the
+ * ten genotypes AA AC AG AT CC CG CT GG GT TT, logL = the sum over the four bases of the eligible strands' sums of the term
+ * that the genotype gives the base, whatever the site's alleles.
+ *
+ *   mdx_pileup_likelihoods_begin   behind mdx_pileup_begin and in front of the first mdx_pileup_add (else MDX_ERR_STATE):
+ *                      allocates and zeroes the sums; an allocation that fails is MDX_ERR_HIP with the size.  noqual_quality
+ *                      1..93.  A later mdx_pileup_begin or a new reference releases them, mdx_reset zeroes them, mdx_destroy
+ *                      frees them; mdx_pileup_info's bytes include them.  Called again it zeroes them and takes the new table.
+ *   mdx_pileup_add     launches the add kernel's variant while the sums exist: three 64-bit atomics beside the counter's.  It
+ *                      then reads the quality column, if the batch brings one, for the records that have qualities.
+ *   mdx_pileup_likelihoods_finish  synchronous; one launch (a lane per site) that leaves the sums as they are.  sums
+ *                      [n_sites][24]; gl [n_sites][10]: logL minus the site's largest, <= 0, in units of 2^-24 (natural
+ *                      logarithm); best [n_sites]: the index of the first genotype at 0; bases [n_sites]: the eligible
+ *                      strands' base counters summed — 0: ten zeros, best 0; counts [2]: pairs that added, those of them from
+ *                      records without qualities.  Any pointer may be NULL.  MDX_ERR_STATE without the sums.
+ *
+ * Limit: the largest magnitude of the table, below 2^29, times the 2^31 records of the stage's limit is below 2^63: no sum
+ * leaves its int64. */
+int mdx_pileup_likelihoods_begin(mdx_ctx *ctx, const int64_t *table /* [94][3] */, int32_t noqual_quality);
+int mdx_pileup_likelihoods_finish(mdx_ctx *ctx, int64_t *sums /* [n_sites][24] or NULL */, int64_t *gl /* [n_sites][10] */, uint8_t *best,
+                                  uint32_t *bases /* [n_sites] each */, uint64_t *counts /* [2] */);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

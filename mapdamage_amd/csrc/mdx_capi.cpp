@@ -238,6 +238,11 @@ struct mdx_ctx {
         int list = 0;                          // pairs a round of the add kernel's LDS list takes
         uint64_t added = 0;                    // records of the batches added, known without a readback
         mdx_pileup_config cfg{};
+        // genotype likelihoods (mdx_pileup_likelihoods_begin); all null without it
+        unsigned long long *sums = nullptr;    // [n_sites][24] int64 in two's complement
+        unsigned long long *gl_counts = nullptr;   // [2]: pairs that added, those of them from records without qualities
+        int64_t *gl_table = nullptr;           // [94][3]
+        int32_t noqual = 0;
     } pileup;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -399,7 +404,7 @@ int depth_clear(mdx_ctx *c) {
 // ---- allele counts at listed sites: the context's side (the launches: mdx_pileup.hip)
 void pileup_release(mdx_ctx *c) {
     auto &p = c->pileup;
-    void *ptrs[] = {p.site_pos, p.site_off, p.alleles, p.counters, p.counts};
+    void *ptrs[] = {p.site_pos, p.site_off, p.alleles, p.counters, p.counts, p.sums, p.gl_counts, p.gl_table};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     p = mdx_ctx::Pileup{};
 }
@@ -408,6 +413,10 @@ int pileup_clear(mdx_ctx *c) {
     auto &p = c->pileup;
     HIP_TRY(c, hipMemsetAsync(p.counters, 0, (size_t)p.n_sites * MDX_PILEUP_COUNTERS * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(p.counts, 0, 4 * 8, c->stream));
+    if (p.sums) {
+        HIP_TRY(c, hipMemsetAsync(p.sums, 0, (size_t)p.n_sites * MDX_GL_SUMS * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(p.gl_counts, 0, 2 * 8, c->stream));
+    }
     p.added = 0;
     return MDX_OK;
 }
@@ -2025,7 +2034,9 @@ int mdx_pileup_add(mdx_ctx *c, const mdx_batch *b) {
     auto &p = c->pileup;
     if (!p.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_add: call mdx_pileup_begin first");
     if (b->n_reads == 0) return MDX_OK;
-    // (a counter is a uint32: the counted records are not known without a readback, the records added bound them)
+    // (a counter is a uint32: the counted records are not known without a readback, the records added bound them.  The same
+    // limit keeps the likelihoods' sums inside an int64: a record adds at most one term to a sum, and the largest magnitude of
+    // the table, below 2^29, times 2^31 is below 2^63)
     if (p.added + (uint64_t)b->n_reads >= ((uint64_t)1 << 31))
         return fail(c, MDX_ERR_ARG, "mdx_pileup_add: 2^31 records or more since mdx_pileup_begin; a counter is a uint32");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -2035,7 +2046,13 @@ int mdx_pileup_add(mdx_ctx *c, const mdx_batch *b) {
     k.seq = b->seq; k.qual = b->qual; k.seq_packed = b->seq_format != MDX_SEQ_ASCII ? 1 : 0;
     k.contig_off = c->d_contig_off; k.n_contig = c->n_contig; k.n_libraries = dedup_libraries(c);
     k.k5 = (uint32_t)p.cfg.mask5; k.k3 = (uint32_t)p.cfg.mask3; k.min_qual = (uint32_t)p.cfg.min_basequal;
-    mdx_k_pileup_add(k, pileup_sites(c), p.list, p.counts, c->stream);
+    if (p.sums) {
+        MdxPileupSums gl{};
+        gl.sums = p.sums; gl.counts = p.gl_counts; gl.table = p.gl_table; gl.noqual = (uint32_t)p.noqual;
+        mdx_k_pileup_add_likelihoods(k, pileup_sites(c), p.list, p.counts, gl, c->stream);
+    } else {
+        mdx_k_pileup_add(k, pileup_sites(c), p.list, p.counts, c->stream);
+    }
     HIP_TRY(c, hipGetLastError());
     p.added += (uint64_t)b->n_reads;
     return MDX_OK;
@@ -2080,7 +2097,72 @@ int mdx_pileup_info(mdx_ctx *c, uint64_t *info) {
     const auto &p = c->pileup;
     info[0] = (uint64_t)p.list; info[1] = (uint64_t)mdx_k_pileup_block();
     info[2] = (uint64_t)p.n_sites * (MDX_PILEUP_COUNTERS * 4 + 4 + (p.has_alleles ? 2 : 0)) + ((uint64_t)c->n_contig + 1) * 8 + 4 * 8;
+    if (p.sums) info[2] += (uint64_t)p.n_sites * MDX_GL_SUMS * 8 + MDX_GL_QUALITIES * MDX_GL_TERMS * 8 + 2 * 8;
     info[3] = (uint64_t)p.n_sites;
+    return MDX_OK;
+}
+
+int mdx_pileup_likelihoods_begin(mdx_ctx *c, const int64_t *table, int32_t noqual_quality) {
+    if (!c) return MDX_ERR_ARG;
+    auto &p = c->pileup;
+    if (!p.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_begin: call mdx_pileup_begin first");
+    if (!table) return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_begin: null table");
+    if (noqual_quality < 1 || noqual_quality >= MDX_GL_QUALITIES)
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_begin: noqual_quality " + std::to_string(noqual_quality) + " is not 1..93");
+    if (p.added) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_begin: records have been added since mdx_pileup_begin; the sums would lack them");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!p.sums) {
+        const size_t bytes = (size_t)p.n_sites * MDX_GL_SUMS * 8;
+        if (hipMalloc((void **)&p.sums, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p.sums = nullptr;
+            return fail(c, MDX_ERR_HIP, "mdx_pileup_likelihoods_begin: out of device memory for the sums of " + std::to_string(bytes) + " bytes (192 per site of " +
+                                        std::to_string(p.n_sites) + ")");
+        }
+        hipError_t e = hipMalloc((void **)&p.gl_counts, 2 * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&p.gl_table, MDX_GL_QUALITIES * MDX_GL_TERMS * 8);
+        if (e != hipSuccess) {
+            for (void *q : {(void *)p.sums, (void *)p.gl_counts, (void *)p.gl_table}) if (q) (void)hipFree(q);
+            p.sums = p.gl_counts = nullptr; p.gl_table = nullptr;
+            return fail(c, MDX_ERR_HIP, std::string("mdx_pileup_likelihoods_begin: ") + hipGetErrorString(e));
+        }
+    }
+    p.noqual = noqual_quality;
+    HIP_TRY(c, hipMemcpy(p.gl_table, table, MDX_GL_QUALITIES * MDX_GL_TERMS * 8, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(p.sums, 0, (size_t)p.n_sites * MDX_GL_SUMS * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(p.gl_counts, 0, 2 * 8, c->stream));
+    return MDX_OK;
+}
+
+int mdx_pileup_likelihoods_finish(mdx_ctx *c, int64_t *sums, int64_t *gl, uint8_t *best, uint32_t *bases, uint64_t *counts) {
+    if (!c) return MDX_ERR_ARG;
+    auto &p = c->pileup;
+    if (!p.on || !p.sums) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_finish: call mdx_pileup_begin and mdx_pileup_likelihoods_begin first");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)p.n_sites;
+    DevBuf out;     // gl [n][10] | bases [n] | best [n]
+    const size_t bases_at = n * MDX_GL_GENOTYPES * 8, best_at = bases_at + 4 * n;
+    if (out.reserve(best_at + n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, MDX_ERR_HIP, "mdx_pileup_likelihoods_finish: out of device memory for " + std::to_string(n) + " sites of 85 bytes");
+    }
+    int64_t *d_gl = (int64_t *)out.p;
+    uint32_t *d_bases = (uint32_t *)((uint8_t *)out.p + bases_at);
+    uint8_t *d_best = (uint8_t *)out.p + best_at;
+    mdx_k_pileup_likelihoods(pileup_sites(c), p.sums, p.cfg.single_strand, d_gl, d_best, d_bases, c->stream);
+    hipError_t e = hipGetLastError();
+    unsigned long long w[2] = {0, 0};
+    if (e == hipSuccess && sums) e = hipMemcpyAsync(sums, p.sums, n * MDX_GL_SUMS * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && gl) e = hipMemcpyAsync(gl, d_gl, n * MDX_GL_GENOTYPES * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && best) e = hipMemcpyAsync(best, d_best, n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && bases) e = hipMemcpyAsync(bases, d_bases, 4 * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(w, p.gl_counts, sizeof w, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    out.release();
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(c, MDX_ERR_HIP, std::string("mdx_pileup_likelihoods_finish: ") + hipGetErrorString(e));
+    if (counts) for (int q = 0; q < 2; q++) counts[q] = w[q];
     return MDX_OK;
 }
 

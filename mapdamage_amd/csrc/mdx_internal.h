@@ -564,6 +564,18 @@ int mdx_k_pileup_list();            // pairs its LDS list holds at most
 // counts [4]: counted, outside, records with at least one site, pairs; list: the list's capacity in force (1 .. mdx_k_pileup_list())
 void mdx_k_pileup_add(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, hipStream_t s);
 void mdx_k_pileup_call(const MdxPileupSites &st, const MdxPileupCall &a, hipStream_t s);
+// genotype likelihoods beside the counters (mdx_pileup_likelihoods_begin)
+struct MdxPileupSums {
+    unsigned long long *sums;       // [n_sites][MDX_GL_SUMS] int64 in two's complement
+    unsigned long long *counts;     // [2] pairs that added, those of them from records without qualities
+    const int64_t *table;           // [MDX_GL_QUALITIES][MDX_GL_TERMS] on the device
+    uint32_t noqual;                // the row of a record without qualities
+};
+void mdx_k_pileup_add_likelihoods(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, const MdxPileupSums &gl,
+                                  hipStream_t s);                                           // mdx_k_pileup_add and the sums
+// gl [n_sites][MDX_GL_GENOTYPES], best and bases [n_sites], all on the device
+void mdx_k_pileup_likelihoods(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best, uint32_t *bases,
+                              hipStream_t s);
 
 // ---- the record filter of the decoders as a kernel argument (MdxFilterArgs, mdx_filter_reason)
 #include "mdx_filter.h"

@@ -14,6 +14,8 @@
 //            it stopped until its pairs are done.  A record with more pairs than the list holds takes several rounds alone.
 //         No block waits for another.  The per-launch counters by ballot and one atomic per wavefront, the pairs by one per block.
 //   call  a lane per site: the reference's letter, the depth, the call (mdx_pileup_call)
+//   likelihoods (mdx_pileup_likelihoods_begin)  the add kernel's variant puts the three terms of a pair's quality beside its
+//         counter, into the site's 24 int64 sums; a lane per site makes the ten values from them (mdx_pileup_likelihoods)
 // A site's index comes from site_off alone, which the host has checked against n_sites: no address outside the counters is
 // formed.
 #include "mdx_internal.h"
@@ -49,15 +51,26 @@ __device__ __forceinline__ int64_t first_site(const int32_t *site_pos, int64_t l
     return lo;
 }
 
-__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts) {
+// GL: the variant of --pileup-likelihoods.  A pair that adds to a base counter adds the three terms of its quality to the
+// site's row of sums as well, three 64-bit atomics in two's complement, and the block keeps the table of terms in the LDS, filled
+// once: a lane's row depends on its own pair's quality, so a lookup in constant memory would be serialised quality by quality
+// over the wavefront (the scalar path takes one address at a time), and one in global memory is a load per pair; the LDS takes
+// 64 different rows at once.  Without GL nothing of it is compiled: pileup_add_kernel is the kernel as it was.
+template <bool GL>
+__device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const MdxPileupSites &st, int list, u64 *counts, const MdxPileupSums &gl) {
     __shared__ MdxPileupRecord rec[MDX_PU_BLOCK];
     __shared__ int64_t rec_site[MDX_PU_BLOCK];          // a record's first site
     __shared__ u64 before[MDX_PU_BLOCK + 1];            // the pairs of the records in front of it; [MDX_PU_BLOCK]: the block's
     __shared__ u64 wave_tot[MDX_PU_BLOCK / 64];
     __shared__ uint32_t list_site[MDX_PU_LIST];         // a pair's site, as its distance from the record's first
     __shared__ uint16_t list_rec[MDX_PU_LIST];          // ... and its record, as its lane
+    __shared__ int64_t terms[GL ? MDX_GL_QUALITIES * MDX_GL_TERMS : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * MDX_PU_BLOCK + threadIdx.x;
+    if constexpr (GL) {
+        // (visible to every lane behind phase 1's barriers)
+        for (int q = threadIdx.x; q < MDX_GL_QUALITIES * MDX_GL_TERMS; q += MDX_PU_BLOCK) terms[q] = gl.table[q];
+    }
     // ---- phase 1
     int kind = MDX_DEPTH_IGNORED;
     u64 n_pairs = 0;
@@ -94,6 +107,7 @@ __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_kernel(MdxPileupKey k
     __syncthreads();
     // ---- phase 2
     const u64 total = before[MDX_PU_BLOCK];
+    u64 n_added = 0, n_noqual = 0;                      // GL: the wavefront's pairs that added, those of them without qualities
     for (u64 base = 0; base < total; base += (u64)list) {
         const u64 stop = base + (u64)list < total ? base + (u64)list : total;
         {
@@ -108,11 +122,42 @@ __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_kernel(MdxPileupKey k
         for (uint32_t e = threadIdx.x; e < held; e += MDX_PU_BLOCK) {
             const uint32_t l = list_rec[e];
             const int64_t site = rec_site[l] + (int64_t)list_site[e];
-            const int cls = mdx_pileup_site(k, rec[l], (int64_t)st.site_pos[site]);
-            if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
+            if constexpr (!GL) {
+                const int cls = mdx_pileup_site(k, rec[l], (int64_t)st.site_pos[site]);
+                if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
+            } else {
+                uint32_t qi = 0;
+                const int cls = mdx_pileup_site_quality(k, rec[l], (int64_t)st.site_pos[site], gl.noqual, &qi);
+                if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
+                const bool adds = cls >= 0 && cls < 8, noqual = adds && !rec[l].has_qual;
+                if (adds) {
+                    // (cls < 8 and qi < MDX_GL_QUALITIES: the row lies inside the site's sums and inside the table)
+                    u64 *row = gl.sums + (size_t)site * MDX_GL_SUMS + (size_t)cls * MDX_GL_TERMS;
+                    const int64_t *t = &terms[qi * MDX_GL_TERMS];
+#pragma unroll
+                    for (int q = 0; q < MDX_GL_TERMS; q++) atomicAdd(&row[q], (u64)t[q]);
+                }
+                // the lanes of a wavefront that are here hold e in lane order, so whenever one of them is here lane 0 is: its
+                // two numbers are the wavefront's
+                n_added += (u64)__popcll(__ballot(adds));
+                n_noqual += (u64)__popcll(__ballot(noqual));
+            }
         }
         __syncthreads();
     }
+    if constexpr (GL) {
+        if (lane == 0) {
+            if (n_added) atomicAdd(&gl.counts[0], n_added);
+            if (n_noqual) atomicAdd(&gl.counts[1], n_noqual);
+        }
+    }
+}
+
+__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts) {
+    pileup_add_body<false>(k, st, list, counts, MdxPileupSums{});
+}
+__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_likelihoods_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts, MdxPileupSums gl) {
+    pileup_add_body<true>(k, st, list, counts, gl);
 }
 
 // the largest t in [0, n_contig) with off[t] <= g: the sequence whose slice holds site g (behind a row of empty slices, the last)
@@ -153,6 +198,37 @@ __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_call_kernel(MdxPileupSite
     a.call[g] = letter;
 }
 
+// a lane per site: the site's sums (192 bytes) and base counters as 16-byte loads, the rule's ten values, best and bases
+__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_likelihoods_kernel(MdxPileupSites st, const u64 *sums, int single_strand, int64_t *gl,
+                                                                          uint8_t *best, uint32_t *bases) {
+    const int64_t g = (int64_t)blockIdx.x * MDX_PU_BLOCK + threadIdx.x;
+    if (g >= st.n_sites) return;
+    int64_t S[MDX_GL_SUMS];
+    const ulonglong2 *row = (const ulonglong2 *)(sums + (size_t)g * MDX_GL_SUMS);          // (192 bytes a row: aligned to 16)
+#pragma unroll
+    for (int q = 0; q < MDX_GL_SUMS / 2; q++) {
+        const ulonglong2 w = row[q];
+        S[2 * q] = (int64_t)w.x; S[2 * q + 1] = (int64_t)w.y;
+    }
+    uint32_t c[8];
+    const uint4 *crow = (const uint4 *)(st.counters + (size_t)g * MDX_PILEUP_COUNTERS);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const uint4 w = crow[q];
+        c[4 * q] = w.x; c[4 * q + 1] = w.y; c[4 * q + 2] = w.z; c[4 * q + 3] = w.w;
+    }
+    const int ref = st.alleles ? (int)st.alleles[2 * g] : -1, alt = st.alleles ? (int)st.alleles[2 * g + 1] : -1;
+    int64_t v[MDX_GL_GENOTYPES];
+    uint8_t first;
+    uint32_t n;
+    mdx_pileup_likelihoods(S, c, single_strand, ref, alt, v, &first, &n);
+    ulonglong2 *out = (ulonglong2 *)(gl + (size_t)g * MDX_GL_GENOTYPES);                   // (80 bytes a row: aligned to 16)
+#pragma unroll
+    for (int q = 0; q < MDX_GL_GENOTYPES / 2; q++) out[q] = make_ulonglong2((u64)v[2 * q], (u64)v[2 * q + 1]);
+    best[g] = first;
+    bases[g] = n;
+}
+
 }  // namespace
 
 void mdx_k_pileup_add(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, hipStream_t s) {
@@ -160,6 +236,20 @@ void mdx_k_pileup_add(const MdxPileupKey &k, const MdxPileupSites &st, int list,
     if (list < 1) list = 1;
     if (list > MDX_PU_LIST) list = MDX_PU_LIST;
     pileup_add_kernel<<<(unsigned)((k.n + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(k, st, list, counts);
+}
+
+void mdx_k_pileup_add_likelihoods(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, const MdxPileupSums &gl,
+                                  hipStream_t s) {
+    if (k.n <= 0) return;
+    if (list < 1) list = 1;
+    if (list > MDX_PU_LIST) list = MDX_PU_LIST;
+    pileup_add_likelihoods_kernel<<<(unsigned)((k.n + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(k, st, list, counts, gl);
+}
+
+void mdx_k_pileup_likelihoods(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best, uint32_t *bases,
+                              hipStream_t s) {
+    if (st.n_sites <= 0) return;
+    pileup_likelihoods_kernel<<<(unsigned)((st.n_sites + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(st, sums, single_strand, gl, best, bases);
 }
 
 void mdx_k_pileup_call(const MdxPileupSites &st, const MdxPileupCall &a, hipStream_t s) {

@@ -30,6 +30,8 @@
 // z % k of them in A C G T order.
 //
 // Offsets are clamped to their columns, as the other rules clamp them: no byte outside a column is read.
+//
+// The genotype likelihoods at the same sites (--pileup-likelihoods): at the end of this file.
 #pragma once
 #include <stdint.h>
 #include "mdx_depth_key.h"
@@ -218,4 +220,100 @@ MDX_PU_FN uint32_t mdx_pileup_call(const uint32_t *c, int mode, uint64_t seed, u
         if (cum > draw) return (uint32_t)b;
     }
     return MDX_PILEUP_NO_CALL;
+}
+
+// ---- Genotype likelihoods at the sites (mdx_pileup_likelihoods_begin / _finish, --pileup-likelihoods): GATK's model, which is
+// ANGSD's -GL 2, in integers.
+//
+// A (record, site) pair adds exactly when mdx_pileup_site gives one of the eight base x strand counters; Masked, Other, LowQual,
+// Deletions and N add nothing.  Its quality is min(qual[q], 93), for a record without qualities the noqual quality (1 .. 93).
+// With e = min(0.75, 10^(-q / 10)) an observed base b has, under a diploid genotype, the term
+//   HOM  log(1 - e)              the genotype is bb
+//   HET  log((1 - e) / 2 + e / 6)    it is heterozygous and holds b
+//   NO   log(e / 3)              otherwise
+// which the caller brings as a table int64 [94][3] of round(term * 2^24) (mapdamage_amd/pileup.py builds it).  A site's sums are
+// int64 S[2 strands][4 bases][3] — row c of them for counter c of the eight —, to which a pair adds the three terms of its
+// quality: integers, so the sums are the same in any order, slab layout and schedule.  The largest magnitude of the table, 377 699
+// 653, times 2^31 is below 2^59: the stage's limit of fewer than 2^31 records keeps every sum, and every sum of sums below,
+// inside an int64.
+//
+// The likelihoods of a site are a function of its sums, its eight base counters and its alleles (mdx_pileup_likelihoods): the
+// eligible strands are those of mdx_pileup_call — both, but with alleles and single_strand the - strand alone at a {C, T} site
+// and the + strand alone at a {G, A} site.  T[b][.] = the eligible strands' S[.][b][.] summed.  For the ten genotypes AA AC AG AT
+// CC CG CT GG GT TT, logL(a1 a2) = sum over b of T[b][HOM] if a1 == a2 == b, T[b][HET] if a1 != a2 and b is one of them, T[b][NO]
+// otherwise: all four bases, whatever the alleles.  gl = logL - max logL (<= 0), best = the first genotype at the maximum,
+// bases = the eligible strands' base counters summed.  A site without bases has ten zeros and best 0.
+#define MDX_GL_QUALITIES 94
+#define MDX_GL_TERMS 3                  // HOM HET NO
+#define MDX_GL_SUMS 24                  // [2][4][3]
+#define MDX_GL_GENOTYPES 10
+
+// mdx_pileup_site, and for a pair that adds (a result 0 .. 7) its row of the table in *qi: the quality clamped to 93, noqual for
+// a record without qualities.  The same walk, the same tests in the same order; *qi is untouched for any other result.
+MDX_PU_FN int mdx_pileup_site_quality(const MdxPileupKey &k, const MdxPileupRecord &r, int64_t p, uint32_t noqual, uint32_t *qi) {
+    int64_t at = r.pos, x = 0;
+    for (uint32_t c = r.c0; c < r.c1; c++) {
+        const uint32_t w = k.cigar[c], op = w & 15u;
+        const int64_t ln = (int64_t)(w >> 4);
+        if (MDX_PU_IS_REF(op)) {
+            if (p < at + ln) {
+                if (p < at) return MDX_PILEUP_NOTHING;
+                if (op == 2u) return MDX_PILEUP_DELETIONS;
+                if (op == 3u) return MDX_PILEUP_NOTHING;
+                const int64_t q = x + (p - at);
+                if (mdx_pileup_masked(r, q)) return MDX_PILEUP_MASKED;
+                if (q >= (int64_t)r.n_seq) return MDX_PILEUP_OTHER;
+                const uint32_t base = mdx_pileup_base(k, r, (uint32_t)q);
+                if (base > 3u) return MDX_PILEUP_OTHER;
+                uint32_t quality = noqual;
+                if (r.has_qual) {
+                    quality = (uint32_t)k.qual[r.s0 + (uint32_t)q];
+                    if (quality < k.min_qual) return MDX_PILEUP_LOWQUAL;
+                    if (quality > (uint32_t)(MDX_GL_QUALITIES - 1)) quality = (uint32_t)(MDX_GL_QUALITIES - 1);
+                }
+                *qi = quality;
+                return (int)(base + 4u * r.rev);
+            }
+            at += ln;
+        }
+        if (MDX_PU_IS_QRY(op)) x += ln;
+    }
+    return MDX_PILEUP_NOTHING;
+}
+
+// the strands of a site that are eligible, as mdx_pileup_call takes them
+MDX_PU_FN void mdx_pileup_strands(int single_strand, int ref, int alt, bool *plus, bool *minus) {
+    *plus = *minus = true;
+    if (ref >= 0 && alt >= 0 && single_strand) {
+        const int lo = ref < alt ? ref : alt, hi = ref < alt ? alt : ref;
+        if (lo == 1 && hi == 3) *plus = false;
+        if (lo == 0 && hi == 2) *minus = false;
+    }
+}
+
+// the likelihoods of a site from its sums S [MDX_GL_SUMS] and its base counters c [8]: gl [MDX_GL_GENOTYPES], the index of the
+// best and the bases behind them
+MDX_PU_FN void mdx_pileup_likelihoods(const int64_t *S, const uint32_t *c, int single_strand, int ref, int alt, int64_t *gl, uint8_t *best,
+                                      uint32_t *bases) {
+    bool plus, minus;
+    mdx_pileup_strands(single_strand, ref, alt, &plus, &minus);
+    int64_t T[4][MDX_GL_TERMS];
+    uint32_t n = 0;
+    for (int b = 0; b < 4; b++) {
+        n += (plus ? c[b] : 0u) + (minus ? c[4 + b] : 0u);
+        for (int t = 0; t < MDX_GL_TERMS; t++)
+            T[b][t] = (plus ? S[b * MDX_GL_TERMS + t] : 0) + (minus ? S[(4 + b) * MDX_GL_TERMS + t] : 0);
+    }
+    const int64_t none = T[0][2] + T[1][2] + T[2][2] + T[3][2];
+    int g = 0, first = 0;
+    int64_t top = 0;
+    for (int a1 = 0; a1 < 4; a1++)
+        for (int a2 = a1; a2 < 4; a2++, g++) {
+            const int64_t v = a1 == a2 ? none - T[a1][2] + T[a1][0] : none - T[a1][2] - T[a2][2] + T[a1][1] + T[a2][1];
+            gl[g] = v;
+            if (g == 0 || v > top) { top = v; first = g; }
+        }
+    for (g = 0; g < MDX_GL_GENOTYPES; g++) gl[g] -= top;
+    *best = (uint8_t)first;
+    *bases = n;
 }

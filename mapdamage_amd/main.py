@@ -317,6 +317,18 @@ def build_parser():
     g.add_argument("--pileup-seed", metavar="N", type=int, default=None, help="with --pileup-sites: the seed of the draws (default 0)")
     g.add_argument("--pileup-min-depth", metavar="D", type=int, default=None,
                    help="with --pileup-sites: a site with fewer than D eligible bases is called N (default 1)")
+    g.add_argument("--pileup-likelihoods", action="store_true", default=False,
+                   help="with --pileup-sites: the ten diploid genotype likelihoods at every site, from the same pass: what `angsd "
+                        "-GL 2 -doGlf 2 -sites FILE` makes of the counted records (GATK's model).  A base adds where it adds to a "
+                        "base counter of pileup.tsv, so --pileup-min-basequal and --pileup-mask-ends shape them too; "
+                        "--pileup-single-strand-mode chooses the strands.  pileup_likelihoods.tsv gives log10 ratios to the best "
+                        "genotype, pileup_likelihoods_summary.tsv the totals.  Takes 192 bytes of HBM per site more.  Not beside -Q")
+    g.add_argument("--pileup-noqual-quality", metavar="Q", type=int, default=None,
+                   help="with --pileup-likelihoods: the quality of the bases of a record without qualities (1..93, default 30)")
+    g.add_argument("--pileup-beagle", metavar="PATH", default=None,
+                   help="with --pileup-likelihoods and sites that bring ref and alt: the BEAGLE genotype likelihood file of `angsd "
+                        "-doGlf 2` — ref/ref, ref/alt, alt/alt per site, normalised — for PCAngsd, NGSadmix, ngsRelate; gzip if "
+                        "PATH ends in .gz")
     g.add_argument("--pileup-single-strand-mode", action="store_true", default=False,
                    help="with --pileup-sites whose lines bring ref and alt: at a C/T site only the bases of reverse-strand records "
                         "are eligible, at a G/A site only those of forward-strand records (pileupCaller --singleStrandMode)")
@@ -517,6 +529,13 @@ def _check_pileup(parser, o):
                                       ("--pileup-call", o.pileup_call), ("--pileup-seed", o.pileup_seed),
                                       ("--pileup-min-depth", o.pileup_min_depth),
                                       ("--pileup-single-strand-mode", o.pileup_single_strand_mode or None)) if value is not None]
+    with_likelihoods = [name for name, value in (("--pileup-noqual-quality", o.pileup_noqual_quality), ("--pileup-beagle", o.pileup_beagle))
+                        if value is not None]
+    if with_likelihoods and not o.pileup_likelihoods:
+        parser.error("%s need%s --pileup-likelihoods: the genotype likelihoods they belong to" % (" / ".join(with_likelihoods),
+                                                                                                 "s" if len(with_likelihoods) == 1 else ""))
+    if o.pileup_likelihoods and o.pileup_sites is None:
+        parser.error("--pileup-likelihoods needs --pileup-sites: the list of sites the likelihoods are made at")
     if o.pileup_sites is None:
         if given:
             parser.error("%s need%s --pileup-sites: the list of sites the pileup is made at" % (" / ".join(given), "s" if len(given) == 1 else ""))
@@ -557,6 +576,28 @@ def _check_pileup(parser, o):
         parser.error("--pileup-sites %s holds no site" % o.pileup_sites)
     if o.pileup_single_strand_mode and not alleles:
         parser.error("--pileup-single-strand-mode needs Ref and Alt on every site: the lines of %s bring no alleles" % o.pileup_sites)
+    if not o.pileup_likelihoods:
+        return
+    if o.minqual:
+        parser.error("--pileup-likelihoods cannot be combined with -Q %d: under --min-basequal the decoder drops the quality column of "
+                     "a slab none of whose bases is below the threshold, and the likelihoods need every base's quality; "
+                     "--pileup-min-basequal sets a threshold for the sites" % o.minqual)
+    o.pileup_noqual_quality = 30 if o.pileup_noqual_quality is None else o.pileup_noqual_quality
+    if not 1 <= o.pileup_noqual_quality <= 93:
+        parser.error("--pileup-noqual-quality %d: a quality of 1..93" % o.pileup_noqual_quality)
+    if o.pileup_beagle is not None:
+        if not alleles:
+            parser.error("--pileup-beagle needs Ref and Alt on every site, the two alleles of its three genotypes: the lines of %s "
+                         "bring no alleles" % o.pileup_sites)
+        if not Path(o.pileup_beagle).absolute().parent.is_dir():
+            parser.error("--pileup-beagle %s: its directory does not exist" % o.pileup_beagle)
+        if o.filename is not None and not is_stream(o.filename):
+            try:
+                same = os.path.samefile(o.filename, o.pileup_beagle)
+            except OSError:
+                same = False
+            if same:
+                parser.error("--pileup-beagle %s is the input file: the run would overwrite what it reads" % o.pileup_beagle)
 
 
 def parse_args(argv):
@@ -1155,7 +1196,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
     depth = bool(getattr(options, "depth", False)) and not sam_text
     # (--pileup-sites: likewise; the sites and their counters are resident beside the reference)
     pileup = getattr(options, "pileup_sites_list", None) if not sam_text else None
-    pileup_qual = pileup is not None and options.pileup_min_basequal > 0
+    likelihoods = pileup is not None and bool(getattr(options, "pileup_likelihoods", False))
+    pileup_qual = pileup is not None and (options.pileup_min_basequal > 0 or likelihoods)
     carry = None
     try:
         engine.set_reference(ref)
@@ -1167,6 +1209,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             engine.pileup_begin(pileup.pos, pileup.off, pileup.alleles, min_basequal=options.pileup_min_basequal,
                                 mask_ends=options.pileup_mask_ends, call=options.pileup_call, seed=options.pileup_seed,
                                 min_depth=options.pileup_min_depth, single_strand=options.pileup_single_strand_mode)
+            if likelihoods:
+                engine.pileup_likelihoods_begin(pileup_files.likelihood_table(), options.pileup_noqual_quality)
         stages.mark("reference resident")
         warned_about_quals = False
         error = None
@@ -1279,6 +1323,8 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
                     options.depth_regions_result = engine.depth_regions()
             if pileup is not None:
                 options.pileup_result = (list(ref.names),) + engine.pileup_finish() + (engine.pileup_info(),)
+                if likelihoods:
+                    options.pileup_likelihoods_result = engine.pileup_likelihoods_finish(with_sums=False)[1:]
             if kept_out is not None:
                 kept_out.commit(logger)
         # (the stream is closed first: mdx_gbam_close hands its arena back to the context, which must still be alive)
@@ -1376,6 +1422,18 @@ def _report_pileup(options, logger):
         logger.warning("--pileup-sites: at %d of %d sites the reference's base is neither Ref nor Alt; the usual sign of a list "
                        "of sites made for another build of the genome", strangers, len(sites))
     logger.debug("Pileup: %d pairs of a record and a site; a list of %d pairs a round; %d bytes of HBM", counts["pairs"], info["list_pairs"], info["bytes"])
+    if getattr(options, "pileup_likelihoods_result", None) is None:
+        return
+    # --pileup-likelihoods: the two files of the folder, the BEAGLE file and the log line
+    gl, best, bases, added = options.pileup_likelihoods_result
+    values["noqual_quality"] = options.pileup_noqual_quality
+    t0 = time.perf_counter()
+    pileup_files.write_likelihoods(options.folder / "pileup_likelihoods.tsv", names, sites, gl, best, bases)
+    (options.folder / "pileup_likelihoods_summary.tsv").write_text(pileup_files.likelihoods_summary_text(values, bases, added))
+    if getattr(options, "pileup_beagle", None) is not None:
+        pileup_files.write_beagle(options.pileup_beagle, names, sites, gl, bases)
+    logger.info(pileup_files.likelihoods_log_line(values, bases, added))
+    logger.debug("Pileup likelihoods: the files of %d sites formatted and written in %.3f s", len(sites), time.perf_counter() - t0)
 
 
 def main(argv):
@@ -1522,6 +1580,9 @@ def main(argv):
                 return 1
             if options.pileup_single_strand_mode and options.pileup_sites_list.alleles is None:
                 logger.error("--pileup-single-strand-mode needs Ref and Alt on every site: the lines of %s bring no alleles", options.pileup_sites)
+                return 1
+            if getattr(options, "pileup_beagle", None) is not None and options.pileup_sites_list.alleles is None:
+                logger.error("--pileup-beagle needs Ref and Alt on every site: the lines of %s bring no alleles", options.pileup_sites)
                 return 1
         libraries = reader.get_libraries()
         try:

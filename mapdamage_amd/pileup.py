@@ -1,11 +1,17 @@
 """--pileup-sites: the list of sites read and held to the input's header, and the files written from what
 ``DamageEngine.pileup_finish`` delivers.  Text only: the counters, the reference's letters, the depths and the calls are the
-device's (csrc/mdx_pileup.hip, the rule: csrc/mdx_pileup_key.h), nothing is counted or drawn here."""
+device's (csrc/mdx_pileup.hip, the rule: csrc/mdx_pileup_key.h), nothing is counted or drawn here.  --pileup-likelihoods: the
+table of the model's terms, which the device only adds, and the files written from ``DamageEngine.pileup_likelihoods_finish``;
+nothing of the likelihoods is added or reduced here either."""
+import gzip
+import math
+import os
 import re
+import tempfile
 
 import numpy as np
 
-from .depth import _replace_with
+from .depth import _replace_with, _umask
 
 COUNTERS = ("A+", "C+", "G+", "T+", "A-", "C-", "G-", "T-", "Deletions", "LowQual", "Other", "Masked")
 PILEUP_HEADER = "Sequence\tPosition\tId\tRef\tAlt\tRefBase\t" + "\t".join(COUNTERS) + "\tDepth"
@@ -187,3 +193,121 @@ def off_build(sites, refbase):
     letter = np.asarray(refbase, "S1").view(np.uint8)
     table = np.frombuffer(BASES.encode(), np.uint8)
     return int(((letter != table[sites.alleles[:, 0]]) & (letter != table[sites.alleles[:, 1]])).sum())
+
+
+# ---------------------------------------------------------------------- --pileup-likelihoods
+GENOTYPES = ("AA", "AC", "AG", "AT", "CC", "CG", "CT", "GG", "GT", "TT")
+LIKELIHOODS_HEADER = "Sequence\tPosition\tId\tRef\tAlt\tBases\t" + "\t".join(GENOTYPES) + "\tBest\n"
+LIKELIHOODS_SUMMARY_HEADER = "SitesFile\tMinBaseQual\tMaskEnds\tSingleStrandMode\tNoQualQuality\tSites\tSitesWithBases\tBaseObservations\tWithoutQualities\n"
+BEAGLE_HEADER = "marker\tallele1\tallele2\tInd0\tInd0\tInd0\n"
+GL_QUALITIES, GL_SCALE_BITS = 94, 24
+GL_UNIT = float(1 << GL_SCALE_BITS)
+
+
+def likelihood_table():
+    """int64 [94][3], per quality q the terms HOM, HET, NO of GATK's model (ANGSD -GL 2) as ``round(term * 2^24)``: with e =
+    min(0.75, 10^(-q/10)) the log likelihood of an observed base b under a genotype bb, under a heterozygous one that holds b,
+    under any other.  Python doubles in exactly this order, so that every build of the table is the same one; the device only
+    adds its entries (csrc/mdx_pileup_key.h)."""
+    rows = []
+    for q in range(GL_QUALITIES):
+        e = min(0.75, 10.0 ** (-q / 10.0))
+        hom = math.log(1.0 - e)
+        het = math.log((1.0 - e) / 2.0 + e / 6.0)
+        no = math.log(e / 3.0)
+        rows.append([round(math.ldexp(x, GL_SCALE_BITS)) for x in (hom, het, no)])
+    table = np.array(rows, np.int64)
+    # (a record adds at most one term to a sum and fewer than 2^31 records are added: no sum leaves its int64)
+    assert int(np.abs(table).max()) << 31 < 1 << 63
+    return table
+
+
+def genotype_index(a, b):
+    """The place of the genotype of the bases ``a`` and ``b`` (0 .. 3) in GENOTYPES."""
+    a, b = np.minimum(a, b), np.maximum(a, b)           # (numbers or arrays of them)
+    return 4 * a - a * (a - 1) // 2 + (b - a)
+
+
+def likelihoods_chunks(names, sites, gl, best, bases, chunk=PILEUP_CHUNK):
+    """pileup_likelihoods.tsv as bytes, a chunk of rows at a time: a line per site in the order of pileup.tsv; a genotype's value
+    is ``gl / 2^24 / ln 10``, the log10 of its likelihood over the best one's; ``Best`` is ``.`` where no base was taken."""
+    yield LIKELIHOODS_HEADER.encode()
+    gl = np.asarray(gl, np.int64).reshape(-1, len(GENOTYPES))
+    row_format = "%s\t%d\t%s\t%s\t%s\t%d" + "\t%.6f" * len(GENOTYPES) + "\t%s\n"
+    for lo in range(0, len(sites), chunk):
+        hi = min(len(sites), lo + chunk)
+        tid, pos = sites.tid[lo:hi].tolist(), (sites.pos[lo:hi].astype(np.int64) + 1).tolist()
+        if sites.alleles is not None:
+            ref, alt = ([BASES[b] for b in sites.alleles[lo:hi, q].tolist()] for q in (0, 1))
+        else:
+            ref = alt = ["."] * (hi - lo)
+        values = (gl[lo:hi].astype(np.float64) / GL_UNIT / math.log(10.0)).tolist()
+        n, first = np.asarray(bases[lo:hi]).tolist(), np.asarray(best[lo:hi]).tolist()
+        out = []
+        for k in range(hi - lo):
+            out.append(row_format % ((names[tid[k]], pos[k], sites.ids[lo + k], ref[k], alt[k], n[k]) + tuple(values[k])
+                                     + (GENOTYPES[first[k]] if n[k] else ".",)))
+        yield "".join(out).encode()
+
+
+def write_likelihoods(path, names, sites, gl, best, bases):
+    """pileup_likelihoods.tsv under a temporary name in ``path``'s directory, moved into place at the end."""
+    _replace_with(path, likelihoods_chunks(names, sites, gl, best, bases))
+
+
+def beagle_chunks(names, sites, gl, bases, chunk=PILEUP_CHUNK):
+    """The BEAGLE GL file of ``angsd -doGlf 2`` as bytes: per site ``<sequence>_<position>``, ref and alt as 0 1 2 3 for A C G
+    T, and the likelihoods of ref/ref, ref/alt and alt/alt, ``exp(gl / 2^24)`` over their sum — a third each where no base was
+    taken.  The list brings alleles."""
+    yield BEAGLE_HEADER.encode()
+    gl = np.asarray(gl, np.int64).reshape(-1, len(GENOTYPES))
+    for lo in range(0, len(sites), chunk):
+        hi = min(len(sites), lo + chunk)
+        ref, alt = sites.alleles[lo:hi, 0].astype(np.int64), sites.alleles[lo:hi, 1].astype(np.int64)
+        rows = np.arange(hi - lo)
+        three = np.stack([gl[lo:hi][rows, genotype_index(x, y)] for x, y in ((ref, ref), (ref, alt), (alt, alt))], axis=1)
+        # (over the largest of the three, which leaves the quotients as they are: at a deep site whose bases are neither allele
+        # all three are far below the best genotype and would underflow to 0 / 0)
+        like = np.exp((three - three.max(axis=1, keepdims=True)).astype(np.float64) / GL_UNIT)
+        like /= like.sum(axis=1, keepdims=True)
+        like[np.asarray(bases[lo:hi]) == 0] = 1.0 / 3.0
+        tid, pos = sites.tid[lo:hi].tolist(), (sites.pos[lo:hi].astype(np.int64) + 1).tolist()
+        ref, alt, like = ref.tolist(), alt.tolist(), like.tolist()
+        yield "".join("%s_%d\t%d\t%d\t%.6f\t%.6f\t%.6f\n" % ((names[tid[k]], pos[k], ref[k], alt[k]) + tuple(like[k])) for k in range(hi - lo)).encode()
+
+
+def write_beagle(path, names, sites, gl, bases):
+    """--pileup-beagle PATH under a temporary name in its directory, moved into place at the end; any failure removes it.  A
+    path that ends in ``.gz`` is gzip with a zero mtime and no name, so the same run writes the same bytes."""
+    path = os.path.abspath(str(path))
+    if not path.endswith(".gz"):
+        _replace_with(path, beagle_chunks(names, sites, gl, bases))
+        return
+    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(path))
+    try:
+        with os.fdopen(fd, "wb") as raw, gzip.GzipFile(filename="", mode="wb", fileobj=raw, mtime=0) as out:
+            for text in beagle_chunks(names, sites, gl, bases):
+                out.write(text)
+        os.chmod(tmp, 0o666 & ~_umask())
+        os.replace(tmp, path)
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
+def likelihoods_summary_text(options, bases, counts):
+    """pileup_likelihoods_summary.tsv: one line of the option values, the sites, those with at least one base, the base
+    observations and those of them from records without qualities.  ``options``: summary_text's and noqual_quality."""
+    bases = np.asarray(bases, np.int64)
+    return LIKELIHOODS_SUMMARY_HEADER + "%s\t%d\t%d,%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % (
+        options["path"], options["min_basequal"], options["mask_ends"][0], options["mask_ends"][1], int(bool(options["single_strand"])),
+        options["noqual_quality"], len(bases), int((bases >= 1).sum()), counts["added"], counts["without_qualities"])
+
+
+def likelihoods_log_line(options, bases, counts):
+    bases = np.asarray(bases, np.int64)
+    return ("Pileup likelihoods: %d sites, %d with bases, %d base observations (%d from records without qualities, taken at %d)"
+            % (len(bases), int((bases >= 1).sum()), counts["added"], counts["without_qualities"], options["noqual_quality"]))

@@ -9,12 +9,17 @@ cold processes, each under a time limit of its own, alternating:
   sparse_masked   `--pileup-sites sparse.txt --pileup-min-basequal 20 --pileup-mask-ends 2,2`: the stream brings its qualities
   write_kept      `--write-kept x.kept.bam`: the first half of the route the option replaces (the genotyper that inflates the
                   file again is not timed)
+with --likelihoods these instead of the last two:
+  sparse_gl       `--pileup-sites sparse.txt --pileup-likelihoods`
+  dense_gl        `--pileup-sites dense.txt --pileup-likelihoods`
+and then per list the difference to the same list without the option, and from the log the seconds the host took to format and
+write the likelihood files.
 
 Reported per command: the wall times, their median and spread (max - min); the medians' differences from `plain`, and
 plain - parent_plain; from the log the option's line.  The claim to check: plain - parent_plain is within the repeats' spread
 (nothing new runs when the option is off).  One JSON line on stdout.
 
-    python tools/pileup_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR]"""
+    python tools/pileup_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR] [--likelihoods]"""
 import argparse
 import json
 import os
@@ -61,6 +66,7 @@ def main():
     ap.add_argument("--dir", help="where the BAM, FASTA and outputs go (a temporary folder by default, removed afterwards)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
+    ap.add_argument("--likelihoods", action="store_true", help="time --pileup-likelihoods on either list instead of sparse_masked and write_kept")
     args = ap.parse_args()
     import numpy as np
 
@@ -88,9 +94,12 @@ def main():
         legs = [("plain", ROOT, [])]
         if args.parent_root:
             legs.append(("parent_plain", os.path.abspath(args.parent_root), []))
-        legs += [("sparse", ROOT, ["--pileup-sites", sparse]), ("dense", ROOT, ["--pileup-sites", dense]),
-                 ("sparse_masked", ROOT, ["--pileup-sites", sparse, "--pileup-min-basequal", "20", "--pileup-mask-ends", "2,2"]),
-                 ("write_kept", ROOT, ["--write-kept", os.path.join(work, "x.kept.bam")])]
+        legs += [("sparse", ROOT, ["--pileup-sites", sparse]), ("dense", ROOT, ["--pileup-sites", dense])]
+        if args.likelihoods:
+            legs += [("sparse_gl", ROOT, ["--pileup-sites", sparse, "--pileup-likelihoods"]), ("dense_gl", ROOT, ["--pileup-sites", dense, "--pileup-likelihoods"])]
+        else:
+            legs += [("sparse_masked", ROOT, ["--pileup-sites", sparse, "--pileup-min-basequal", "20", "--pileup-mask-ends", "2,2"]),
+                     ("write_kept", ROOT, ["--write-kept", os.path.join(work, "x.kept.bam")])]
         times = {name: [] for name, _, _ in legs}
         status = 0
         for _ in range(args.repeats):
@@ -117,9 +126,18 @@ def main():
                 m = re.search(r"Pileup: (\d+) pairs of a record and a site; a list of (\d+) pairs a round; (\d+) bytes of HBM", log)
                 result[name].update(pairs=int(m.group(1)), list_pairs=int(m.group(2)), hbm_bytes=int(m.group(3)),
                                     pileup_tsv_bytes=os.path.getsize(os.path.join(work, name, "pileup.tsv")))
+            line = re.search(r"Pileup likelihoods: \d+ sites, .*", log)
+            if line:
+                m = re.search(r"Pileup likelihoods: the files of \d+ sites formatted and written in ([0-9.]+) s", log)
+                result[name].update(likelihoods_log_line=line.group(0), likelihoods_format_s=float(m.group(1)),
+                                    likelihoods_tsv_bytes=os.path.getsize(os.path.join(work, name, "pileup_likelihoods.tsv")))
         if status == 0:
-            for name in ("sparse", "dense", "sparse_masked", "write_kept"):
-                result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            for name, _, _ in legs:
+                if name not in ("plain", "parent_plain"):
+                    result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
+            if args.likelihoods:
+                for name in ("sparse", "dense"):
+                    result["%s_gl_minus_%s_s" % (name, name)] = round(result[name + "_gl"]["median_s"] - result[name]["median_s"], 3)
             if args.parent_root:
                 result["plain_minus_parent_plain_s"] = round(result["plain"]["median_s"] - result["parent_plain"]["median_s"], 3)
             tables = {name: [open(os.path.join(work, name, f)).read() for f in FILES] for name, _, _ in legs}
