@@ -587,6 +587,38 @@ int mdx_pileup_likelihoods_begin(mdx_ctx *ctx, const int64_t *table /* [94][3] *
 int mdx_pileup_likelihoods_finish(mdx_ctx *ctx, int64_t *sums /* [n_sites][24] or NULL */, int64_t *gl /* [n_sites][10] */, uint8_t *best,
                                   uint32_t *bases /* [n_sites] each */, uint64_t *counts /* [2] */);
 
+/* ---- The same likelihoods under a damage profile: the position-specific deamination rates of a misincorporation.txt inside
+ * the error model (as ATLAS and snpAD have them), instead of mask5 / mask3 (the rule: csrc/mdx_pileup_key.h).
+ *
+ * A pair adds exactly when it adds above, with the same quality.  Its base has two distances in query bases of the stored query
+ * without terminal soft clips, [qs, qe) — insertions count, D and N columns do not; the windows of mask5 / mask3, not the
+ * alignment columns of misincorporation.txt —: z5 = q - qs + 1 and z3 = qe - q for a forward record, exchanged for a reverse
+ * one; a distance below 1 (a CIGAR that disagrees with its SEQ) is taken as 1.  Each indexes row min(z, n_rows) - 1 of its end;
+ * the last row is the pooled tail.  In stored orientation a forward record has ct = d5[z5], ga = d3[z3], a reverse record ct =
+ * d3[z3], ga = d5[z5].  An observed C or T is the source s or the product t of the channel C>T with r = ct, an observed G or A of
+ * G>A with r = ga; with Pss = (1 - r)(1 - e) + r e / 3 and Pst = r (1 - e) + (1 - r) e / 3 the table holds, per end, row and
+ * quality, round(2^24 * x) for the nine x
+ *   observed s:  log Pss (genotype ss), log(Pss / 2 + e / 6) (s and another), log(e / 3) (no s)
+ *   observed t:  log(1 - e) (tt), log(Pst / 2 + (1 - e) / 2) (st), log Pst (ss), log((1 - e) / 2 + e / 6) (t and another, not s),
+ *                log(Pst / 2 + e / 6) (s and another, not t), log(e / 3) (neither)
+ * end 0 with the 5' C>T rates, end 1 with the 3' G>A rates.  A site's sums are int64 [2 strands][10 genotypes AA AC AG AT CC CG
+ * CT GG GT TT], 160 bytes a site; a pair adds ten terms to its strand's row.  At the finish logL is the eligible strands' rows
+ * summed.
+ *
+ *   mdx_pileup_likelihoods_damage_begin   behind mdx_pileup_begin and in front of the first mdx_pileup_add, as
+ *                      mdx_pileup_likelihoods_begin, which it excludes within the same pileup: whichever of the two is called
+ *                      second is MDX_ERR_STATE.  table [2][n_rows][94][9]; n_rows = K + 1, 2..255; noqual_quality 1..93.
+ *                      Allocates and zeroes the sums and copies the table (n_rows * 13 536 bytes) to the device.  A later
+ *                      mdx_pileup_begin or a new reference releases both, mdx_reset zeroes the sums, mdx_destroy frees them;
+ *                      mdx_pileup_info's bytes include them.  Called again it zeroes the sums and takes the new table.
+ *   mdx_pileup_add     launches the add kernel's third variant while these sums exist: ten 64-bit atomics beside the
+ *                      counter's, the nine terms read from the table in device memory.
+ *   mdx_pileup_likelihoods_finish   serves both models; in this one sums is [n_sites][20], everything else as above.
+ *
+ * Limit: every probability is at least e / 3, so no entry is larger in magnitude than the plain table's: the same bound. */
+int mdx_pileup_likelihoods_damage_begin(mdx_ctx *ctx, const int64_t *table /* [2][n_rows][94][9] */, int32_t n_rows /* K + 1 */,
+                                        int32_t noqual_quality);
+
 /* Zero all accumulators (new run with the same options and reference). */
 int mdx_reset(mdx_ctx *ctx);
 

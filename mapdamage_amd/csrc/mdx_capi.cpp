@@ -243,6 +243,10 @@ struct mdx_ctx {
         unsigned long long *gl_counts = nullptr;   // [2]: pairs that added, those of them from records without qualities
         int64_t *gl_table = nullptr;           // [94][3]
         int32_t noqual = 0;
+        // ... under a damage profile (mdx_pileup_likelihoods_damage_begin): sums [n_sites][20], gl_table [2][gld_rows][94][9]
+        int32_t gld_rows = 0;                  // K + 1; 0: the plain model
+        size_t sums_per_site() const { return gld_rows ? MDX_GLD_SUMS : MDX_GL_SUMS; }
+        size_t table_entries() const { return gld_rows ? (size_t)2 * (size_t)gld_rows * MDX_GL_QUALITIES * MDX_GLD_TERMS : (size_t)MDX_GL_QUALITIES * MDX_GL_TERMS; }
     } pileup;
     bool counted = false;          // records were tabulated since mdx_create / mdx_reset
     int lgd_copies = MDX_LGD_COPIES;   // copies of the dense length histogram (mdx_lgd_copies_for)
@@ -414,7 +418,7 @@ int pileup_clear(mdx_ctx *c) {
     HIP_TRY(c, hipMemsetAsync(p.counters, 0, (size_t)p.n_sites * MDX_PILEUP_COUNTERS * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(p.counts, 0, 4 * 8, c->stream));
     if (p.sums) {
-        HIP_TRY(c, hipMemsetAsync(p.sums, 0, (size_t)p.n_sites * MDX_GL_SUMS * 8, c->stream));
+        HIP_TRY(c, hipMemsetAsync(p.sums, 0, (size_t)p.n_sites * p.sums_per_site() * 8, c->stream));
         HIP_TRY(c, hipMemsetAsync(p.gl_counts, 0, 2 * 8, c->stream));
     }
     p.added = 0;
@@ -2048,8 +2052,9 @@ int mdx_pileup_add(mdx_ctx *c, const mdx_batch *b) {
     k.k5 = (uint32_t)p.cfg.mask5; k.k3 = (uint32_t)p.cfg.mask3; k.min_qual = (uint32_t)p.cfg.min_basequal;
     if (p.sums) {
         MdxPileupSums gl{};
-        gl.sums = p.sums; gl.counts = p.gl_counts; gl.table = p.gl_table; gl.noqual = (uint32_t)p.noqual;
-        mdx_k_pileup_add_likelihoods(k, pileup_sites(c), p.list, p.counts, gl, c->stream);
+        gl.sums = p.sums; gl.counts = p.gl_counts; gl.table = p.gl_table; gl.noqual = (uint32_t)p.noqual; gl.n_rows = (uint32_t)p.gld_rows;
+        if (p.gld_rows) mdx_k_pileup_add_likelihoods_damage(k, pileup_sites(c), p.list, p.counts, gl, c->stream);
+        else mdx_k_pileup_add_likelihoods(k, pileup_sites(c), p.list, p.counts, gl, c->stream);
     } else {
         mdx_k_pileup_add(k, pileup_sites(c), p.list, p.counts, c->stream);
     }
@@ -2097,7 +2102,7 @@ int mdx_pileup_info(mdx_ctx *c, uint64_t *info) {
     const auto &p = c->pileup;
     info[0] = (uint64_t)p.list; info[1] = (uint64_t)mdx_k_pileup_block();
     info[2] = (uint64_t)p.n_sites * (MDX_PILEUP_COUNTERS * 4 + 4 + (p.has_alleles ? 2 : 0)) + ((uint64_t)c->n_contig + 1) * 8 + 4 * 8;
-    if (p.sums) info[2] += (uint64_t)p.n_sites * MDX_GL_SUMS * 8 + MDX_GL_QUALITIES * MDX_GL_TERMS * 8 + 2 * 8;
+    if (p.sums) info[2] += (uint64_t)p.n_sites * p.sums_per_site() * 8 + (uint64_t)p.table_entries() * 8 + 2 * 8;
     info[3] = (uint64_t)p.n_sites;
     return MDX_OK;
 }
@@ -2110,6 +2115,7 @@ int mdx_pileup_likelihoods_begin(mdx_ctx *c, const int64_t *table, int32_t noqua
     if (noqual_quality < 1 || noqual_quality >= MDX_GL_QUALITIES)
         return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_begin: noqual_quality " + std::to_string(noqual_quality) + " is not 1..93");
     if (p.added) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_begin: records have been added since mdx_pileup_begin; the sums would lack them");
+    if (p.gld_rows) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_begin: this pileup has the sums of mdx_pileup_likelihoods_damage_begin; one model per pileup");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!p.sums) {
@@ -2135,10 +2141,53 @@ int mdx_pileup_likelihoods_begin(mdx_ctx *c, const int64_t *table, int32_t noqua
     return MDX_OK;
 }
 
+int mdx_pileup_likelihoods_damage_begin(mdx_ctx *c, const int64_t *table, int32_t n_rows, int32_t noqual_quality) {
+    if (!c) return MDX_ERR_ARG;
+    auto &p = c->pileup;
+    if (!p.on) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_damage_begin: call mdx_pileup_begin first");
+    if (!table) return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_damage_begin: null table");
+    if (n_rows < 2 || n_rows > MDX_GLD_MAX_ROWS)
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_damage_begin: n_rows " + std::to_string(n_rows) + " is not 2..255 (K + 1, K 1..254)");
+    if (noqual_quality < 1 || noqual_quality >= MDX_GL_QUALITIES)
+        return fail(c, MDX_ERR_ARG, "mdx_pileup_likelihoods_damage_begin: noqual_quality " + std::to_string(noqual_quality) + " is not 1..93");
+    if (p.added) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_damage_begin: records have been added since mdx_pileup_begin; the sums would lack them");
+    if (p.sums && !p.gld_rows)
+        return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_damage_begin: this pileup has the sums of mdx_pileup_likelihoods_begin; one model per pileup");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (p.sums && p.gld_rows != n_rows) {       // called again with another K: the table has another size
+        (void)hipFree(p.gl_table);
+        p.gl_table = nullptr;
+    }
+    const size_t bytes = (size_t)p.n_sites * MDX_GLD_SUMS * 8, table_bytes = (size_t)2 * (size_t)n_rows * MDX_GL_QUALITIES * MDX_GLD_TERMS * 8;
+    hipError_t e = hipSuccess;
+    if (!p.sums && hipMalloc((void **)&p.sums, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        p.sums = nullptr;
+        return fail(c, MDX_ERR_HIP, "mdx_pileup_likelihoods_damage_begin: out of device memory for the sums of " + std::to_string(bytes) + " bytes (160 per site of " +
+                                    std::to_string(p.n_sites) + ")");
+    }
+    if (!p.gl_counts) e = hipMalloc((void **)&p.gl_counts, 2 * 8);
+    if (e == hipSuccess && !p.gl_table) e = hipMalloc((void **)&p.gl_table, table_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        for (void *q : {(void *)p.sums, (void *)p.gl_counts, (void *)p.gl_table}) if (q) (void)hipFree(q);
+        p.sums = p.gl_counts = nullptr; p.gl_table = nullptr; p.gld_rows = 0;
+        return fail(c, MDX_ERR_HIP, std::string("mdx_pileup_likelihoods_damage_begin: ") + hipGetErrorString(e));
+    }
+    p.noqual = noqual_quality;
+    p.gld_rows = n_rows;
+    HIP_TRY(c, hipMemcpy(p.gl_table, table, table_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemsetAsync(p.sums, 0, bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(p.gl_counts, 0, 2 * 8, c->stream));
+    return MDX_OK;
+}
+
 int mdx_pileup_likelihoods_finish(mdx_ctx *c, int64_t *sums, int64_t *gl, uint8_t *best, uint32_t *bases, uint64_t *counts) {
     if (!c) return MDX_ERR_ARG;
     auto &p = c->pileup;
-    if (!p.on || !p.sums) return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_finish: call mdx_pileup_begin and mdx_pileup_likelihoods_begin first");
+    if (!p.on || !p.sums)
+        return fail(c, MDX_ERR_STATE, "mdx_pileup_likelihoods_finish: call mdx_pileup_begin and mdx_pileup_likelihoods_begin or mdx_pileup_likelihoods_damage_begin first");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     const size_t n = (size_t)p.n_sites;
     DevBuf out;     // gl [n][10] | bases [n] | best [n]
@@ -2150,10 +2199,11 @@ int mdx_pileup_likelihoods_finish(mdx_ctx *c, int64_t *sums, int64_t *gl, uint8_
     int64_t *d_gl = (int64_t *)out.p;
     uint32_t *d_bases = (uint32_t *)((uint8_t *)out.p + bases_at);
     uint8_t *d_best = (uint8_t *)out.p + best_at;
-    mdx_k_pileup_likelihoods(pileup_sites(c), p.sums, p.cfg.single_strand, d_gl, d_best, d_bases, c->stream);
+    if (p.gld_rows) mdx_k_pileup_likelihoods_damage(pileup_sites(c), p.sums, p.cfg.single_strand, d_gl, d_best, d_bases, c->stream);
+    else mdx_k_pileup_likelihoods(pileup_sites(c), p.sums, p.cfg.single_strand, d_gl, d_best, d_bases, c->stream);
     hipError_t e = hipGetLastError();
     unsigned long long w[2] = {0, 0};
-    if (e == hipSuccess && sums) e = hipMemcpyAsync(sums, p.sums, n * MDX_GL_SUMS * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && sums) e = hipMemcpyAsync(sums, p.sums, n * p.sums_per_site() * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && gl) e = hipMemcpyAsync(gl, d_gl, n * MDX_GL_GENOTYPES * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && best) e = hipMemcpyAsync(best, d_best, n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && bases) e = hipMemcpyAsync(bases, d_bases, 4 * n, hipMemcpyDeviceToHost, c->stream);

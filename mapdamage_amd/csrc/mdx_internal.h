@@ -570,9 +570,16 @@ struct MdxPileupSums {
     unsigned long long *counts;     // [2] pairs that added, those of them from records without qualities
     const int64_t *table;           // [MDX_GL_QUALITIES][MDX_GL_TERMS] on the device
     uint32_t noqual;                // the row of a record without qualities
+    // under a damage profile (mdx_pileup_likelihoods_damage_begin): sums [n_sites][MDX_GLD_SUMS], table [2][n_rows]
+    // [MDX_GL_QUALITIES][MDX_GLD_TERMS]; 0 without one
+    uint32_t n_rows;
 };
 void mdx_k_pileup_add_likelihoods(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, const MdxPileupSums &gl,
                                   hipStream_t s);                                           // mdx_k_pileup_add and the sums
+void mdx_k_pileup_add_likelihoods_damage(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, const MdxPileupSums &gl,
+                                         hipStream_t s);                                    // ... under a damage profile
+void mdx_k_pileup_likelihoods_damage(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best,
+                                     uint32_t *bases, hipStream_t s);
 // gl [n_sites][MDX_GL_GENOTYPES], best and bases [n_sites], all on the device
 void mdx_k_pileup_likelihoods(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best, uint32_t *bases,
                               hipStream_t s);

@@ -16,6 +16,9 @@
 //   call  a lane per site: the reference's letter, the depth, the call (mdx_pileup_call)
 //   likelihoods (mdx_pileup_likelihoods_begin)  the add kernel's variant puts the three terms of a pair's quality beside its
 //         counter, into the site's 24 int64 sums; a lane per site makes the ten values from them (mdx_pileup_likelihoods)
+//   likelihoods under a damage profile (mdx_pileup_likelihoods_damage_begin)  a third variant: the pair's lane finds its base's
+//         two distances to the query's ends, reads the nine terms of its base, strand, quality and distance from the table in
+//         global memory and adds the ten genotypes' terms to the site's 20 int64 sums; a lane per site folds the strands
 // A site's index comes from site_off alone, which the host has checked against n_sites: no address outside the counters is
 // formed.
 #include "mdx_internal.h"
@@ -56,7 +59,12 @@ __device__ __forceinline__ int64_t first_site(const int32_t *site_pos, int64_t l
 // once: a lane's row depends on its own pair's quality, so a lookup in constant memory would be serialised quality by quality
 // over the wavefront (the scalar path takes one address at a time), and one in global memory is a load per pair; the LDS takes
 // 64 different rows at once.  Without GL nothing of it is compiled: pileup_add_kernel is the kernel as it was.
-template <bool GL>
+// GLD: the variant of --pileup-damage-profile.  Its table, [2][K + 1][94][9] int64, is 284 KB at K = 20 and does not fit the LDS:
+// a pair reads its row of nine terms, 72 contiguous bytes, from global memory — the whole table stays in the L2, and the rows
+// near the read ends and the common qualities in the L1 — and adds ten 64-bit atomics, one per genotype, to its strand's row of
+// the site's sums.  Nothing is staged in the LDS: which 72 bytes a pair needs is known only once its CIGAR is walked.
+enum { MDX_PU_PLAIN = 0, MDX_PU_GL = 1, MDX_PU_GLD = 2 };
+template <int MODE>
 __device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const MdxPileupSites &st, int list, u64 *counts, const MdxPileupSums &gl) {
     __shared__ MdxPileupRecord rec[MDX_PU_BLOCK];
     __shared__ int64_t rec_site[MDX_PU_BLOCK];          // a record's first site
@@ -64,6 +72,7 @@ __device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const Mdx
     __shared__ u64 wave_tot[MDX_PU_BLOCK / 64];
     __shared__ uint32_t list_site[MDX_PU_LIST];         // a pair's site, as its distance from the record's first
     __shared__ uint16_t list_rec[MDX_PU_LIST];          // ... and its record, as its lane
+    constexpr bool GL = MODE == MDX_PU_GL, GLD = MODE == MDX_PU_GLD;
     __shared__ int64_t terms[GL ? MDX_GL_QUALITIES * MDX_GL_TERMS : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * MDX_PU_BLOCK + threadIdx.x;
@@ -122,10 +131,10 @@ __device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const Mdx
         for (uint32_t e = threadIdx.x; e < held; e += MDX_PU_BLOCK) {
             const uint32_t l = list_rec[e];
             const int64_t site = rec_site[l] + (int64_t)list_site[e];
-            if constexpr (!GL) {
+            if constexpr (!GL && !GLD) {
                 const int cls = mdx_pileup_site(k, rec[l], (int64_t)st.site_pos[site]);
                 if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
-            } else {
+            } else if constexpr (GL) {
                 uint32_t qi = 0;
                 const int cls = mdx_pileup_site_quality(k, rec[l], (int64_t)st.site_pos[site], gl.noqual, &qi);
                 if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
@@ -141,11 +150,32 @@ __device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const Mdx
                 // two numbers are the wavefront's
                 n_added += (u64)__popcll(__ballot(adds));
                 n_noqual += (u64)__popcll(__ballot(noqual));
+            } else {
+                uint32_t qi = 0, q = 0;
+                const int cls = mdx_pileup_site_quality_at(k, rec[l], (int64_t)st.site_pos[site], gl.noqual, &qi, &q);
+                if (cls >= 0) atomicAdd(&st.counters[(size_t)site * MDX_PILEUP_COUNTERS + (size_t)cls], 1u);
+                const bool adds = cls >= 0 && cls < 8, noqual = adds && !rec[l].has_qual;
+                if (adds) {
+                    // (both rows < n_rows, qi < MDX_GL_QUALITIES, a term < MDX_GLD_TERMS: the nine lie inside the table; cls < 8: the
+                    // row inside the site's sums)
+                    uint32_t row5, row3;
+                    mdx_pileup_damage_rows(rec[l], q, gl.n_rows, &row5, &row3);
+                    const int64_t *t = gl.table + mdx_pileup_damage_entry(cls, qi, row5, row3, gl.n_rows);
+                    u64 *row = gl.sums + (size_t)site * MDX_GLD_SUMS + (size_t)(cls >> 2) * MDX_GL_GENOTYPES;
+                    const uint32_t b = (uint32_t)cls & 3u;
+                    int g = 0;
+#pragma unroll
+                    for (int a1 = 0; a1 < 4; a1++)
+#pragma unroll
+                        for (int a2 = a1; a2 < 4; a2++, g++) atomicAdd(&row[g], (u64)t[mdx_pileup_damage_term(b, a1, a2)]);
+                }
+                n_added += (u64)__popcll(__ballot(adds));
+                n_noqual += (u64)__popcll(__ballot(noqual));
             }
         }
         __syncthreads();
     }
-    if constexpr (GL) {
+    if constexpr (GL || GLD) {
         if (lane == 0) {
             if (n_added) atomicAdd(&gl.counts[0], n_added);
             if (n_noqual) atomicAdd(&gl.counts[1], n_noqual);
@@ -154,10 +184,13 @@ __device__ __forceinline__ void pileup_add_body(const MdxPileupKey &k, const Mdx
 }
 
 __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts) {
-    pileup_add_body<false>(k, st, list, counts, MdxPileupSums{});
+    pileup_add_body<MDX_PU_PLAIN>(k, st, list, counts, MdxPileupSums{});
 }
 __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_likelihoods_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts, MdxPileupSums gl) {
-    pileup_add_body<true>(k, st, list, counts, gl);
+    pileup_add_body<MDX_PU_GL>(k, st, list, counts, gl);
+}
+__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_add_likelihoods_damage_kernel(MdxPileupKey k, MdxPileupSites st, int list, u64 *counts, MdxPileupSums gl) {
+    pileup_add_body<MDX_PU_GLD>(k, st, list, counts, gl);
 }
 
 // the largest t in [0, n_contig) with off[t] <= g: the sequence whose slice holds site g (behind a row of empty slices, the last)
@@ -229,6 +262,37 @@ __global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_likelihoods_kernel(MdxPil
     bases[g] = n;
 }
 
+// the same under a damage profile: the site's sums (160 bytes) are the ten genotypes per strand already
+__global__ __launch_bounds__(MDX_PU_BLOCK) void pileup_likelihoods_damage_kernel(MdxPileupSites st, const u64 *sums, int single_strand, int64_t *gl,
+                                                                                 uint8_t *best, uint32_t *bases) {
+    const int64_t g = (int64_t)blockIdx.x * MDX_PU_BLOCK + threadIdx.x;
+    if (g >= st.n_sites) return;
+    int64_t S[MDX_GLD_SUMS];
+    const ulonglong2 *row = (const ulonglong2 *)(sums + (size_t)g * MDX_GLD_SUMS);         // (160 bytes a row: aligned to 16)
+#pragma unroll
+    for (int q = 0; q < MDX_GLD_SUMS / 2; q++) {
+        const ulonglong2 w = row[q];
+        S[2 * q] = (int64_t)w.x; S[2 * q + 1] = (int64_t)w.y;
+    }
+    uint32_t c[8];
+    const uint4 *crow = (const uint4 *)(st.counters + (size_t)g * MDX_PILEUP_COUNTERS);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const uint4 w = crow[q];
+        c[4 * q] = w.x; c[4 * q + 1] = w.y; c[4 * q + 2] = w.z; c[4 * q + 3] = w.w;
+    }
+    const int ref = st.alleles ? (int)st.alleles[2 * g] : -1, alt = st.alleles ? (int)st.alleles[2 * g + 1] : -1;
+    int64_t v[MDX_GL_GENOTYPES];
+    uint8_t first;
+    uint32_t n;
+    mdx_pileup_likelihoods_damage(S, c, single_strand, ref, alt, v, &first, &n);
+    ulonglong2 *out = (ulonglong2 *)(gl + (size_t)g * MDX_GL_GENOTYPES);
+#pragma unroll
+    for (int q = 0; q < MDX_GL_GENOTYPES / 2; q++) out[q] = make_ulonglong2((u64)v[2 * q], (u64)v[2 * q + 1]);
+    best[g] = first;
+    bases[g] = n;
+}
+
 }  // namespace
 
 void mdx_k_pileup_add(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, hipStream_t s) {
@@ -244,6 +308,20 @@ void mdx_k_pileup_add_likelihoods(const MdxPileupKey &k, const MdxPileupSites &s
     if (list < 1) list = 1;
     if (list > MDX_PU_LIST) list = MDX_PU_LIST;
     pileup_add_likelihoods_kernel<<<(unsigned)((k.n + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(k, st, list, counts, gl);
+}
+
+void mdx_k_pileup_add_likelihoods_damage(const MdxPileupKey &k, const MdxPileupSites &st, int list, unsigned long long *counts, const MdxPileupSums &gl,
+                                         hipStream_t s) {
+    if (k.n <= 0) return;
+    if (list < 1) list = 1;
+    if (list > MDX_PU_LIST) list = MDX_PU_LIST;
+    pileup_add_likelihoods_damage_kernel<<<(unsigned)((k.n + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(k, st, list, counts, gl);
+}
+
+void mdx_k_pileup_likelihoods_damage(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best, uint32_t *bases,
+                                     hipStream_t s) {
+    if (st.n_sites <= 0) return;
+    pileup_likelihoods_damage_kernel<<<(unsigned)((st.n_sites + MDX_PU_BLOCK - 1) / MDX_PU_BLOCK), MDX_PU_BLOCK, 0, s>>>(st, sums, single_strand, gl, best, bases);
 }
 
 void mdx_k_pileup_likelihoods(const MdxPileupSites &st, const unsigned long long *sums, int single_strand, int64_t *gl, uint8_t *best, uint32_t *bases,

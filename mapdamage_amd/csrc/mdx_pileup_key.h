@@ -31,8 +31,10 @@
 //
 // Offsets are clamped to their columns, as the other rules clamp them: no byte outside a column is read.
 //
-// The genotype likelihoods at the same sites (--pileup-likelihoods): at the end of this file.
+// The genotype likelihoods at the same sites (--pileup-likelihoods), and those under a damage profile
+// (--pileup-damage-profile): at the end of this file.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "mdx_depth_key.h"
 
@@ -314,6 +316,124 @@ MDX_PU_FN void mdx_pileup_likelihoods(const int64_t *S, const uint32_t *c, int s
             if (g == 0 || v > top) { top = v; first = g; }
         }
     for (g = 0; g < MDX_GL_GENOTYPES; g++) gl[g] -= top;
+    *best = (uint8_t)first;
+    *bases = n;
+}
+
+// ---- The same likelihoods under a damage profile (mdx_pileup_likelihoods_damage_begin, --pileup-damage-profile): the
+// position-specific deamination rates of a misincorporation.txt inside the error model, as ATLAS and snpAD put them there,
+// instead of masking the ends.
+//
+// A pair adds exactly when mdx_pileup_site_quality says it adds, with the same quality.  It has two distances, counted in query
+// bases of the stored query [qs, qe) as mdx_pileup_open finds it (insertions count, D and N columns do not — the windows of
+// --pileup-mask-ends, not the table's alignment columns): with q the SEQ index of its base, a forward record has z5 = q - qs + 1
+// and z3 = qe - q, a reverse record (stored reverse-complemented) z5 = qe - q and z3 = q - qs + 1.  A distance below 1, which
+// only a record whose CIGAR and SEQ disagree can have (a base outside [qs, qe), or no query at all: qs = qe = 0), is taken as 1.
+// The row of either end is min(z, n_rows) - 1: n_rows = K + 1, the last row the pooled tail.
+//
+// In the stored orientation a forward record's C>T rate is ct = d5[z5] and its G>A rate ga = d3[z3]; a reverse record's are ct =
+// d3[z3] and ga = d5[z5] (the molecule's 5' C>T shows as a stored G>A at the stored right end).  An observed base is the source
+// s or the product t of exactly one channel — C and T of C>T, G and A of G>A — with that rate r, and with e = min(0.75,
+// 10^(-q / 10)), Pss = (1 - r)(1 - e) + r e / 3, Pst = r (1 - e) + (1 - r) e / 3 its term under a diploid genotype is one of nine,
+// MDX_GLD_*: observed s under ss, s + another, no s; observed t under tt, st, ss, t + another (not s), s + another (not t),
+// neither.  The caller brings them as int64 [2 ends][n_rows][94][9] of round(term * 2^24) (mapdamage_amd/pileup.py builds the
+// table): end 0 the 5' rates, end 1 the 3' rates.  With r = 0 a row is HOM HET NO HOM HET NO HET NO NO of the plain table.
+//
+// A site's sums are int64 [2 strands][10 genotypes], AA AC AG AT CC CG CT GG GT TT, to which a pair adds its ten terms on its
+// strand's row: integers again, the same in any order.  Every probability is at least e / 3, so no term is larger in magnitude
+// than the plain table's NO and the plain limit holds.  The finish (mdx_pileup_likelihoods_damage): logL = the eligible strands'
+// rows summed (mdx_pileup_strands), gl = logL - max, best the first genotype at the maximum, bases the eligible base counters
+// summed; a site without bases has ten zeros and best 0.
+#define MDX_GLD_TERMS 9
+#define MDX_GLD_SUMS 20                 // [2][10]
+#define MDX_GLD_MAX_ROWS 255            // K + 1, K <= 254
+enum { MDX_GLD_S_SS = 0, MDX_GLD_S_SX = 1, MDX_GLD_S_NO = 2, MDX_GLD_T_TT = 3, MDX_GLD_T_ST = 4, MDX_GLD_T_SS = 5, MDX_GLD_T_TX = 6, MDX_GLD_T_SX = 7,
+       MDX_GLD_T_NO = 8 };
+
+// mdx_pileup_site_quality, and for a pair that adds its base's SEQ index in *qo as well: the same walk, the same tests in the
+// same order; *qi and *qo are untouched for any other result.
+MDX_PU_FN int mdx_pileup_site_quality_at(const MdxPileupKey &k, const MdxPileupRecord &r, int64_t p, uint32_t noqual, uint32_t *qi, uint32_t *qo) {
+    int64_t at = r.pos, x = 0;
+    for (uint32_t c = r.c0; c < r.c1; c++) {
+        const uint32_t w = k.cigar[c], op = w & 15u;
+        const int64_t ln = (int64_t)(w >> 4);
+        if (MDX_PU_IS_REF(op)) {
+            if (p < at + ln) {
+                if (p < at) return MDX_PILEUP_NOTHING;
+                if (op == 2u) return MDX_PILEUP_DELETIONS;
+                if (op == 3u) return MDX_PILEUP_NOTHING;
+                const int64_t q = x + (p - at);
+                if (mdx_pileup_masked(r, q)) return MDX_PILEUP_MASKED;
+                if (q >= (int64_t)r.n_seq) return MDX_PILEUP_OTHER;
+                const uint32_t base = mdx_pileup_base(k, r, (uint32_t)q);
+                if (base > 3u) return MDX_PILEUP_OTHER;
+                uint32_t quality = noqual;
+                if (r.has_qual) {
+                    quality = (uint32_t)k.qual[r.s0 + (uint32_t)q];
+                    if (quality < k.min_qual) return MDX_PILEUP_LOWQUAL;
+                    if (quality > (uint32_t)(MDX_GL_QUALITIES - 1)) quality = (uint32_t)(MDX_GL_QUALITIES - 1);
+                }
+                *qi = quality;
+                *qo = (uint32_t)q;
+                return (int)(base + 4u * r.rev);
+            }
+            at += ln;
+        }
+        if (MDX_PU_IS_QRY(op)) x += ln;
+    }
+    return MDX_PILEUP_NOTHING;
+}
+
+// the rows (0 .. n_rows - 1) of the 5' and of the 3' rates for base q (q < n_seq) of the opened record
+MDX_PU_FN void mdx_pileup_damage_rows(const MdxPileupRecord &r, uint32_t q, uint32_t n_rows, uint32_t *row5, uint32_t *row3) {
+    int64_t left = (int64_t)q - (int64_t)r.qs + 1, right = (int64_t)r.qe - (int64_t)q;
+    if (left < 1) left = 1;
+    if (right < 1) right = 1;
+    if (left > (int64_t)n_rows) left = (int64_t)n_rows;
+    if (right > (int64_t)n_rows) right = (int64_t)n_rows;
+    *row5 = (uint32_t)(r.rev ? right : left) - 1u;
+    *row3 = (uint32_t)(r.rev ? left : right) - 1u;
+}
+
+// where in the table the nine terms of a pair lie: its counter cls (0 .. 7), its quality qi (< 94) and its two rows (< n_rows)
+MDX_PU_FN size_t mdx_pileup_damage_entry(int cls, uint32_t qi, uint32_t row5, uint32_t row3, uint32_t n_rows) {
+    const uint32_t base = (uint32_t)cls & 3u, rev = (uint32_t)cls >> 2;
+    const bool ct = (base & 1u) != 0u;                  // C or T: the C>T channel; A or G: the G>A channel
+    // the channel's rate is the 5' end's where the record shows the molecule's strand (C>T forward, G>A reverse), else the 3' end's
+    const bool five = ct ? rev == 0u : rev != 0u;
+    const uint32_t end = five ? 0u : 1u, row = five ? row5 : row3;
+    return (((size_t)end * n_rows + row) * MDX_GL_QUALITIES + qi) * MDX_GLD_TERMS;
+}
+
+// which of the nine terms the observed base (0 .. 3) has under the genotype a1 a2
+MDX_PU_FN int mdx_pileup_damage_term(uint32_t base, int a1, int a2) {
+    const bool ct = (base & 1u) != 0u;
+    const int s = ct ? 1 : 2, t = ct ? 3 : 0;
+    const int ns = (a1 == s ? 1 : 0) + (a2 == s ? 1 : 0), nt = (a1 == t ? 1 : 0) + (a2 == t ? 1 : 0);
+    if ((int)base == s) return ns == 2 ? MDX_GLD_S_SS : ns == 1 ? MDX_GLD_S_SX : MDX_GLD_S_NO;
+    if (nt == 2) return MDX_GLD_T_TT;
+    if (nt == 1 && ns == 1) return MDX_GLD_T_ST;
+    if (ns == 2) return MDX_GLD_T_SS;
+    if (nt == 1) return MDX_GLD_T_TX;
+    if (ns == 1) return MDX_GLD_T_SX;
+    return MDX_GLD_T_NO;
+}
+
+// the likelihoods of a site from its sums S [MDX_GLD_SUMS] and its base counters c [8]
+MDX_PU_FN void mdx_pileup_likelihoods_damage(const int64_t *S, const uint32_t *c, int single_strand, int ref, int alt, int64_t *gl, uint8_t *best,
+                                             uint32_t *bases) {
+    bool plus, minus;
+    mdx_pileup_strands(single_strand, ref, alt, &plus, &minus);
+    uint32_t n = 0;
+    for (int b = 0; b < 4; b++) n += (plus ? c[b] : 0u) + (minus ? c[4 + b] : 0u);
+    int first = 0;
+    int64_t top = 0;
+    for (int g = 0; g < MDX_GL_GENOTYPES; g++) {
+        const int64_t v = (plus ? S[g] : 0) + (minus ? S[MDX_GL_GENOTYPES + g] : 0);
+        gl[g] = v;
+        if (g == 0 || v > top) { top = v; first = g; }
+    }
+    for (int g = 0; g < MDX_GL_GENOTYPES; g++) gl[g] -= top;
     *best = (uint8_t)first;
     *bases = n;
 }

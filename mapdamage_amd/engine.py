@@ -56,7 +56,7 @@ EXPORTS = (
     "mdx_dedup_begin", "mdx_dedup_mark", "mdx_dedup_counts", "mdx_dedup_histogram", "mdx_dedup_info",
     "mdx_depth_begin", "mdx_depth_add", "mdx_depth_finish", "mdx_depth_runs", "mdx_depth_fetch", "mdx_depth_info", "mdx_depth_regions",
     "mdx_pileup_begin", "mdx_pileup_add", "mdx_pileup_finish", "mdx_pileup_info",
-    "mdx_pileup_likelihoods_begin", "mdx_pileup_likelihoods_finish",
+    "mdx_pileup_likelihoods_begin", "mdx_pileup_likelihoods_finish", "mdx_pileup_likelihoods_damage_begin",
 )
 
 SEQ_ASCII, SEQ_4BIT, SEQ_4BITQ = 0, 1, 2      # include/mdx.h MDX_SEQ_*
@@ -233,6 +233,7 @@ def load_library(path=None):
     lib.mdx_pileup_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_pileup_info.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.mdx_pileup_likelihoods_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]
+    lib.mdx_pileup_likelihoods_damage_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
     lib.mdx_pileup_likelihoods_finish.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     if path is None:
         _lib = lib
@@ -645,14 +646,29 @@ class DamageEngine:
         if table.shape != (94, 3):
             raise ValueError("pileup_likelihoods_begin: the table is %r, not (94, 3)" % (table.shape,))
         self._check(self._lib.mdx_pileup_likelihoods_begin(self._ctx, _ptr(table), ctypes.c_int32(int(noqual_quality))))
+        self._pileup_sums = self.PILEUP_SUMS
+
+    PILEUP_DAMAGE_SUMS = 20     # [2 strands][10 genotypes]
+
+    def pileup_likelihoods_damage_begin(self, table, noqual_quality=30):
+        """The sites' zeroed sums of the damage-aware model, 160 bytes per site (include/mdx.h
+        ``mdx_pileup_likelihoods_damage_begin``): behind ``pileup_begin``, in front of the first ``pileup_add``, instead of
+        ``pileup_likelihoods_begin``.  ``table``: int64 [2][K + 1][94][9], ``pileup.damage_likelihood_table(profile)``;
+        ``noqual_quality``: the quality of a record without qualities, 1..93."""
+        table = np.ascontiguousarray(table, np.int64)
+        if table.ndim != 4 or table.shape[0] != 2 or table.shape[2:] != (94, 9):
+            raise ValueError("pileup_likelihoods_damage_begin: the table is %r, not (2, K + 1, 94, 9)" % (table.shape,))
+        self._check(self._lib.mdx_pileup_likelihoods_damage_begin(self._ctx, _ptr(table), ctypes.c_int32(table.shape[1]), ctypes.c_int32(int(noqual_quality))))
+        self._pileup_sums = self.PILEUP_DAMAGE_SUMS
 
     def pileup_likelihoods_finish(self, with_sums=True):
         """``(sums, gl, best, bases, counts)`` (``mdx_pileup_likelihoods_finish``): int64 [sites][24] — the terms HOM HET NO
-        summed per strand and base, None without ``with_sums`` —, int64 [sites][10] — the ten genotypes' log likelihoods minus
+        summed per strand and base; behind ``pileup_likelihoods_damage_begin`` [sites][20], the ten genotypes' terms summed per
+        strand; None without ``with_sums`` —, int64 [sites][10] — the ten genotypes' log likelihoods minus
         the site's largest, in units of 2^-24 —, the index of the best as uint8, the bases behind them as uint32, and a dict of
         the pairs that added and those of them from records without qualities."""
         n = getattr(self, "_n_pileup_sites", 0)
-        sums = np.zeros((max(1, n), self.PILEUP_SUMS), np.int64) if with_sums else None
+        sums = np.zeros((max(1, n), getattr(self, "_pileup_sums", self.PILEUP_SUMS)), np.int64) if with_sums else None
         gl = np.zeros((max(1, n), self.PILEUP_GENOTYPES), np.int64)
         best, bases, counts = np.zeros(max(1, n), np.uint8), np.zeros(max(1, n), np.uint32), np.zeros(2, np.uint64)
         self._check(self._lib.mdx_pileup_likelihoods_finish(self._ctx, _ptr(sums) if with_sums else None, _ptr(gl), _ptr(best), _ptr(bases), _ptr(counts)))

@@ -329,6 +329,16 @@ def build_parser():
                    help="with --pileup-likelihoods and sites that bring ref and alt: the BEAGLE genotype likelihood file of `angsd "
                         "-doGlf 2` — ref/ref, ref/alt, alt/alt per site, normalised — for PCAngsd, NGSadmix, ngsRelate; gzip if "
                         "PATH ends in .gz")
+    g.add_argument("--pileup-damage-profile", metavar="FILE", default=None,
+                   help="with --pileup-likelihoods: a misincorporation.txt, this program's or mapDamage's, usually that of a first run "
+                        "over the same file: its C>T rates by distance from the 5' end and G>A rates by distance from the 3' end enter "
+                        "the error model (as in ATLAS and snpAD), so a T over a C near a read's start counts as the deamination it "
+                        "probably is, and no base has to be masked.  Distances count query bases, as --pileup-mask-ends does.  "
+                        "pileup_damage_profile.tsv lists the rates used.  Takes 160 instead of 192 bytes of HBM per site.  Not beside "
+                        "--single-stranded")
+    g.add_argument("--pileup-damage-positions", metavar="K", type=int, default=None,
+                   help="with --pileup-damage-profile: the positions from either end that keep their own rate; every base further in "
+                        "takes the pooled rate of the positions K+1 and up (1..254 and below the table's --length; default 20)")
     g.add_argument("--pileup-single-strand-mode", action="store_true", default=False,
                    help="with --pileup-sites whose lines bring ref and alt: at a C/T site only the bases of reverse-strand records "
                         "are eligible, at a G/A site only those of forward-strand records (pileupCaller --singleStrandMode)")
@@ -534,6 +544,10 @@ def _check_pileup(parser, o):
     if with_likelihoods and not o.pileup_likelihoods:
         parser.error("%s need%s --pileup-likelihoods: the genotype likelihoods they belong to" % (" / ".join(with_likelihoods),
                                                                                                  "s" if len(with_likelihoods) == 1 else ""))
+    if o.pileup_damage_positions is not None and o.pileup_damage_profile is None:
+        parser.error("--pileup-damage-positions needs --pileup-damage-profile: the table whose positions it counts")
+    if o.pileup_damage_profile is not None and not o.pileup_likelihoods:
+        parser.error("--pileup-damage-profile needs --pileup-likelihoods: the genotype likelihoods whose error model it enters")
     if o.pileup_likelihoods and o.pileup_sites is None:
         parser.error("--pileup-likelihoods needs --pileup-sites: the list of sites the likelihoods are made at")
     if o.pileup_sites is None:
@@ -598,6 +612,27 @@ def _check_pileup(parser, o):
                 same = False
             if same:
                 parser.error("--pileup-beagle %s is the input file: the run would overwrite what it reads" % o.pileup_beagle)
+    if o.pileup_damage_profile is None:
+        return
+    if o.single_stranded:
+        parser.error("--pileup-damage-profile cannot be combined with --single-stranded: in such a library both ends deaminate C>T, "
+                     "and the rate of a base is a function of both its distances, which the profile's two rows per base do not give")
+    if o.filename is not None and not is_stream(o.filename):
+        try:
+            same = os.path.samefile(o.filename, o.pileup_damage_profile)
+        except OSError:
+            same = False
+        if same:
+            parser.error("--pileup-damage-profile %s is the input file: a misincorporation.txt is expected" % o.pileup_damage_profile)
+    o.pileup_damage_positions = pileup_files.GLD_DEFAULT_POSITIONS if o.pileup_damage_positions is None else o.pileup_damage_positions
+    if not 1 <= o.pileup_damage_positions <= pileup_files.GLD_MAX_POSITIONS:
+        parser.error("--pileup-damage-positions %d: 1..%d positions" % (o.pileup_damage_positions, pileup_files.GLD_MAX_POSITIONS))
+    try:
+        o.pileup_damage_profile_rows = pileup_files.read_damage_profile(o.pileup_damage_profile, o.pileup_damage_positions)
+    except (OSError, UnicodeDecodeError) as error:
+        parser.error("--pileup-damage-profile %s: %s" % (o.pileup_damage_profile, error))
+    except pileup_files.ProfileError as error:
+        parser.error("--pileup-damage-profile: %s" % error)
 
 
 def parse_args(argv):
@@ -1209,7 +1244,10 @@ def _tabulate_on_device(options, reader, ref, libraries, logger, ranks, stages):
             engine.pileup_begin(pileup.pos, pileup.off, pileup.alleles, min_basequal=options.pileup_min_basequal,
                                 mask_ends=options.pileup_mask_ends, call=options.pileup_call, seed=options.pileup_seed,
                                 min_depth=options.pileup_min_depth, single_strand=options.pileup_single_strand_mode)
-            if likelihoods:
+            profile = getattr(options, "pileup_damage_profile_rows", None)
+            if likelihoods and profile is not None:
+                engine.pileup_likelihoods_damage_begin(pileup_files.damage_likelihood_table(profile), options.pileup_noqual_quality)
+            elif likelihoods:
                 engine.pileup_likelihoods_begin(pileup_files.likelihood_table(), options.pileup_noqual_quality)
         stages.mark("reference resident")
         warned_about_quals = False
@@ -1433,6 +1471,10 @@ def _report_pileup(options, logger):
     if getattr(options, "pileup_beagle", None) is not None:
         pileup_files.write_beagle(options.pileup_beagle, names, sites, gl, bases)
     logger.info(pileup_files.likelihoods_log_line(values, bases, added))
+    profile = getattr(options, "pileup_damage_profile_rows", None)
+    if profile is not None:
+        (options.folder / "pileup_damage_profile.tsv").write_text(pileup_files.damage_profile_text(profile))
+        logger.info(pileup_files.damage_profile_log_line(profile))
     logger.debug("Pileup likelihoods: the files of %d sites formatted and written in %.3f s", len(sites), time.perf_counter() - t0)
 
 

@@ -311,3 +311,147 @@ def likelihoods_log_line(options, bases, counts):
     bases = np.asarray(bases, np.int64)
     return ("Pileup likelihoods: %d sites, %d with bases, %d base observations (%d from records without qualities, taken at %d)"
             % (len(bases), int((bases >= 1).sum()), counts["added"], counts["without_qualities"], options["noqual_quality"]))
+
+
+# ---------------------------------------------------------------------- --pileup-damage-profile
+GLD_TERMS, GLD_MAX_POSITIONS, GLD_DEFAULT_POSITIONS = 9, 254, 20
+DAMAGE_PROFILE_HEADER = "End\tPosition\tSubstitutions\tBases\tRate\n"
+PROFILE_ENDS = (("5p", "C", "C>T"), ("3p", "G", "G>A"))         # the end, its base column and its substitution column
+
+
+class ProfileError(ValueError):
+    """A misincorporation.txt that --pileup-damage-profile cannot take; the message names the file (and the line)."""
+
+
+class DamageProfile:
+    """``positions`` K; ``ends``: per end of PROFILE_ENDS its K + 1 rows ``(substitutions, bases, rate)``, the last the pooled
+    tail of the positions K + 1 .. ``largest``; a row without bases has the rate of the nearest row in front of it."""
+
+    def __init__(self, path, positions, largest, ends):
+        self.path, self.positions, self.largest, self.ends = path, positions, largest, ends
+
+    def rates(self, end):
+        return [row[2] for row in self.ends[end]]
+
+
+def parse_damage_profile(lines, positions=GLD_DEFAULT_POSITIONS, source="the damage profile"):
+    """A misincorporation.txt, this project's or mapDamage's: ``#`` lines and empty lines skipped, the first line left is the
+    header, the columns End, Pos, C, G, C>T and G>A found by name; C>T over C of the 5p rows and G>A over G of the 3p rows,
+    summed over samples, libraries and strands per position.  Raises ProfileError."""
+    sums = ({}, {})                 # per end {position: [substitutions, bases]}
+    column = None
+    for number, line in enumerate(lines, 1):
+        line = line.rstrip("\r\n")
+        if not line.strip() or line.startswith("#"):
+            continue
+        fields = line.split("\t")
+        if column is None:
+            names = {name: i for i, name in enumerate(fields)}
+            missing = [name for name in ("End", "Pos", "C", "G", "C>T", "G>A") if name not in names]
+            if missing:
+                raise ProfileError("%s, line %d: the header lacks the column%s %s" % (source, number, "s" if len(missing) > 1 else "", ", ".join(missing)))
+            column = names
+            continue
+        if len(fields) <= max(column[name] for name in ("End", "Pos", "C", "G", "C>T", "G>A")):
+            raise ProfileError("%s, line %d: %d fields, fewer than the header's" % (source, number, len(fields)))
+        end = fields[column["End"]]
+        if end not in ("5p", "3p"):
+            raise ProfileError("%s, line %d: End is %r, neither 5p nor 3p" % (source, number, end))
+        numbers = {}
+        for name in ("Pos", "C", "G", "C>T", "G>A"):
+            text = fields[column[name]]
+            if not text.isascii() or not text.isdigit():
+                raise ProfileError("%s, line %d: %s is %r, not a non-negative integer" % (source, number, name, text))
+            numbers[name] = int(text)
+        if numbers["Pos"] < 1:
+            raise ProfileError("%s, line %d: Pos is 0; positions count from 1" % (source, number))
+        for base, sub in (("C", "C>T"), ("G", "G>A")):
+            if numbers[sub] > numbers[base]:
+                raise ProfileError("%s, line %d: %s is %d, above the %d of %s" % (source, number, sub, numbers[sub], numbers[base], base))
+        which = 0 if end == "5p" else 1
+        _, base, sub = PROFILE_ENDS[which]
+        cell = sums[which].setdefault(numbers["Pos"], [0, 0])
+        cell[0] += numbers[sub]
+        cell[1] += numbers[base]
+    if column is None:
+        raise ProfileError("%s holds no header line" % source)
+    for which, (end, _, _) in enumerate(PROFILE_ENDS):
+        if not sums[which]:
+            raise ProfileError("%s holds no %s rows" % (source, end))
+    largest = max(max(sums[0]), max(sums[1]))
+    if not 1 <= positions <= GLD_MAX_POSITIONS:
+        raise ProfileError("--pileup-damage-positions %d: 1..%d positions" % (positions, GLD_MAX_POSITIONS))
+    if positions >= largest:
+        raise ProfileError("%s: --pileup-damage-positions %d needs positions beyond it for the tail, and the largest Pos is %d" % (source, positions, largest))
+    ends = []
+    for which, (end, base, sub) in enumerate(PROFILE_ENDS):
+        rows, rate = [], None
+        for z in range(1, positions + 2):
+            if z <= positions:
+                n_sub, n_base = sums[which].get(z, (0, 0))
+            else:
+                n_sub = sum(cell[0] for pos, cell in sums[which].items() if pos > positions)
+                n_base = sum(cell[1] for pos, cell in sums[which].items() if pos > positions)
+            if n_base:
+                rate = n_sub / n_base
+            elif rate is None:
+                raise ProfileError("%s: no %s at position 1 of the %s rows; the profile needs the rate of the first position" % (source, base, end))
+            rows.append((n_sub, n_base, rate))
+        ends.append(rows)
+    return DamageProfile(source, positions, largest, ends)
+
+
+def read_damage_profile(path, positions=GLD_DEFAULT_POSITIONS):
+    with open(path, newline="") as handle:
+        return parse_damage_profile(handle, positions, str(path))
+
+
+def damage_terms(r, q):
+    """The nine terms of a channel with rate ``r`` at quality ``q`` as ``round(term * 2^24)``: the observed source under ss, s and
+    another, no s; the observed product under tt, st, ss, t and another, s and another, neither.  Python doubles in exactly this
+    order (csrc/mdx_pileup_key.h)."""
+    e = min(0.75, 10.0 ** (-q / 10.0))
+    pss = (1.0 - r) * (1.0 - e) + r * (e / 3.0)
+    pst = r * (1.0 - e) + (1.0 - r) * (e / 3.0)
+    terms = (math.log(pss),
+             math.log(pss / 2.0 + (e / 3.0) / 2.0),
+             math.log(e / 3.0),
+             math.log(1.0 - e),
+             math.log(pst / 2.0 + (1.0 - e) / 2.0),
+             math.log(pst),
+             math.log((1.0 - e) / 2.0 + (e / 3.0) / 2.0),
+             math.log(pst / 2.0 + (e / 3.0) / 2.0),
+             math.log(e / 3.0))
+    return [round(math.ldexp(x, GL_SCALE_BITS)) for x in terms]
+
+
+def damage_likelihood_table(profile):
+    """int64 [2 ends][K + 1][94][9] for ``mdx_pileup_likelihoods_damage_begin``: ``damage_terms`` of every row's rate, end 0 the
+    5p C>T rates, end 1 the 3p G>A rates."""
+    plain = likelihood_table()
+    for q in range(GL_QUALITIES):
+        hom, het, no = plain[q].tolist()
+        # (without damage the model is the plain one: a zero profile reproduces --pileup-likelihoods bit for bit)
+        assert damage_terms(0.0, q) == [hom, het, no, hom, het, no, het, no, no], q
+    # (rows without bases repeat the rate in front of them: a rate's rows are made once)
+    rows = {rate: [damage_terms(rate, q) for q in range(GL_QUALITIES)] for rate in set(profile.rates(0) + profile.rates(1))}
+    table = np.array([[rows[rate] for rate in profile.rates(end)] for end in range(2)], np.int64)
+    assert table.shape == (2, profile.positions + 1, GL_QUALITIES, GLD_TERMS)
+    # (every probability is at least e / 3: no term is larger in magnitude than the plain table's, and its bound holds)
+    assert int(np.abs(table).max()) <= int(np.abs(plain).max()) and int(np.abs(table).max()) << 31 < 1 << 63
+    return table
+
+
+def damage_profile_text(profile):
+    """pileup_damage_profile.tsv: a line per row of either end, the tail as ``>K``."""
+    out = [DAMAGE_PROFILE_HEADER]
+    for (end, _, _), rows in zip(PROFILE_ENDS, profile.ends):
+        for z, (n_sub, n_base, rate) in enumerate(rows, 1):
+            out.append("%s\t%s\t%d\t%d\t%s\n" % (end, str(z) if z <= profile.positions else ">%d" % profile.positions, n_sub, n_base, "%.15g" % rate))
+    return "".join(out)
+
+
+def damage_profile_log_line(profile):
+    five, three = profile.rates(0), profile.rates(1)
+    return ("Pileup damage profile: %s, %d positions; 5p C>T %.6g at position 1, tail %.6g; 3p G>A %.6g, tail %.6g"
+            % (profile.path, profile.positions, five[0], five[-1], three[0], three[-1]))

@@ -14,12 +14,18 @@ with --likelihoods these instead of the last two:
   dense_gl        `--pileup-sites dense.txt --pileup-likelihoods`
 and then per list the difference to the same list without the option, and from the log the seconds the host took to format and
 write the likelihood files.
+With --damage-profile [FILE] only plain, parent_plain, sparse_gl, dense_gl and
+  sparse_gld      `--pileup-sites sparse.txt --pileup-likelihoods --pileup-damage-profile FILE`
+  dense_gld       `--pileup-sites dense.txt --pileup-likelihoods --pileup-damage-profile FILE`
+FILE by default the misincorporation.txt that `plain` has just written (the two-run workflow); and per list the difference to
+the same list under --pileup-likelihoods alone.
 
 Reported per command: the wall times, their median and spread (max - min); the medians' differences from `plain`, and
 plain - parent_plain; from the log the option's line.  The claim to check: plain - parent_plain is within the repeats' spread
 (nothing new runs when the option is off).  One JSON line on stdout.
 
-    python tools/pileup_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR] [--likelihoods]"""
+    python tools/pileup_bench.py [--reads N] [--repeats K] [--duplicate-rate RATE] [--dir DIR] [--timeout S] [--parent-root DIR] [--likelihoods]
+                                  [--damage-profile [FILE]]"""
 import argparse
 import json
 import os
@@ -67,6 +73,8 @@ def main():
     ap.add_argument("--timeout", type=int, default=300, help="seconds each timed command may take")
     ap.add_argument("--parent-root", help="a built checkout of the parent commit: `plain` is timed there as well")
     ap.add_argument("--likelihoods", action="store_true", help="time --pileup-likelihoods on either list instead of sparse_masked and write_kept")
+    ap.add_argument("--damage-profile", nargs="?", const="", default=None, metavar="FILE",
+                    help="time --pileup-likelihoods with and without --pileup-damage-profile FILE on either list (FILE: by default plain's misincorporation.txt)")
     args = ap.parse_args()
     import numpy as np
 
@@ -94,8 +102,16 @@ def main():
         legs = [("plain", ROOT, [])]
         if args.parent_root:
             legs.append(("parent_plain", os.path.abspath(args.parent_root), []))
-        legs += [("sparse", ROOT, ["--pileup-sites", sparse]), ("dense", ROOT, ["--pileup-sites", dense])]
-        if args.likelihoods:
+        if args.damage_profile is not None:
+            profile = args.damage_profile or os.path.join(work, "plain", "misincorporation.txt")
+            for name, sites in (("sparse", sparse), ("dense", dense)):
+                legs += [(name + "_gl", ROOT, ["--pileup-sites", sites, "--pileup-likelihoods"]),
+                         (name + "_gld", ROOT, ["--pileup-sites", sites, "--pileup-likelihoods", "--pileup-damage-profile", profile])]
+        else:
+            legs += [("sparse", ROOT, ["--pileup-sites", sparse]), ("dense", ROOT, ["--pileup-sites", dense])]
+        if args.damage_profile is not None:
+            pass
+        elif args.likelihoods:
             legs += [("sparse_gl", ROOT, ["--pileup-sites", sparse, "--pileup-likelihoods"]), ("dense_gl", ROOT, ["--pileup-sites", dense, "--pileup-likelihoods"])]
         else:
             legs += [("sparse_masked", ROOT, ["--pileup-sites", sparse, "--pileup-min-basequal", "20", "--pileup-mask-ends", "2,2"]),
@@ -131,11 +147,17 @@ def main():
                 m = re.search(r"Pileup likelihoods: the files of \d+ sites formatted and written in ([0-9.]+) s", log)
                 result[name].update(likelihoods_log_line=line.group(0), likelihoods_format_s=float(m.group(1)),
                                     likelihoods_tsv_bytes=os.path.getsize(os.path.join(work, name, "pileup_likelihoods.tsv")))
+            line = re.search(r"Pileup damage profile: .*", log)
+            if line:
+                result[name]["damage_profile_log_line"] = line.group(0)
         if status == 0:
             for name, _, _ in legs:
                 if name not in ("plain", "parent_plain"):
                     result["%s_minus_plain_s" % name] = round(result[name]["median_s"] - result["plain"]["median_s"], 3)
-            if args.likelihoods:
+            if args.damage_profile is not None:
+                for name in ("sparse", "dense"):
+                    result["%s_gld_minus_%s_gl_s" % (name, name)] = round(result[name + "_gld"]["median_s"] - result[name + "_gl"]["median_s"], 3)
+            elif args.likelihoods:
                 for name in ("sparse", "dense"):
                     result["%s_gl_minus_%s_s" % (name, name)] = round(result[name + "_gl"]["median_s"] - result[name]["median_s"], 3)
             if args.parent_root:
